@@ -12,8 +12,9 @@ One "step" = one pass of the hot path over one batch: every one of the B instanc
 in HBM.  Episodes end every T steps; the batched reset (new reward weights) is part of the timed region.
 Instances shard across GPUs with no data-path collective (weak scaling: B per GPU fixed).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP events on the launch stream) and
-`cpu_baseline` (the C oracle port timed on the host cores; N=1 only).
+A plain run sets up, runs exactly W untimed and K timed steps, writes the last step's outputs when --dump-outputs DIR is given,
+and prints ONE JSON line (rank 0) with the headline figure.  --full adds `roofline` (dominant kernel, HIP events on the launch
+stream), `cpu_baseline` (the C oracle port timed on the host cores; N=1 only) and the other measurements beside the headline.
 """
 import argparse
 import json
@@ -375,6 +376,37 @@ def launch_ranks(n, argv):
     return p.wait()
 
 
+DUMP_MAX_ELEMENTS = 400_000     # per array: 16 arrays at most, none above 3.2 MB, so a dump stays well under 64 MB
+
+
+def step_outputs(ro):
+    """What a caller of Rollout.step() receives from the last step (host numpy arrays): the sampled decision, the next observation
+    and masks, the rewards, and the trajectory slot that step wrote (scaled rewards, done, local critic values at act time);
+    the normalised advantages and value targets of the last hand-off when one has happened."""
+    env = ro.env
+    out = {"task": ro.task, "machine": ro.mach, "job": ro.job, "tasks_fea": env.tasks_fea, "adj_ell_col": env.ell_col,
+           "adj_ell_val": env.ell_val, "m_fea2": env.m_fea2, "info": env.info, "candidate": env.candidate, "job_mask": env.job_mask}
+    if ro.collect:
+        pos = (ro.buf_pos - 1) % ro.S                   # the slot of the last step (a finished buffer has wrapped buf_pos to 0)
+        e, t = divmod(pos, ro.T)
+        out.update(r4=ro.buf_r[pos], done=ro.buf_done[pos], job_v=ro.buf_jv[e, t], mach_v=ro.buf_mv[e, t])
+        if ro.last_adv is not None:
+            out.update(adv_norm=torch.stack(ro.last_adv[0]), adv_targets=torch.stack(ro.last_adv[1]))
+    return {k: v.detach().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(outputs, path):
+    """DIR/<name>.npy per array: floating arrays keep f32 / f64, integer ones become f64 (exact); an array above
+    DUMP_MAX_ELEMENTS is replaced by the same fixed seeded sample of its flattened elements in every run"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.asarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     global torch
     if len(sys.argv) >= 6 and sys.argv[1] == "--cpu-baseline-worker":
@@ -383,8 +415,8 @@ def main():
         return
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=720)
-    ap.add_argument("--warmup", type=int, default=360)
+    ap.add_argument("--steps", type=int, default=720, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=360, help="untimed steps before them")
     ap.add_argument("--batch", type=int, default=4096, help="instances per GPU")
     ap.add_argument("--size", default="6x6x2")
     ap.add_argument("--policy", default="auto", choices=["auto", "actor", "random"])
@@ -392,14 +424,19 @@ def main():
     ap.add_argument("--trajectory", default="advantage", choices=["advantage", "full"],
                     help="what the rollout records per step: the advantage inputs (rewards, dones, critic values) or every "
                          "field of the reference's ReplayBuffer (device-resident TrajectoryBuffer, SURVEY 8f N2)")
-    ap.add_argument("--min-seconds", type=float, default=0.5,
-                    help="the timed region repeats blocks of exactly --steps steps until it has lasted at least this long")
-    ap.add_argument("--min-warmup-seconds", type=float, default=1.0,
-                    help="the untimed warm-up lasts at least this long (extra steps beyond --warmup; 0 = exactly --warmup + 20 probe steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-env-sweep", action="store_true", help="skip the step-kernel batch sweep (N=1 only)")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the short legs of BASELINE configs 2 and 4's shard (N=1, headline size only)")
-    ap.add_argument("--no-full-handoff", action="store_true", help="skip the untimed full hand-off leg (N>1)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat blocks of --steps timed steps until they have lasted at least this long (default 0: exactly --steps)")
+    ap.add_argument("--min-warmup-seconds", type=float, default=0.0,
+                    help="extend the untimed warm-up until it has lasted at least this long (default 0: exactly --warmup steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure beside the headline: HIP-event kernel times and rooflines, the hand-off (N>1), the CPU "
+                         "baseline, the step-kernel batch sweep, --trajectory full and the BASELINE config legs (N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-env-sweep", action="store_true", help="--full without the step-kernel batch sweep (N=1 only)")
+    ap.add_argument("--no-config-legs", action="store_true", help="--full without the short legs of BASELINE configs 2 and 4's shard (N=1, headline size only)")
+    ap.add_argument("--no-full-handoff", action="store_true", help="--full without the untimed full hand-off leg (N>1)")
     ap.add_argument("--weights", default="random", choices=["random", "top1"],
                     help="actor weights: seeded random initialisation (default; throughput does not depend on the values unless a range "
                          "fallback trips, which encoder_status reports) or the reference's shipped J6M6E2 `top1` checkpoint (its tensors "
@@ -408,6 +445,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N` (N > 1): this process has not imported torch or touched a GPU; it starts the N ranks as a
         # CHILD torch.distributed.run (never an exec), relays rank 0's JSON line and exits with the child's return code
@@ -418,7 +457,7 @@ def main():
     if args.gpus != world:          # checked before the CPU legs and before torch is loaded: a mis-launched run exits at once
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     cpu_leg = None
-    if world == 1 and not args.no_cpu_baseline:        # before anything initialises the GPU or loads torch in this process
+    if args.full and world == 1 and not args.no_cpu_baseline:      # before anything initialises the GPU or loads torch in this process
         Jc, Mc, Ec = [int(x) for x in args.size.split("x")]
         cpu_leg = cpu_baseline_subprocess(Jc, Mc, Ec, args.batch)
     import torch as _torch
@@ -475,33 +514,36 @@ def main():
     for _ in range(args.warmup):
         ro.step()
     sync()
-    # a fresh box / first process needs more than a handful of steps to reach its steady state (lazy module loads, clock
-    # ramp): the untimed warm-up is extended to --min-warmup-seconds; the extra step count is agreed across ranks (the
-    # hand-off collective fires on a step count)
     warm_steps = args.warmup
-    t_probe0 = time.perf_counter()
-    for _ in range(20):
-        ro.step()
-    sync()
-    warm_steps += 20
-    per_step = agree_max((time.perf_counter() - t_probe0) / 20)
-    extra = int(agree_max(float(max(0, int(np.ceil((args.min_warmup_seconds - (time.perf_counter() - t_w0)) / max(per_step, 1e-6)))))))
-    extra = min(extra, 20000)
-    for _ in range(extra):
-        ro.step()
-    sync()
-    warm_steps += extra
-    # timed region: a whole number of blocks of --steps steps, bracketed by barrier + synchronize on both sides, long enough to
-    # last --min-seconds (the driver's --steps 20 is 7 ms of work: too short to time).  The block count comes from one untimed
-    # calibration block and is agreed across ranks, so every rank times the same number of steps.
+    if args.min_warmup_seconds > 0:
+        # a fresh box / first process needs more than a handful of steps to reach its steady state (lazy module loads, clock
+        # ramp): the untimed warm-up is extended to --min-warmup-seconds; the extra step count is agreed across ranks (the
+        # hand-off collective fires on a step count)
+        t_probe0 = time.perf_counter()
+        for _ in range(20):
+            ro.step()
+        sync()
+        warm_steps += 20
+        per_step = agree_max((time.perf_counter() - t_probe0) / 20)
+        extra = int(agree_max(float(max(0, int(np.ceil((args.min_warmup_seconds - (time.perf_counter() - t_w0)) / max(per_step, 1e-6)))))))
+        extra = min(extra, 20000)
+        for _ in range(extra):
+            ro.step()
+        sync()
+        warm_steps += extra
+    # timed region: a whole number of blocks of --steps steps (one by default), bracketed by barrier + synchronize on both sides.
+    # With --min-seconds the block count comes from one untimed calibration block and is agreed across ranks, so every rank
+    # times the same number of steps.
     handoffs0 = ro.n_handoffs
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        ro.step()
-    sync()
-    t_block = agree_max(time.perf_counter() - t0)
-    blocks = max(1, min(100000, int(np.ceil(1.15 * args.min_seconds / max(t_block, 1e-6)))))   # (margin: the calibration block runs a little slow)
+    blocks = 1
+    if args.min_seconds > 0:
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            ro.step()
+        sync()
+        t_block = agree_max(time.perf_counter() - t0)
+        blocks = max(1, min(100000, int(np.ceil(1.15 * args.min_seconds / max(t_block, 1e-6)))))   # (margin: the calibration block runs a little slow)
     sync()
     t0 = time.perf_counter()
     for _ in range(blocks * args.steps):
@@ -510,6 +552,8 @@ def main():
     elapsed_local = time.perf_counter() - t0
     elapsed = agree_max(elapsed_local)
     steps_timed = blocks * args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(ro), args.dump_outputs)
     per_rank_ms = None
     if dist is not None:                                # every rank's own time for the same timed region (the line's value uses the MAX)
         tl = torch.tensor([elapsed_local / steps_timed * 1e3], dtype=torch.float64, device="cpu" if one_device else "cuda")
@@ -517,23 +561,25 @@ def main():
         dist.all_gather(allt, tl)
         per_rank_ms = [float(x.item()) for x in allt]
     handoffs = ro.n_handoffs - handoffs0
-    # the advantage all-gather of the rollout -> update hand-off (the only collective of the data path) fires once per
-    # S = buffer_episodes*T steps; when the timed region was shorter than that (N > 1), run the steps up to the next hand-off
-    # now so that the RCCL exchange is exercised and measured (reported separately, not part of `value`)
     gather = ro.last_gather
-    if world > 1 and handoffs == 0 and ro.collect:
-        while ro.n_handoffs == handoffs0:
+    ktimes = prof_steps = None
+    if args.full:
+        # the advantage all-gather of the rollout -> update hand-off (the only collective of the data path) fires once per
+        # S = buffer_episodes*T steps; when the timed region was shorter than that (N > 1), run the steps up to the next hand-off
+        # now so that the RCCL exchange is exercised and measured (reported separately, not part of `value`)
+        if world > 1 and handoffs == 0 and ro.collect:
+            while ro.n_handoffs == handoffs0:
+                ro.step()
+            sync()
+            gather = ro.last_gather
+        # second pass with HIP events recorded on the launch stream around every kernel launch
+        # (kept out of the timed region above: two event records per launch would perturb `value`)
+        prof_steps = min(max(args.steps, T), 4 * T)
+        ro.timing_begin()
+        for _ in range(prof_steps):
             ro.step()
+        ktimes = ro.timing_end()
         sync()
-        gather = ro.last_gather
-    # second pass with HIP events recorded on the launch stream around every kernel launch
-    # (kept out of the timed region above: two event records per launch would perturb `value`)
-    prof_steps = min(max(args.steps, T), 4 * T)
-    ro.timing_begin()
-    for _ in range(prof_steps):
-        ro.step()
-    ktimes = ro.timing_end()
-    sync()
     ro.check_finished_cleanly()
     enc_status = None
     if ro.actor is not None:        # a fallback (time-out of the single-launch GIN kernel / f16 range) would be a silent performance cliff: say so
@@ -543,7 +589,7 @@ def main():
                       "range_fallbacks": n_range, "product_mode": mode, "rollout_restarts": ro.n_resident_failures}
 
     full_handoff = None
-    if world > 1 and policy == "actor" and not args.no_full_handoff:
+    if args.full and world > 1 and policy == "actor" and not args.no_full_handoff:
         try:
             del ro.traj
         except AttributeError:
@@ -554,41 +600,6 @@ def main():
         full_handoff = full_handoff_leg(rollout_mod, J, M, E, B, local_rank, rank, world, dist)
     if rank == 0:
         value = world * B * steps_timed / elapsed
-        # dominant kernel by measured device time
-        dom = max(ktimes, key=lambda k: ktimes[k]["ms_total"])
-        kd = ktimes[dom]
-        avg_s = kd["ms_total"] / max(kd["launches"], 1) * 1e-3
-        headline = (B, J, M) == (4096, 6, 6)
-        traffic_note = (f"profiles/{PMC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command at B=4096 J6M6E2, "
-                        "FETCH_SIZE x2 gfx950 correction; not re-measured inside this run)")
-
-        def env_roof(sec, name):
-            alg = B * env_bytes(J, M)
-            tr = pmc_traffic("env_step") if headline else None
-            d = {"kernel": name, "bound": "hbm", "achieved": alg / sec / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                 "frac": alg / sec / 1e9 / HBM_PEAK_GBPS, "frac_of_measured_copy_bw": alg / sec / 1e9 / HBM_MEASURED_GBPS,
-                 "traffic": tr, "traffic_source": traffic_note if tr is not None else None,
-                 "avg_launch_us": sec * 1e6, "algorithmic_bytes_per_launch": alg,
-                 "algorithmic_bytes_per_env_step": env_bytes(J, M), "env_steps_per_s": B / sec}
-            if tr is not None:      # the same launch priced on the bytes the incremental kernel really moves (PMC)
-                d["achieved_on_pmc_traffic_GBps"] = tr / sec / 1e9
-                d["frac_of_measured_copy_bw_on_pmc_traffic"] = tr / sec / 1e9 / HBM_MEASURED_GBPS
-            return d
-
-        if dom == "env_step":
-            roof = env_roof(avg_s, ro.env_kernel_name() + " (fused state transition + rewards + scaler + incremental observation + job mask)")
-            roof["launches"] = kd["launches"]
-        else:
-            roof = ro.roofline(dom, kd)
-            if headline:
-                roof["traffic"] = pmc_traffic(dom)
-                roof["traffic_source"] = traffic_note if roof["traffic"] is not None else None
-                if roof["traffic"] is not None:            # the HBM side of the same launch on the bytes it really moved (its `frac` is the matrix-core one)
-                    roof["achieved_GBps_on_pmc_traffic"] = roof["traffic"] / avg_s / 1e9
-                    roof["frac_hbm_on_pmc_traffic"] = roof["traffic"] / avg_s / 1e9 / HBM_PEAK_GBPS
-        # the north-star kernel is always reported as well (extra key)
-        ke = ktimes["env_step"]
-        roof_env = env_roof(ke["ms_total"] / max(ke["launches"], 1) * 1e-3, ro.env_kernel_name())
         out = {
             "metric": "env-steps/sec (batched J%dM%dE%d)" % (J, M, E), "value": value, "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / steps_timed * 1e3,
@@ -597,11 +608,9 @@ def main():
             "config": {"workload": f"J{J}M{M}E{E}, {B} parallel instances per GPU ({ro.instances_desc}), {ro.describe()}",
                        "instances_per_gpu": B, "obs_dtype": args.obs, "policy": policy, "trajectory": args.trajectory,
                        "parallelism": f"instances sharded over {world} GPU(s); env/encoder path has no collective; one all-gather of advantages per {ro.S}-step buffer (RCCL when world>1)"},
-            "roofline": roof, "roofline_env_step": roof_env,
             "handoff": {"buffer_steps": ro.S, "handoffs_in_timed_region": handoffs, "world": (gather or {}).get("world"),
                         "allgather_bytes_per_rank": (gather or {}).get("bytes_per_rank"), "allgather_ms": (gather or {}).get("ms"),
                         "what": "local-critic GAE (4 reverse scans) + ONE packed all-gather of the 4 advantage tensors [4,S,B] f32 + global normalisation"},
-            "kernel_times_ms": {k: v for k, v in ktimes.items()}, "kernel_times_steps": prof_steps,
             "encoder_status": enc_status,
             "weights": "seeded random initialisation (encoder.random_init_weights)" if weights is None else "the reference's shipped J6M6E2 top1 checkpoint (tests/golden/encoder_j6m6e2_top1.npz)",
         }
@@ -610,71 +619,107 @@ def main():
             out["handoff"]["allgather_GBps_per_rank"] = ((gather or {}).get("bytes_per_rank") or 0) * (world - 1) / max((gather or {}).get("ms") or 1e30, 1e-9) / 1e6 if gather else None
         if full_handoff is not None:
             out["handoff_full"] = full_handoff
-        # the two latency chains beside the dominant kernel (round-3 review: "no roofline at all"): matrix time and LDS traffic bound
-        heads = {}
-        for fam in ("heads", "heads_gat3", "heads_gat3_heads", "gat3"):
-            if fam in ktimes and ktimes[fam]["launches"]:
+        if args.full:
+            # dominant kernel by measured device time
+            dom = max(ktimes, key=lambda k: ktimes[k]["ms_total"])
+            kd = ktimes[dom]
+            avg_s = kd["ms_total"] / max(kd["launches"], 1) * 1e-3
+            headline = (B, J, M) == (4096, 6, 6)
+            traffic_note = (f"profiles/{PMC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command at B=4096 J6M6E2, "
+                            "FETCH_SIZE x2 gfx950 correction; not re-measured inside this run)")
+
+            def env_roof(sec, name):
+                alg = B * env_bytes(J, M)
+                tr = pmc_traffic("env_step") if headline else None
+                d = {"kernel": name, "bound": "hbm", "achieved": alg / sec / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                     "frac": alg / sec / 1e9 / HBM_PEAK_GBPS, "frac_of_measured_copy_bw": alg / sec / 1e9 / HBM_MEASURED_GBPS,
+                     "traffic": tr, "traffic_source": traffic_note if tr is not None else None,
+                     "avg_launch_us": sec * 1e6, "algorithmic_bytes_per_launch": alg,
+                     "algorithmic_bytes_per_env_step": env_bytes(J, M), "env_steps_per_s": B / sec}
+                if tr is not None:      # the same launch priced on the bytes the incremental kernel really moves (PMC)
+                    d["achieved_on_pmc_traffic_GBps"] = tr / sec / 1e9
+                    d["frac_of_measured_copy_bw_on_pmc_traffic"] = tr / sec / 1e9 / HBM_MEASURED_GBPS
+                return d
+
+            if dom == "env_step":
+                roof = env_roof(avg_s, ro.env_kernel_name() + " (fused state transition + rewards + scaler + incremental observation + job mask)")
+                roof["launches"] = kd["launches"]
+            else:
+                roof = ro.roofline(dom, kd)
+                if headline:
+                    roof["traffic"] = pmc_traffic(dom)
+                    roof["traffic_source"] = traffic_note if roof["traffic"] is not None else None
+                    if roof["traffic"] is not None:            # the HBM side of the same launch on the bytes it really moved (its `frac` is the matrix-core one)
+                        roof["achieved_GBps_on_pmc_traffic"] = roof["traffic"] / avg_s / 1e9
+                        roof["frac_hbm_on_pmc_traffic"] = roof["traffic"] / avg_s / 1e9 / HBM_PEAK_GBPS
+            # the north-star kernel is always reported as well (extra key)
+            ke = ktimes["env_step"]
+            roof_env = env_roof(ke["ms_total"] / max(ke["launches"], 1) * 1e-3, ro.env_kernel_name())
+            out.update({"roofline": roof, "roofline_env_step": roof_env,
+                        "kernel_times_ms": {k: v for k, v in ktimes.items()}, "kernel_times_steps": prof_steps})
+            # the two latency chains beside the dominant kernel (round-3 review: "no roofline at all"): matrix time and LDS traffic bound
+            heads = {}
+            for fam in ("heads", "heads_gat3", "heads_gat3_heads", "gat3"):
+                if fam in ktimes and ktimes[fam]["launches"]:
+                    try:
+                        heads[fam] = ro.roofline(fam, ktimes[fam])
+                    except Exception as ex:
+                        heads[fam] = {"error": repr(ex)}
+            if heads:
+                out["roofline_heads"] = heads
+            if world == 1 and policy == "actor" and args.trajectory == "advantage" and not args.no_config_legs:
+                # the same rollout with the complete device trajectory buffer (every field of the reference's ReplayBuffer):
+                # its cost under the driver's clock, as an extra key (`value` stays the advantage-inputs trajectory BASELINE's metric names)
                 try:
-                    heads[fam] = ro.roofline(fam, ktimes[fam])
-                except Exception as ex:
-                    heads[fam] = {"error": repr(ex)}
-        if heads:
-            out["roofline_heads"] = heads
-        full_rate = None
-        if world == 1 and policy == "actor" and args.trajectory == "advantage" and not args.no_config_legs:
-            # the same rollout with the complete device trajectory buffer (every field of the reference's ReplayBuffer):
-            # its cost under the driver's clock, as an extra key (`value` stays the advantage-inputs trajectory BASELINE's metric names)
-            try:
-                del ro.traj
-            except AttributeError:
-                pass
-            ro2 = rollout_mod.Rollout(J, M, E, B, device=local_rank, policy=policy, obs_dtype=args.obs, instance_seed=0, rank=rank, world=world, collect="full")
-            for _ in range(2 * T):
-                ro2.step()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            nfull = 10 * T
-            for _ in range(nfull):
-                ro2.step()
-            torch.cuda.synchronize()
-            dtf = time.perf_counter() - t0
-            full_rate = {"value": B * nfull / dtf, "unit": "env-steps/s", "ms_per_step": dtf / nfull * 1e3, "steps_timed": nfull,
-                         "what": "--trajectory full: the device-resident TrajectoryBuffer records every field of the reference's ReplayBuffer per step"}
-            del ro2
-            torch.cuda.empty_cache()
-            out["trajectory_full"] = full_rate
-        if world == 1 and not args.no_env_sweep:
-            del ro
-            torch.cuda.empty_cache()
-            sweep = [env_kernel_large_batch(J, M, E, local_rank, B=b, episodes=1 if b >= 65536 else 2) for b in (4096, 16384, 65536, 262144)]
-            out["roofline_env_step_batch_sweep"] = sweep
-            out["roofline_env_step_large_batch"] = sweep[-1]
-            if B == sweep[0]["instances"]:
-                # SURVEY 8(d)'s denominator for the step kernel as it runs INSIDE the rollout (the sweep's figure is the kernel alone)
-                c16 = sweep[0]["same_footprint_copy"]["access_16B"]["avg_launch_us"]
-                out["roofline_env_step"]["same_footprint_copy_us"] = c16
-                out["roofline_env_step"]["frac_of_same_footprint_copy"] = c16 / out["roofline_env_step"]["avg_launch_us"]
-                ko = footprint_kernel_only(B, J, M, E, out["roofline_env_step"]["kernel"])
-                if ko:                                             # the figure to quote: both durations kernel-only (see footprint_kernel_only)
-                    out["roofline_env_step"]["frac_of_same_footprint_copy_kernel_only"] = ko["frac"]
-                    out["roofline_env_step"]["kernel_only"] = ko
-        if world == 1 and headline and policy == "actor" and not args.no_config_legs:
-            legs = {}
-            for name, (cj, cm, ce, cb) in (("J10M10E2_x8192", (10, 10, 2, 8192)), ("J20M20E4_x2048", (20, 20, 4, 2048))):
-                try:
-                    legs[name] = config_leg(rollout_mod, cj, cm, ce, cb, local_rank)
-                except Exception as ex:
-                    legs[name] = {"error": repr(ex)}
-            out["configs"] = legs
-        if cpu_leg is not None:
-            # like for like: the CPU figure is the ENVIRONMENT alone; so is gpu_env_only (the step kernel's own rate, HIP events around the
-            # launch, inside the rollout).  `value` of the line is the FULL rollout step (both actor forwards included) — not the pair to compare.
-            if "error" not in cpu_leg:
-                cpu_leg["gpu_env_only_env_steps_per_s"] = roof_env["env_steps_per_s"]
-                cpu_leg["gpu_env_only_over_cpu"] = roof_env["env_steps_per_s"] / cpu_leg["value"]
-                cpu_leg["gpu_full_rollout_env_steps_per_s"] = value
-                cpu_leg["compare"] = "value (CPU, environment only) with gpu_env_only_env_steps_per_s; gpu_full_rollout_env_steps_per_s is the line's `value` and includes both actor forwards"
-            out["cpu_baseline"] = cpu_leg
+                    del ro.traj
+                except AttributeError:
+                    pass
+                ro2 = rollout_mod.Rollout(J, M, E, B, device=local_rank, policy=policy, obs_dtype=args.obs, instance_seed=0, rank=rank, world=world, collect="full")
+                for _ in range(2 * T):
+                    ro2.step()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                nfull = 10 * T
+                for _ in range(nfull):
+                    ro2.step()
+                torch.cuda.synchronize()
+                dtf = time.perf_counter() - t0
+                out["trajectory_full"] = {"value": B * nfull / dtf, "unit": "env-steps/s", "ms_per_step": dtf / nfull * 1e3, "steps_timed": nfull,
+                                          "what": "--trajectory full: the device-resident TrajectoryBuffer records every field of the reference's ReplayBuffer per step"}
+                del ro2
+                torch.cuda.empty_cache()
+            if world == 1 and not args.no_env_sweep:
+                del ro
+                torch.cuda.empty_cache()
+                sweep = [env_kernel_large_batch(J, M, E, local_rank, B=b, episodes=1 if b >= 65536 else 2) for b in (4096, 16384, 65536, 262144)]
+                out["roofline_env_step_batch_sweep"] = sweep
+                out["roofline_env_step_large_batch"] = sweep[-1]
+                if B == sweep[0]["instances"]:
+                    # SURVEY 8(d)'s denominator for the step kernel as it runs INSIDE the rollout (the sweep's figure is the kernel alone)
+                    c16 = sweep[0]["same_footprint_copy"]["access_16B"]["avg_launch_us"]
+                    out["roofline_env_step"]["same_footprint_copy_us"] = c16
+                    out["roofline_env_step"]["frac_of_same_footprint_copy"] = c16 / out["roofline_env_step"]["avg_launch_us"]
+                    ko = footprint_kernel_only(B, J, M, E, out["roofline_env_step"]["kernel"])
+                    if ko:                                             # the figure to quote: both durations kernel-only (see footprint_kernel_only)
+                        out["roofline_env_step"]["frac_of_same_footprint_copy_kernel_only"] = ko["frac"]
+                        out["roofline_env_step"]["kernel_only"] = ko
+            if world == 1 and headline and policy == "actor" and not args.no_config_legs:
+                legs = {}
+                for name, (cj, cm, ce, cb) in (("J10M10E2_x8192", (10, 10, 2, 8192)), ("J20M20E4_x2048", (20, 20, 4, 2048))):
+                    try:
+                        legs[name] = config_leg(rollout_mod, cj, cm, ce, cb, local_rank)
+                    except Exception as ex:
+                        legs[name] = {"error": repr(ex)}
+                out["configs"] = legs
+            if cpu_leg is not None:
+                # like for like: the CPU figure is the ENVIRONMENT alone; so is gpu_env_only (the step kernel's own rate, HIP events around the
+                # launch, inside the rollout).  `value` of the line is the FULL rollout step (both actor forwards included) — not the pair to compare.
+                if "error" not in cpu_leg:
+                    cpu_leg["gpu_env_only_env_steps_per_s"] = roof_env["env_steps_per_s"]
+                    cpu_leg["gpu_env_only_over_cpu"] = roof_env["env_steps_per_s"] / cpu_leg["value"]
+                    cpu_leg["gpu_full_rollout_env_steps_per_s"] = value
+                    cpu_leg["compare"] = "value (CPU, environment only) with gpu_env_only_env_steps_per_s; gpu_full_rollout_env_steps_per_s is the line's `value` and includes both actor forwards"
+                out["cpu_baseline"] = cpu_leg
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -17,7 +17,7 @@ def test_bench_runs_with_two_ranks_and_reports_the_handoff():
     env = dict(os.environ, MTFJSP_BENCH_ONE_DEVICE="1", MTFJSP_NO_RESIDENT_GIN="1")   # (streaming GIN: two resident grids on one GPU only time out)
     # the plain form the driver uses: bench.py starts its two ranks itself (a child torch.distributed.run on 127.0.0.1)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "10", "--batch", "256",
-           "--min-seconds", "0.05", "--min-warmup-seconds", "0.1"]
+           "--min-seconds", "0.05", "--min-warmup-seconds", "0.1", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]

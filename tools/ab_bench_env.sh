@@ -8,7 +8,7 @@ out=gpurun_out/${tag}_ab_${var}.txt
 for r in $(seq 1 $reps); do
   for v in on off; do
     if [ $v = off ]; then export $var=1; else unset $var; fi
-    python bench.py --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python3 -c "
+    python bench.py --full --min-seconds 0.5 --min-warmup-seconds 1 --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 kt=d.get('kernel_times_ms',{})

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 $reps); do
   for v in tail separate; do
     if [ $v = tail ]; then export MTFJSP_FUSED_ENV3=1; else unset MTFJSP_FUSED_ENV3; fi
-    python bench.py --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python3 -c "
+    python bench.py --full --min-seconds 0.5 --min-warmup-seconds 1 --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 kt=d.get('kernel_times_ms',{})

@@ -4,7 +4,7 @@
 for i in 1 2 3; do
   for lib in "$@"; do
     if [ -n "$lib" ]; then export MTFJSP_LIB=$PWD/e2e-mappo-for-mt-fjsp_amd/$lib; else unset MTFJSP_LIB; fi
-    python bench.py --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --min-seconds 0.5 --min-warmup-seconds 1 --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python -c "
 import sys,json,os
 d=json.loads(sys.stdin.read())
 k=d['kernel_times_ms']

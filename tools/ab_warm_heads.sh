@@ -1,7 +1,7 @@
 for i in 1 2 3; do
   for v in 1 0; do
     if [ $v = 1 ]; then export MTFJSP_NO_WARM_HEADS=1; else unset MTFJSP_NO_WARM_HEADS; fi
-    python bench.py --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --min-seconds 0.5 --min-warmup-seconds 1 --no-cpu-baseline --no-env-sweep --no-config-legs 2>/dev/null | tail -1 | python -c "
 import sys,json,os
 d=json.loads(sys.stdin.read())
 k=d['kernel_times_ms']

@@ -6,9 +6,9 @@ rm -f gpurun_out/encoder_errors_observed.json
 timeout 3000 python -m pytest tests -q -m gpu 2>&1 | tail -12
 bash tools/profile_rollout.sh $tag 2>&1 | tail -14
 python - "$tag" <<'PY'
-import json, sys
+import json, os, sys
 tag = sys.argv[1]
-d = json.loads(open(f"gpurun_out/{tag}_bench.json").read().strip().splitlines()[-1])
+d = json.loads(open(os.path.join(os.environ.get("OUT_DIR", "tool_out"), f"{tag}_bench.json")).read().strip().splitlines()[-1])
 print("value %.3f M" % (d["value"] / 1e6), "ms/step %.4f" % d["ms_per_step"], {k: round(v["ms_total"] / max(v["launches"], 1) * 1e3, 2) for k, v in d["kernel_times_ms"].items()})
 for s in d.get("roofline_env_step_batch_sweep", []):
     print(s["instances"], s["kernel"], "%.2f us" % s["avg_launch_us"], "copy 16B %.2f us (grid %d) 8B %.2f us -> frac %.3f / %.3f" % (
