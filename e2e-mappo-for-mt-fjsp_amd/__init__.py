@@ -9,4 +9,4 @@ The directory name contains '-' and is therefore imported through importlib:
     import importlib; pkg = importlib.import_module("e2e-mappo-for-mt-fjsp_amd")
 or via the root-level alias module `mtfjsp_amd`.
 """
-__all__ = ["capi", "batch_env", "parallel_env", "instances", "encoder", "rollout", "dist"]
+__all__ = ["capi", "batch_env", "parallel_env", "instances", "encoder", "rollout", "dist", "baselines"]

@@ -30,6 +30,7 @@ class DeviceBatchEnv:
         self.L = capi.lib()
         self.J, self.M, self.E, self.B = int(n_job), int(n_machine), int(n_edge), int(batch)
         self.T = self.J * self.M
+        self.left_shift = bool(left_shift)
         self.obs_f32 = obs_dtype in ("f32", torch.float32, np.float32)
         self.device = torch.device("cuda", device)
         cfg = capi.Config(self.J, self.M, self.E, self.B, int(bool(left_shift)), capi.OBS_F32 if self.obs_f32 else capi.OBS_F64,

@@ -72,6 +72,7 @@ PROTOTYPES = {
     "mtfjsp_pack_views": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "mtfjsp_observe_mfea1": (_I, [_VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_random_actions": (_I, [_VP, _U64, _U64, _VP, _VP, _VP]),
+    "mtfjsp_pdr_plan": (_I, [_VP, _VP, _VP, _VP, _U64, _VP, _VP]),
     "mtfjsp_export_dense_adj": (_I, [_VP, _VP]),
     "mtfjsp_export_dense_adj_host": (_I, [_VP, _VP]),
     "mtfjsp_valid_action_mask": (_I, [_VP, _VP]),

@@ -1515,18 +1515,8 @@ static size_t gat3x_lds_bytes() { return (size_t)8 * 2 * 4 * 64 * 16 + (size_t)8
 // barrier, the next weight is requested while the current one is multiplied), is reused for every tile, and the eight
 // waves load the MFMA pipes evenly (512 products each).  Only activations live in LDS: every A tile is read by all waves
 // and every intermediate is written back as the next product's A tile (three barriers per chunk of 8 tiles).
-// Philox4x32-10 (counter-based; Salmon et al. 2011) and the categorical / greedy pick shared by k_sample and the fused
+// Philox4x32-10 (philox4x32, mtfjsp_env_dev.h) and the categorical / greedy pick shared by k_sample and the fused
 // selection at the end of k_heads (agent:22-72): p[0..n) with stride 1.
-__device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 // the uniform number of instance b's draw (the part of pick_action that does not depend on the probabilities: k_headsx forms it early)
 __device__ __forceinline__ float pick_uniform(int b, uint64_t seed, uint64_t counter)
 {

@@ -34,23 +34,6 @@
 // ---------------------------------------------------------------------------------------------
 // numpy float64 add.reduce order: 0 + pairwise_sum (8 accumulators, 128-element leaf blocks).
 // env:896 np.sum(pt_est) and pe:176-183 np.mean use it; restated so e1/r_pt are bit-identical.
-__device__ __forceinline__ double pw_leaf(const double *a, int n)
-{
-    if (n < 8) {
-        double r = 0.0;
-        for (int i = 0; i < n; i++) r += a[i];
-        return r;
-    }
-    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
-        r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < n; i++) res += a[i];
-    return res;
-}
 template <int DEPTH>
 __device__ __noinline__ double pw_sum(const double *a, int n)
 {
@@ -122,17 +105,6 @@ __device__ __forceinline__ int wave_scan_incl(int x)
     return x;
 }
 
-// Philox4x32-10 (counter-based; Salmon et al. 2011)
-__device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 // env.generate_random_weights("01") (env:1253-1259) of instance b: three uniforms in [0,1), normalised by their sum (numpy's sum of three =
 // left-to-right adds).  53-bit uniforms like python's random.random(): (a >> 5, b >> 6) -> (a*2^26 + b) / 2^53.
 __device__ __forceinline__ void draw_w3(int b, uint64_t seed, uint64_t episode, double (&w)[3])
@@ -1726,6 +1698,18 @@ struct mtfjsp_env {
 };
 
 static thread_local std::string g_create_err;
+
+// the handle as the library's other translation units see it (mtfjsp_env_dev.h)
+void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v)
+{
+    v->B = h->cfg.batch; v->J = h->cfg.n_job; v->M = h->cfg.n_machine; v->T = h->T; v->device_id = h->cfg.device_id;
+    v->loaded = h->loaded; v->t = h->t; v->p = h->p; v->stream = h->stream;
+}
+int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg)
+{
+    h->err = msg;
+    return code;
+}
 
 #define HIPCHK(h, call)                                                                         \
     do {                                                                                        \

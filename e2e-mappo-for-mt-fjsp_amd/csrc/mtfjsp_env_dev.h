@@ -81,3 +81,45 @@ __device__ __forceinline__ int up16_i(int x) { return (int)__builtin_amdgcn_perm
 __device__ __forceinline__ int up32_i(int x) { return (int)__builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false)[1]; }
 __device__ __forceinline__ double up16_d(double x) { return __hiloint2double(up16_i(__double2hiint(x)), up16_i(__double2loint(x))); }
 __device__ __forceinline__ double up32_d(double x) { return __hiloint2double(up32_i(__double2hiint(x)), up32_i(__double2loint(x))); }
+
+// numpy float64 add.reduce over one leaf block (n <= 128) of a contiguous row: plain left to right below 8 elements, 8 accumulators
+// from 8 on (numpy's pairwise_sum; the caller adds the reduction's initial 0)
+__device__ __forceinline__ double pw_leaf(const double *a, int n)
+{
+    if (n < 8) {
+        double r = 0.0;
+        for (int i = 0; i < n; i++) r += a[i];
+        return r;
+    }
+    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
+    int i = 8;
+    for (; i < n - (n % 8); i += 8) {
+        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
+        r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
+    }
+    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (; i < n; i++) res += a[i];
+    return res;
+}
+
+// Philox4x32-10 (counter-based; Salmon et al. 2011)
+__device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1)
+{
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// host side: what the library's other translation units (mtfjsp_pdr.hip) see of a handle; defined in mtfjsp_env.hip
+struct EnvHostView {
+    int B, J, M, T, device_id;
+    bool loaded;
+    const double *t, *p;               // [B,T,M] device instance arrays
+    hipStream_t stream;
+};
+__attribute__((visibility("hidden"))) void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v);
+__attribute__((visibility("hidden"))) int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg);   // sets mtfjsp_last_error, returns code

@@ -1,0 +1,47 @@
+#!/usr/bin/env python3
+"""The greedy policy and the 12 priority dispatch rules of the reference's test_all.py on the SAME instances, one table
+(paper Tables V / VI).  The instances are generated on the device; the rules are planned there by k_pdr_plan and replayed by the
+step kernel with left shift off, and only the policy's evaluation (which builds its own batch) reads the instances back.
+
+    python examples/pdr_baselines.py [--instances 1024] [--size 6 6 2]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mtfjsp_amd  # noqa: F401  (alias of the package directory)
+from importlib import import_module
+
+baselines = import_module("e2e-mappo-for-mt-fjsp_amd.baselines")
+batch_env = import_module("e2e-mappo-for-mt-fjsp_amd.batch_env")
+evaluate = import_module("e2e-mappo-for-mt-fjsp_amd.evaluate")
+encoder = import_module("e2e-mappo-for-mt-fjsp_amd.encoder")
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--instances", type=int, default=1024)
+ap.add_argument("--size", type=int, nargs=3, default=[6, 6, 2], metavar=("J", "M", "E"))
+a = ap.parse_args()
+(J, M, E), N = a.size, a.instances
+args = {"n_job": J, "n_machine": M, "n_edge": E, "weight_mk": 0.4, "weight_ec": 0.4, "weight_tt": 0.2}
+
+env = batch_env.DeviceBatchEnv(J, M, E, N, left_shift=False, obs_dtype="f32")
+env.generate_instances(seed=2024)
+torch.cuda.synchronize(); t0 = time.perf_counter()
+rules = baselines.pdr_baselines(None, None, None, None, args, env=env, seed=0)      # 12 rollouts of N on the generated batch
+t_rules = time.perf_counter() - t0
+
+t, p, tt, edge = env.read_instances()
+weights = encoder.random_init_weights(seed=0)            # or (torch.load(job_actor.pth), torch.load(machine_actor.pth))
+t0 = time.perf_counter()
+_, final4, obj = evaluate.validate_cost_batched(weights, t, p, tt, edge, args)
+t_policy = time.perf_counter() - t0
+
+print(f"{N} instances J{J}M{M}E{E}: 12 rules in {t_rules * 1e3:.1f} ms, greedy policy in {t_policy * 1e3:.1f} ms")
+print(f"{'method':<16}{'objective':>12}{'makespan':>12}{'energy':>12}{'transport':>12}{'idle':>12}")
+rows = [("policy (greedy)", final4, obj)] + [(name, rules[name][1], rules[name][2]) for name, _, _ in baselines.RULES]
+for name, f4, ob in rows:
+    print(f"{name:<16}{ob.mean():>12.2f}{f4[:, 0].mean():>12.2f}{f4[:, 1].mean():>12.2f}{f4[:, 2].mean():>12.2f}{f4[:, 3].mean():>12.2f}")

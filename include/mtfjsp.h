@@ -1,7 +1,8 @@
 /*
  * mtfjsp.h — C ABI of libmtfjsp.so: MI355X-native batched MT-FJSP disjunctive-graph
- * environment (reset / step / observe / masks) and the rollout forward passes of
- * the GIN + GAT actors.  This is the drop-in boundary for the hot path of
+ * environment (reset / step / observe / masks), the rollout forward passes of
+ * the GIN + GAT actors, and the planner of the dispatch-rule baselines ("pdrs:" =
+ * tester/pdrs.py).  This is the drop-in boundary for the hot path of
  * RKWin93/E2E-MAPPO-for-MT-FJSP; every entry point cites the reference interface
  * it replaces ("pe:" = trainer/parallel_env.py, "env:" = graph-jsp-env/src/
  * graph_jsp_env/disjunctive_graph_jsp_env_singlestep.py, "ppo:" =
@@ -178,6 +179,20 @@ int mtfjsp_observe_mfea1(mtfjsp_handle_t h, const int32_t *task_idx, const uint8
  * for perf runs"): job uniform over unmasked jobs of the bound job_mask, machine uniform over feasible ones. */
 int mtfjsp_random_actions(mtfjsp_handle_t h, uint64_t seed, uint64_t counter, int32_t *task_idx,
                           int32_t *mach_idx, int32_t *job_idx);
+
+/* ------------------------------------------------------------------ dispatch-rule baselines */
+/* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
+ * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"
+ * data type that pdrs:690-702 hard-codes); m_rule[b] in 0..1 = SPT (pdrs:46-52), SEC (pdrs:55-66); both device, [B] — rules are
+ * per instance, so one handle holding N instances 12 times carries all 12 pairs of test_all.py:484-540 through one rollout.
+ * mor_order device [B,M,J] (row = the job order of one column: MOR's random.shuffle, replayed) or NULL: drawn on the device, one
+ * Fisher-Yates per (instance, column) from the Philox stream keyed by (seed, instance, column).  task_out, mach_out device [B,T]:
+ * the (task, machine) of step s (pdrs:751-754), to be replayed through mtfjsp_step on a handle with left_shift = 0 (pdrs:669).
+ * Reads t, p from the handle's device instance arrays (loaded or generated).  The rule ids are read back and checked first (one
+ * small copy that synchronises the handle's stream): an id out of range returns MTFJSP_ERR_ARG and nothing is written.  The
+ * plan itself is one launch on the handle's stream. */
+int mtfjsp_pdr_plan(mtfjsp_handle_t h, const int32_t *o_rule, const int32_t *m_rule, const int32_t *mor_order, uint64_t seed,
+                    int32_t *task_out, int32_t *mach_out);
 
 /* ------------------------------------------------------------------ exports (compat / tests) */
 /* dense adj_wrk [B,T,T] f64, row = destination, diagonal 1 (env:2066-2073) — what pe:136 returns. */
