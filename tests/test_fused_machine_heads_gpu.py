@@ -12,6 +12,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from selection_check import assert_selection_exact  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 J, M, E, B = 6, 6, 2, 4096
 
@@ -66,6 +69,9 @@ def test_three_in_one_launch_equals_the_separate_launches_and_the_oracle(steps_b
     assert float((fused[2] - sep[2]).abs().max()) <= 2e-5 * max(1.0, float(sep[2].abs().max()))
     same = float((fused[3] == sep[3]).float().mean())
     assert same >= 0.999, same                                    # (a sampled index can only differ where the cumulative probabilities are within round-off of the draw)
+    # ... while each launch's index is exactly the model's pick from the probabilities THAT launch stored (tests/selection_check.py)
+    assert_selection_exact(fused[0], fused[3], fused[4], ro.actor.seed, 2 * ro.nsteps + 1, ro.actor.greedy, mask=env.mmask, form="three_in_one")
+    assert_selection_exact(sep[0], sep[3], sep[4], ro.actor.seed, 2 * ro.nsteps + 1, ro.actor.greedy, mask=env.mmask, form="k_headsx")
     # ... and the oracle of the machine actor on the inputs the launch used
     mo = eo.machine_actor_forward(ma, env.m_fea1.cpu().numpy(), env.m_fea2.cpu().numpy(), e.h_pooled_o.cpu().numpy(), env.mmask.cpu().numpy(), B, M)
     mscale = max(1.0, float(np.abs(mo["h_pooled"]).max()))
@@ -87,7 +93,7 @@ def test_three_in_one_launch_with_f64_observations_and_eight_machines(shape, obs
     env, e = ro.env, ro.actor.enc
     assert e.check()
     assert _one_decision(ro) == 1
-    fused = [x.clone() for x in (e.mch_prob, e.h_pooled_m, e.mach_v, ro.mach)]
+    fused = [x.clone() for x in (e.mch_prob, e.h_pooled_m, e.mach_v, ro.mach, ro.actor.mch_logp)]
     e.arm_selection(1, ro.actor.greedy, ro.actor.seed, 2 * ro.nsteps + 1, ro.mach, ro.actor.mch_logp)
     mprob, h_m, mach_v = e.machine_actor_forward(env.m_fea1, env.m_fea2, e.h_pooled_o, env.mmask)
     torch.cuda.synchronize()
@@ -95,6 +101,9 @@ def test_three_in_one_launch_with_f64_observations_and_eight_machines(shape, obs
     assert float((fused[0] - mprob).abs().max()) <= 2e-6
     assert float((fused[1] - h_m).abs().max()) <= 2e-6 * scale
     assert float((fused[3] == ro.mach).float().mean()) >= 0.999
+    assert_selection_exact(fused[0], fused[3], fused[4], ro.actor.seed, 2 * ro.nsteps + 1, ro.actor.greedy, mask=env.mmask, form="three_in_one")
+    assert_selection_exact(mprob, ro.mach, ro.actor.mch_logp, ro.actor.seed, 2 * ro.nsteps + 1, ro.actor.greedy, mask=env.mmask,
+                           form="k_headsx10" if m > 6 else "k_headsx")    # (16 instances x 8 machines: eight tiles per group)
     mo = eo.machine_actor_forward(ma, env.m_fea1.cpu().numpy().astype(np.float32), env.m_fea2.cpu().numpy().astype(np.float32), e.h_pooled_o.cpu().numpy(),
                                   env.mmask.cpu().numpy(), B, m)
     assert float(np.abs(fused[0].cpu().numpy() - mo["prob"]).max()) <= 1e-4
