@@ -175,7 +175,8 @@ class DeviceBatchEnv:
         return self._sp_buf if rc == 1 else None
 
     def gae(self, r, v, v_next, done, gamma, lam, out=None):
-        """un-normalised GAE advantages [S,B] for one reward channel (views with arbitrary (s,b) strides allowed for r/v/v_next)"""
+        """un-normalised GAE advantages [S,B] for one reward channel.  Only r / v / v_next may be strided views (arbitrary (s,b)
+        element strides); done and out must be contiguous [S,B] — out may be a contiguous slice of a larger packed buffer"""
         S = done.shape[0]
         if out is None:
             out = torch.empty(S, self.B, dtype=torch.float32, device=self.device)
