@@ -125,3 +125,106 @@ def pdr_baselines(t, p, tt, edge, args, rules=RULES, mor_order=None, seed=0, dev
         plans[name] = (task, mach)
     out[PLANS] = plans
     return out
+
+
+# ---- one-step look-ahead rules (csrc/mtfjsp_lookahead.hip): the dynamic half of the table.  (name, column of the raw rewards whose
+# one-step value decides: 2 idle time — the reference's LWKR_IT_o_jointActor, pdrs:465-540 —, 4 transport time, 1 makespan,
+# 3 energy, 0 the scalar reward)
+LOOKAHEAD_RULES = [("LA_IT", 2), ("LA_TT", 4), ("LA_MK", 1), ("LA_EC", 3), ("LA_R", 0)]
+
+
+class Lookahead:
+    """The scratch handle and buffers of one-step look-ahead decisions for `src` (a DeviceBatchEnv with loaded or generated
+    instances): B*T copies, copy (b, j, m) tries job j's next task on machine m for instance b.  The constants are forked once,
+    here; `decide(column)` is expand, one ordinary step of the scratch handle and the selection — five launches, no read-back."""
+
+    def __init__(self, src):
+        self.src, B, T, dev = src, src.B, src.T, src.device
+        self.scratch = DeviceBatchEnv(src.J, src.M, src.E, B * T, left_shift=src.left_shift, obs_dtype="f32" if src.obs_f32 else "f64",
+                                      device=dev.index or 0, gamma=src.gamma, w_cfg=src.w_cfg, scaling_divisor=src.scaling_divisor)
+        self.scratch.fork_from(src, torch.arange(B * T, dtype=torch.int32, device=dev) // T, instance=True, state=False, obs=False)
+        self.task_c = torch.empty(B * T, dtype=torch.int32, device=dev)
+        self.mach_c = torch.empty(B * T, dtype=torch.int32, device=dev)
+        self.task = torch.empty(B, dtype=torch.int32, device=dev)
+        self.mach = torch.empty(B, dtype=torch.int32, device=dev)
+        self.job = torch.empty(B, dtype=torch.int32, device=dev)
+        self.best = torch.empty(B, dtype=torch.float64, device=dev)
+
+    def expand(self):
+        capi.check(self.src.L.mtfjsp_lookahead_expand(self.scratch.h, self.src.h, self.task_c.data_ptr(), self.mach_c.data_ptr()), self.scratch.h)
+
+    def select(self, column):
+        capi.check(self.src.L.mtfjsp_lookahead_select(self.scratch.h, self.src.h, int(column), self.task.data_ptr(), self.mach.data_ptr(),
+                                                      self.job.data_ptr(), self.best.data_ptr()), self.scratch.h)
+
+    def decide(self, column):
+        """-> (task, mach) [B] int32 device tensors (overwritten by the next decision): the action whose one-step raw[column] is
+        largest, ties to the lowest (job, machine); task -1 for a finished instance.  `self.best`: the winning values."""
+        self.expand()
+        self.scratch.step(self.task_c, self.mach_c)
+        self.select(column)
+        return self.task, self.mach
+
+    def close(self):
+        self.scratch.close()
+
+
+def lookahead_baselines(t, p, tt, edge, args, rules=LOOKAHEAD_RULES, device=0, obs_dtype="f32", left_shift=False):
+    """One-step look-ahead dispatch rules `rules` ((name, column) each) on the N instances t, p [N,T,M], tt [N,M,M],
+    edge [N,E,M/E]; args as for `pdr_baselines`.  Per rule and step: fork the N instances into N*T copies, step every copy with its
+    (job, machine), take per instance the copy with the largest raw[column] (the least added cost; ties: lowest (job, machine)),
+    step the instance with it.  Unlike the reference's idle-time rule (pdrs:465-540) the tie is not drawn at random (pdrs:520) and
+    the machine is not fixed beforehand by a machine rule: job and machine are chosen jointly.
+    -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, and under PLANS {name: (task[N,T], mach[N,T])}."""
+    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
+    T = J * M
+    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
+    names = [r[0] for r in rules]
+    if len(set(names)) != len(rules) or PLANS in names:
+        raise ValueError("rule names must be distinct")
+    if any(int(r[1]) not in range(5) for r in rules):
+        raise ValueError("a look-ahead rule's column must be 0..4")
+    t = np.asarray(t, np.float64)
+    N = t.shape[0]
+    scal = args.get("reward_scaling", {}) or {}
+    env = DeviceBatchEnv(J, M, E, N, left_shift=left_shift, obs_dtype=obs_dtype, device=device, w_cfg=w,
+                         scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+    la = None
+    out, plans = {}, {}
+    try:
+        env.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=edge)
+        la = Lookahead(env)
+        dev = env.device
+        w3 = torch.tensor([w], dtype=torch.float64, device=dev).repeat(N, 1)
+        for name, column in rules:
+            env.scaler_init()                                           # the scaled components are produced but not used here
+            env.reset(w3)                                               # pdrs:675 reset(Random_weight_type="eval")
+            task = torch.empty(T, N, dtype=torch.int32, device=dev)
+            mach = torch.empty(T, N, dtype=torch.int32, device=dev)
+            cum = torch.zeros(N, 5, dtype=torch.float64, device=dev)
+            bad = torch.zeros(N, dtype=torch.int32, device=dev)
+            for s in range(T):
+                a, m = la.decide(column)
+                task[s].copy_(a); mach[s].copy_(m)
+                env.step(a, m)
+                cum += env.raw                                          # reward, r_mk, r_idle, r_pt, r_tt, in step order
+                bad |= env.status
+            torch.cuda.synchronize(dev)
+            n_bad = int((bad & (capi.ST_INVALID | capi.ST_INFEASIBLE)).ne(0).sum().item())
+            if n_bad:
+                raise RuntimeError(f"look-ahead rollout: {n_bad} instance(s) met an invalid action or an infeasible machine")
+            if not bool(env.info[:, 1].all().item()):
+                raise RuntimeError("look-ahead rollout: an episode did not finish after T steps")
+            prev = env.read_state(capi.STATE_PREV_COSTS)
+            c = cum.cpu().numpy()
+            cost = {"opr_Gt": c[:, 0], "opr_mk": c[:, 1], "opr_idleT": c[:, 2], "opr_pt": c[:, 3], "opr_transT": c[:, 4]}
+            final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
+            obj = w[0] * final4[:, 0] + w[1] * (final4[:, 1] + final4[:, 3]) + w[2] * final4[:, 2]
+            out[name] = (cost, final4, obj)
+            plans[name] = (task.t().contiguous().cpu().numpy(), mach.t().contiguous().cpu().numpy())
+    finally:
+        if la is not None:
+            la.close()
+        env.close()
+    out[PLANS] = plans
+    return out

@@ -31,6 +31,7 @@ class DeviceBatchEnv:
         self.J, self.M, self.E, self.B = int(n_job), int(n_machine), int(n_edge), int(batch)
         self.T = self.J * self.M
         self.left_shift = bool(left_shift)
+        self.gamma, self.w_cfg, self.scaling_divisor = float(gamma), tuple(float(x) for x in w_cfg), float(scaling_divisor)
         self.obs_f32 = obs_dtype in ("f32", torch.float32, np.float32)
         self.device = torch.device("cuda", device)
         cfg = capi.Config(self.J, self.M, self.E, self.B, int(bool(left_shift)), capi.OBS_F32 if self.obs_f32 else capi.OBS_F64,
@@ -107,6 +108,20 @@ class DeviceBatchEnv:
         capi.check(self.L.mtfjsp_read_instances_host(self.h, t.ctypes.data, p.ctypes.data, tt.ctypes.data, shop.ctypes.data), self.h)
         edge = np.stack([np.stack([np.flatnonzero(shop[b] == e) for e in range(E)]) for b in range(B)]).astype(np.int64)
         return t, p, tt, edge
+
+    # ---- fork (mtfjsp_fork: no reference counterpart; pdrs:465-540 replays the prefix instead)
+    def fork_from(self, src, index, instance=True, state=True, obs=True):
+        """instance i of this handle becomes a copy of instance index[i] of `src` (another DeviceBatchEnv of the same size, dtype,
+        left-shift setting and device; any batch): one launch on this handle's stream, nothing is read back.  index: host sequence
+        or int32 device tensor [B] (duplicates, any order; an entry outside [0, src.B) leaves that instance untouched and sets
+        ST_INVALID in its status word).  instance / state / obs: the constants, the scheduling state (enough to step on), the bound
+        observation (include/mtfjsp.h).  Both handles must be on one stream, or the caller orders them."""
+        if not torch.is_tensor(index):
+            index = torch.as_tensor(np.ascontiguousarray(index, np.int32), device=self.device)
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.shape == (self.B,)
+        flags = (capi.FORK_INSTANCE if instance else 0) | (capi.FORK_STATE if state else 0) | (capi.FORK_OBS if obs else 0)
+        self._fork_index = index                                        # alive until the launch has run
+        capi.check(self.L.mtfjsp_fork(self.h, src.h, index.data_ptr(), flags), self.h)
 
     def scaler_init(self):
         capi.check(self.L.mtfjsp_scaler_init(self.h), self.h)

@@ -12,6 +12,7 @@ _LIB = None
 OBS_F64, OBS_F32 = 0, 1
 OK, ERR_ARG, ERR_STATE, ERR_HIP, ERR_ACTION, ERR_RETRY = 0, -1, -2, -3, -4, -5
 PATH_MASK, ST_INVALID, ST_INFEASIBLE = 0x7, 0x100, 0x200
+FORK_INSTANCE, FORK_STATE, FORK_OBS = 1, 2, 4
 STATE_MACHINE, STATE_START, STATE_FINISH, STATE_ROUTES, STATE_PREV_COSTS, STATE_SCALER, STATE_W3 = range(7)
 
 
@@ -73,6 +74,9 @@ PROTOTYPES = {
     "mtfjsp_observe_mfea1": (_I, [_VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_random_actions": (_I, [_VP, _U64, _U64, _VP, _VP, _VP]),
     "mtfjsp_pdr_plan": (_I, [_VP, _VP, _VP, _VP, _U64, _VP, _VP]),
+    "mtfjsp_fork": (_I, [_VP, _VP, _VP, C.c_int32]),
+    "mtfjsp_lookahead_expand": (_I, [_VP, _VP, _VP, _VP]),
+    "mtfjsp_lookahead_select": (_I, [_VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
     "mtfjsp_export_dense_adj": (_I, [_VP, _VP]),
     "mtfjsp_export_dense_adj_host": (_I, [_VP, _VP]),
     "mtfjsp_valid_action_mask": (_I, [_VP, _VP]),

@@ -1704,6 +1704,7 @@ void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v)
 {
     v->B = h->cfg.batch; v->J = h->cfg.n_job; v->M = h->cfg.n_machine; v->T = h->T; v->device_id = h->cfg.device_id;
     v->loaded = h->loaded; v->t = h->t; v->p = h->p; v->stream = h->stream;
+    v->was_reset = h->was_reset; v->obs_bound = h->obs_bound; v->mj = h->mj; v->MJ = h->MJ; v->obs = h->obs;
 }
 int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg)
 {
@@ -2593,4 +2594,153 @@ extern "C" int mtfjsp_timing_end(mtfjsp_handle_t h, double *ms_total, int64_t *l
     if (launches) *launches = (int64_t)h->ev_used;
     h->timing = false; h->ev_used = 0;
     return MTFJSP_OK;
+}
+
+// ------------------------------------------------------------------ mtfjsp_fork
+// Destination instance i becomes a copy of source instance src_index[i]: every per-instance array of the handle is a "segment"
+// (source base, destination base, bytes per instance), and a segment is a flat gather of words — destination word x of the segment
+// belongs to instance x / wps and is word x % wps of it, so the stores of a workgroup are one contiguous run and the loads are
+// contiguous within an instance.  The word is the widest of 16, 8, 4, 1 bytes that divides the instance pitch and both bases: 16 for
+// every record array (TaskSD, TaskPL, JobR, {min_dur, min_pt}) and for whatever else the shape makes a multiple of 16 bytes.
+// A workgroup serves FORK_U * 256 consecutive words of ONE segment (found by its block number in the table of the kernel
+// arguments: scalar compares); a thread's FORK_U index loads, then its FORK_U data loads, are all issued before its first store, as
+// straight-line code: out-of-range words and out-of-range source indices load from a clamped address and only skip the store.
+// The last workgroups set MTFJSP_ST_INVALID in the bound status word of the instances whose index is out of range.
+#define FORK_MAXSEG 24
+#define FORK_U 4
+struct ForkSeg { const unsigned char *src; unsigned char *dst; unsigned wps, shift, nwords, first_block; };
+struct ForkArgs {
+    ForkSeg seg[FORK_MAXSEG];
+    int n;
+    unsigned status_block;             // first workgroup of the status pass (= number of copying workgroups)
+    const int *src_index;              // [B_dst] (IMPLICIT: unused, source = i / div)
+    unsigned div;
+    int B_src, B_dst;
+    int *status;                       // destination's bound status words, or null
+};
+template <bool IMPLICIT>
+__device__ __forceinline__ int fork_source(const ForkArgs &A, unsigned inst) { return IMPLICIT ? (int)(inst / A.div) : A.src_index[inst]; }
+
+// hipcc sinks a load whose only use is a conditional store into that store's branch, behind the stores before it: an empty statement
+// that names the loaded registers, in the block of the loads, keeps every request where it was written
+__device__ __forceinline__ void fork_keep(fp_u4 &v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void fork_keep(fp_u2 &v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void fork_keep(unsigned &v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void fork_keep(unsigned char &v) { unsigned x = v; asm volatile("" : "+v"(x)); v = (unsigned char)x; }
+
+template <typename WORD, bool IMPLICIT>
+__device__ __forceinline__ void fork_words(const ForkArgs &A, const ForkSeg g, unsigned blk)
+{
+    const WORD *__restrict__ s = reinterpret_cast<const WORD *>(g.src);
+    WORD *__restrict__ d = reinterpret_cast<WORD *>(g.dst);
+    unsigned x[FORK_U], w[FORK_U];
+    int si[FORK_U];
+    WORD v[FORK_U];
+#pragma unroll
+    for (int u = 0; u < FORK_U; u++) {
+        x[u] = (blk * FORK_U + u) * 256u + threadIdx.x;
+        const unsigned c = x[u] < g.nwords ? x[u] : g.nwords - 1;
+        const unsigned inst = c / g.wps;
+        w[u] = c - inst * g.wps;
+        si[u] = fork_source<IMPLICIT>(A, inst);
+    }
+#pragma unroll
+    for (int u = 0; u < FORK_U; u++) {
+        const unsigned ss = (unsigned)si[u] < (unsigned)A.B_src ? (unsigned)si[u] : 0u;
+        v[u] = s[(size_t)ss * g.wps + w[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < FORK_U; u++) fork_keep(v[u]);
+#pragma unroll
+    for (int u = 0; u < FORK_U; u++)
+        if (x[u] < g.nwords && (unsigned)si[u] < (unsigned)A.B_src) d[x[u]] = v[u];
+}
+
+template <bool IMPLICIT>
+__global__ __launch_bounds__(256) void k_env_fork(ForkArgs A)
+{
+    const unsigned blk = blockIdx.x;
+    if (blk >= A.status_block) {                                            // index out of range: the instance is untouched but for this bit
+        const unsigned i = (blk - A.status_block) * 256u + threadIdx.x, c = i < (unsigned)A.B_dst ? i : (unsigned)A.B_dst - 1;
+        const int si = fork_source<IMPLICIT>(A, c);
+        unsigned st = (unsigned)A.status[c];
+        fork_keep(st);
+        if (i < (unsigned)A.B_dst && (unsigned)si >= (unsigned)A.B_src) A.status[c] = (int)(st | MTFJSP_ST_INVALID);
+        return;
+    }
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < FORK_MAXSEG; i++) k = (i < A.n && blk >= A.seg[i].first_block) ? i : k;
+    const ForkSeg g = A.seg[k];
+    const unsigned local = blk - g.first_block;
+    if (g.shift == 4) fork_words<fp_u4, IMPLICIT>(A, g, local);
+    else if (g.shift == 3) fork_words<fp_u2, IMPLICIT>(A, g, local);
+    else if (g.shift == 2) fork_words<unsigned, IMPLICIT>(A, g, local);
+    else fork_words<unsigned char, IMPLICIT>(A, g, local);
+}
+
+int mtfjsp_env_fork_launch(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32_t *src_index, int div, int flags, const char *who)
+{
+    auto fail = [&](int code, const char *msg) { dst->err = std::string(who) + ": " + msg; return code; };
+    const int all = MTFJSP_FORK_INSTANCE | MTFJSP_FORK_STATE | MTFJSP_FORK_OBS;
+    if (dst == src) return fail(MTFJSP_ERR_ARG, "destination and source are the same handle (an in-place gather races between instances)");
+    if (!flags || (flags & ~all)) return fail(MTFJSP_ERR_ARG, "flags must be a combination of MTFJSP_FORK_INSTANCE, _STATE, _OBS");
+    if (!src_index && div < 1) return fail(MTFJSP_ERR_ARG, "bad implicit index");
+    const mtfjsp_config_t &a = dst->cfg, &b = src->cfg;
+    if (a.n_job != b.n_job || a.n_machine != b.n_machine || a.n_edge != b.n_edge || a.obs_dtype != b.obs_dtype ||
+        (a.left_shift != 0) != (b.left_shift != 0) || a.device_id != b.device_id)
+        return fail(MTFJSP_ERR_ARG, "handles differ in n_job, n_machine, n_edge, obs_dtype, left_shift or device");
+    if (!src->loaded) return fail(MTFJSP_ERR_STATE, "the source has no instances loaded or generated");
+    if ((flags & (MTFJSP_FORK_STATE | MTFJSP_FORK_OBS)) && !src->was_reset) return fail(MTFJSP_ERR_STATE, "the source has never been reset");
+    if ((flags & MTFJSP_FORK_OBS) && (!src->obs_bound || !dst->obs_bound)) return fail(MTFJSP_ERR_STATE, "MTFJSP_FORK_OBS needs observation buffers bound on both handles");
+    if (!(flags & MTFJSP_FORK_INSTANCE) && !dst->loaded) return fail(MTFJSP_ERR_STATE, "the destination has no instances: fork with MTFJSP_FORK_INSTANCE first");
+    const size_t Bd = a.batch, T = dst->T, M = a.n_machine, J = a.n_job, MJ = dst->MJ, es = a.obs_dtype == MTFJSP_OBS_F32 ? 4 : 8;
+    ForkArgs A{};
+    unsigned blocks = 0;
+    bool too_large = false;
+    auto add = [&](const void *s, void *d, size_t pitch) {
+        unsigned sh = 4;
+        while (sh && ((pitch | (size_t)s | (size_t)d) & (((size_t)1 << sh) - 1))) sh--;
+        if (sh == 1) sh = 0;                                                // words of 16, 8, 4 or 1 bytes
+        const size_t wps = pitch >> sh, nwords = Bd * wps;
+        if (nwords >= 0x7fffffffull || A.n >= FORK_MAXSEG) { too_large = true; return; }
+        ForkSeg &g = A.seg[A.n++];
+        g.src = (const unsigned char *)s; g.dst = (unsigned char *)d; g.wps = (unsigned)wps; g.shift = sh; g.nwords = (unsigned)nwords; g.first_block = blocks;
+        blocks += (unsigned)((nwords + FORK_U * 256 - 1) / (FORK_U * 256));
+    };
+    if (flags & MTFJSP_FORK_INSTANCE) {
+        add(src->t, dst->t, T * M * 8); add(src->p, dst->p, T * M * 8); add(src->tt, dst->tt, M * M * 8); add(src->ttT, dst->ttT, M * M * 8);
+        add(src->cst, dst->cst, T * 16); add(src->mean3, dst->mean3, T * 24); add(src->shop, dst->shop, M * 4);
+    }
+    if (flags & MTFJSP_FORK_STATE) {
+        // the step kernels read no bound observation field back (candidate and job_mask included: they derive both from the job
+        // records and only write them), so the state is the handle's own arrays
+        add(src->sd, dst->sd, T * sizeof(TaskSD)); add(src->pl, dst->pl, T * sizeof(TaskPL)); add(src->jr, dst->jr, J * sizeof(JobR));
+        add(src->mj, dst->mj, MJ * sizeof(MJRec)); add(src->mfea, dst->mfea, M * 64); add(src->scal, dst->scal, SCAL_N * 8);
+        add(src->d_w3, dst->d_w3, 24);
+    }
+    if (flags & MTFJSP_FORK_OBS) {
+        const mtfjsp_obs_t &so = src->obs, &dob = dst->obs;
+        add(so.tasks_fea, dob.tasks_fea, T * 12 * es); add(so.ell_col, dob.ell_col, T * 8); add(so.ell_val, dob.ell_val, T * 8);
+        add(so.m_fea2, dob.m_fea2, M * 8 * es); add(so.info, dob.info, 48);
+        if (so.raw && dob.raw) add(so.raw, dob.raw, 40);
+        add(so.candidate, dob.candidate, J * 4); add(so.job_mask, dob.job_mask, J); add(so.status, dob.status, 4);
+    }
+    if (too_large) return fail(MTFJSP_ERR_ARG, "an array of the destination has 2^31 or more words");
+    A.status_block = blocks;
+    A.src_index = src_index; A.div = src_index ? 1u : (unsigned)div; A.B_src = b.batch; A.B_dst = a.batch;
+    if (dst->obs_bound) { A.status = dst->obs.status; blocks += (unsigned)((Bd + 255) / 256); }
+    if (hipSetDevice(a.device_id) != hipSuccess) return fail(MTFJSP_ERR_HIP, "hipSetDevice failed");
+    if (src_index) hipLaunchKernelGGL(k_env_fork<false>, dim3(blocks), dim3(256), 0, dst->stream, A);
+    else hipLaunchKernelGGL(k_env_fork<true>, dim3(blocks), dim3(256), 0, dst->stream, A);
+    if (hipGetLastError() != hipSuccess) return fail(MTFJSP_ERR_HIP, "launch failed");
+    if (flags & MTFJSP_FORK_INSTANCE) { dst->loaded = true; dst->was_reset = false; }
+    if (flags & MTFJSP_FORK_STATE) dst->was_reset = true;
+    return MTFJSP_OK;
+}
+extern "C" int mtfjsp_fork(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32_t *src_index, int32_t flags)
+{
+    if (!dst) return MTFJSP_ERR_ARG;
+    if (!src || !src_index) { dst->err = "mtfjsp_fork: null argument"; return MTFJSP_ERR_ARG; }
+    return mtfjsp_env_fork_launch(dst, src, src_index, 1, flags, "mtfjsp_fork");
 }

@@ -114,12 +114,20 @@ __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t 
     }
 }
 
-// host side: what the library's other translation units (mtfjsp_pdr.hip) see of a handle; defined in mtfjsp_env.hip
+// host side: what the library's other translation units (mtfjsp_pdr.hip, mtfjsp_lookahead.hip) see of a handle; defined in mtfjsp_env.hip
 struct EnvHostView {
     int B, J, M, T, device_id;
     bool loaded;
     const double *t, *p;               // [B,T,M] device instance arrays
     hipStream_t stream;
+    bool was_reset, obs_bound;
+    const MJRec *mj;                   // [B,MJ]: .cnt of element j = scheduled operations of job j
+    int MJ;
+    mtfjsp_obs_t obs;                  // the bound observation (valid with obs_bound)
 };
 __attribute__((visibility("hidden"))) void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v);
 __attribute__((visibility("hidden"))) int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg);   // sets mtfjsp_last_error, returns code
+// mtfjsp_fork's checks and launch.  src_index == nullptr: destination instance i takes source instance i / div (the look-ahead's
+// implicit index: T copies per source instance); the public entry point always passes an index.
+__attribute__((visibility("hidden"))) int mtfjsp_env_fork_launch(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32_t *src_index, int div, int flags,
+                                                                 const char *who);

@@ -180,6 +180,55 @@ int mtfjsp_observe_mfea1(mtfjsp_handle_t h, const int32_t *task_idx, const uint8
 int mtfjsp_random_actions(mtfjsp_handle_t h, uint64_t seed, uint64_t counter, int32_t *task_idx,
                           int32_t *mach_idx, int32_t *job_idx);
 
+/* ------------------------------------------------------------------ fork */
+/* Device-side copy of environment state between handles: destination instance i becomes a copy of source instance src_index[i]
+ * (device, int32 [dst.batch]; duplicates and any order allowed) — the primitive of every search-style use: continue one partial
+ * schedule in several directions, try an action and take it back (keep the original, step the copy).  The reference has no
+ * counterpart: its one-step look-ahead rule re-runs env.reset() and replays the whole prefix for every candidate (pdrs:465-540).
+ *   MTFJSP_FORK_INSTANCE  the instance constants: t, p, tt and what load_instances derives from them (transposed tt, {min_dur,
+ *                         min_pt}, per-task means), shop_of_machine
+ *   MTFJSP_FORK_STATE     the scheduling state: per-task, per-job and per-machine records, the f64 machine features, and every
+ *                         per-instance scalar (previous costs, transport, reward weights, the 17 RewardScaling words, the merged-edge
+ *                         words), plus the reset weights mtfjsp_reset_host staged.  The step kernels read no bound observation field
+ *                         back — candidate and job_mask are derived from the job records and only written — so a copy forked with
+ *                         STATE alone steps correctly: info, raw and status of its later steps are right, while its observation
+ *                         (tasks_fea, ELL rows, m_fea2, candidate, job_mask: a step rewrites only the rows it changes) is undefined
+ *                         until its next reset
+ *   MTFJSP_FORK_OBS       the bound observation: tasks_fea, ell_col, ell_val, m_fea2, info, raw (where both have it), candidate,
+ *                         job_mask, status
+ * ONE launch (k_env_fork) on dst's stream, 16-byte words wherever an array's bytes per instance allow; nothing is read back and
+ * nothing synchronises.  ORDERING AGAINST src's STREAM IS THE CALLER'S DUTY (same stream, or an event): the launch reads src's
+ * arrays as they are when it runs.
+ * dst and src must agree in n_job, n_machine, n_edge, obs_dtype, left_shift and device (batches may differ) and must be distinct
+ * handles (an in-place gather races between instances): otherwise MTFJSP_ERR_ARG.  MTFJSP_ERR_STATE: src not loaded; STATE or OBS
+ * from a src that was never reset; OBS without bound observations on either side; no INSTANCE flag and a dst without instances.
+ * Nothing is written on an error return.  After success dst counts as loaded if INSTANCE was set and as reset if STATE was set.
+ * An index outside [0, src.batch) leaves that destination instance untouched and sets MTFJSP_ST_INVALID in its status word (where
+ * dst has observations bound); all other instances are copied. */
+enum { MTFJSP_FORK_INSTANCE = 1, MTFJSP_FORK_STATE = 2, MTFJSP_FORK_OBS = 4 };
+int mtfjsp_fork(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32_t *src_index, int32_t flags);
+
+/* ------------------------------------------------------------------ one-step look-ahead dispatch rules */
+/* = the look-ahead of LWKR_IT_o_jointActor (pdrs:465-540: for every candidate env.reset(), replay of the prefix, the candidate's
+ * step, pdrs:486-510; then the choice, pdrs:512-520), as one copy and one ordinary step per candidate.  src holds B instances,
+ * scratch B*T (T = n_job*n_machine) whose constants were forked once (mtfjsp_fork, MTFJSP_FORK_INSTANCE, index i -> i / T): copy
+ * (b, j, m) = scratch instance (b*n_job + j)*n_machine + m tries "job j's next task on machine m" for source instance b.
+ * mtfjsp_lookahead_expand: forks src's STATE into scratch (k_env_fork with the implicit index i / T) and writes the candidate
+ * actions task_c, mach_c [B*T]; two launches on scratch's stream.  The caller then runs mtfjsp_step(scratch, task_c, mach_c):
+ * the copies of a finished job come back with MTFJSP_ST_INVALID, an infeasible machine with MTFJSP_ST_INFEASIBLE — throw-away
+ * copies either way.  Errors as mtfjsp_fork; scratch.batch != src.batch * T: MTFJSP_ERR_ARG.
+ * mtfjsp_lookahead_select: per source instance, the copy without those two flags whose raw[column] is LARGEST (rewards are
+ * previous minus current cost: the least added cost; column 0..4 = scalar reward, makespan, idle, energy, transport, env:1051-1171),
+ * compared as binary64, no arithmetic; ties go to the lowest (j, m) (pdrs:520 draws among tied jobs with random.choice, and the
+ * reference fixes each task's machine beforehand by a machine rule: here the look-ahead ranges over (job, machine) jointly).
+ * task_out, mach_out [B] (device; the action for mtfjsp_step(src, ...)), job_out [B] and best_out [B] f64 (the winning value)
+ * may be NULL.  An instance without a valid copy (finished) gets task, machine, job -1 and best NaN.  One launch, one wavefront per
+ * source instance, on src's stream; it reads scratch's bound status and raw and src's job records: ordering between the two
+ * handles' streams is the caller's duty here too. */
+int mtfjsp_lookahead_expand(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_t *task_c, int32_t *mach_c);
+int mtfjsp_lookahead_select(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_t column, int32_t *task_out, int32_t *mach_out,
+                            int32_t *job_out, double *best_out);
+
 /* ------------------------------------------------------------------ dispatch-rule baselines */
 /* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
  * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"

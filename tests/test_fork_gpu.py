@@ -1,0 +1,331 @@
+"""PARITY (GPU): mtfjsp_fork / DeviceBatchEnv.fork_from against the C oracle, with no tolerance.
+
+The oracle has no fork.  The expected side of a forked handle is an OracleBatch built from the replicated instances t[index] that
+replays the source's prefix actions and then continues with the copy's own actions; the source's own oracle runs beside it.  Every
+comparison is in full — observation, dense adjacency, masks, info, raw and every mtfjsp_read_state_host array — after the fork and
+after EVERY later step (a step rewrites only the rows its decision changes, see tests/env_parity.py), with the rows a step must
+rewrite poisoned first.
+
+Shapes: one per layout the records are read in (the dispatched kernel is asserted), 5 source and 13 destination instances, f32 and
+f64 observations.  The destination is dirty (it has finished an episode on other instances), the index has duplicates and is not
+monotone.
+"""
+import ctypes as C
+from importlib import import_module
+
+import numpy as np
+import pytest
+import torch
+
+from env_parity import _same, dispatch_kernel, random_valid
+
+pytestmark = pytest.mark.gpu
+
+BS, BD = 5, 13
+INDEX = np.array([3, 0, 4, 4, 1, 2, 0, 3, 3, 1, 4, 2, 0], np.int32)
+SHAPES = {
+    "J3M4E2": (3, 4, 2, "k_env_grp16"),
+    "J6M6E2": (6, 6, 2, "k_env_grp16"),
+    "J3M11E1": (3, 11, 1, "k_env_grp16x2"),        # the two-slot register kernel
+    "J5M12E2": (5, 12, 2, "k_env_step_grp"),       # the LDS kernel
+    "J9M8E2": (9, 8, 2, "k_env_grp16x2"),          # T = 72
+}
+
+
+def _mods():
+    import mtfjsp_amd  # noqa: F401
+    return (import_module("e2e-mappo-for-mt-fjsp_amd.batch_env"), import_module("e2e-mappo-for-mt-fjsp_amd.instances"),
+            import_module("e2e-mappo-for-mt-fjsp_amd.capi"))
+
+
+def _same_nan(got, want, what):
+    """_same for arrays that carry NaN for "unscheduled" (the NaN pattern must agree, then everything else)"""
+    got, want = np.asarray(got), np.asarray(want)
+    _same(np.isnan(got), np.isnan(want), what + " (NaN pattern)")
+    _same(np.where(np.isnan(got), 0.0, got), np.where(np.isnan(want), 0.0, want), what)
+
+
+class Side:
+    """a DeviceBatchEnv and the OracleBatch that must equal it, driven together"""
+
+    def __init__(self, env, orc, t, w3, odt, capi, tag, seed):
+        self.env, self.orc, self.feas, self.w3, self.odt, self.capi, self.tag = env, orc, t >= 0, w3, odt, capi, tag
+        self.rs = np.random.RandomState(seed)
+        self.B, self.T, self.M = t.shape[0], t.shape[1], t.shape[2]
+        self.info, self.raw = np.zeros((self.B, 6)), np.zeros((self.B, 5))
+        self.o = self.cand = self.mask = None
+        self.steps = 0
+
+    def oracle_reset(self, w3):
+        self.w3 = w3
+        self.o = self.orc.reset(w3)
+        self.cand, self.mask = self.orc.job_mask_state()
+        self.info, self.raw = np.zeros((self.B, 6)), np.zeros((self.B, 5))
+        self.steps = 0
+
+    def oracle_step(self, job, task, mach):
+        self.info, self.raw, paths = self.orc.step(task, mach)
+        self.cand, self.mask = self.orc.job_mask_update(job)
+        self.o = self.orc.observe()
+        self.steps += 1
+        return paths
+
+    def check(self, what, observation=True):
+        env, capi, tag = self.env, self.capi, f"{self.tag} {what}"
+        obs = lambda x: np.asarray(x, np.float64).astype(self.odt)      # noqa: E731
+        _same(env.info.cpu().numpy(), self.info, tag + " info"); _same(env.raw.cpu().numpy(), self.raw, tag + " raw")
+        if observation:
+            _same(env.tasks_fea.cpu().numpy(), obs(self.o["tfea"]), tag + " tasks_fea")
+            _same(env.m_fea2.cpu().numpy(), obs(self.o["mfea2"]), tag + " m_fea2")
+            _same(env.dense_adj().cpu().numpy(), self.o["adj"], tag + " dense_adj")
+            _same(env.candidate.cpu().numpy(), self.cand, tag + " candidate"); _same(env.job_mask.cpu().numpy(), self.mask, tag + " job_mask")
+        _same(env.valid_action_mask().cpu().numpy(), self.orc.valid_action_mask(), tag + " valid_action_mask")
+        so = self.orc.state()
+        _same(env.read_state(capi.STATE_MACHINE), so["mach"], tag + " machines"); _same(env.read_state(capi.STATE_ROUTES), so["routes"], tag + " routes")
+        _same_nan(env.read_state(capi.STATE_START), so["st"], tag + " start times"); _same_nan(env.read_state(capi.STATE_FINISH), so["ft"], tag + " finish times")
+        _same(env.read_state(capi.STATE_PREV_COSTS), so["prev"], tag + " previous costs")
+        _same(env.read_state(capi.STATE_SCALER), so["scaler"], tag + " scaler"); _same(env.read_state(capi.STATE_W3), self.w3, tag + " reward weights")
+
+    def step(self, observation=True, check=True):
+        """one step with this side's OWN random valid actions, compared in full"""
+        env, T, M, B = self.env, self.T, self.M, self.B
+        job, task, mach = random_valid(self.rs, self.cand, self.mask, self.feas)
+        if observation:                                                 # poison the rows the step must rewrite (tests/env_parity.py)
+            rows = np.concatenate([b * T + np.arange(task[b], (task[b] // M + 1) * M) for b in range(B)])
+            env.tasks_fea[torch.as_tensor(rows, device=env.tasks_fea.device)] = float("nan")
+        env.step(task, mach)                                            # host variant: raises on an invalid action
+        paths = self.oracle_step(job, task, mach)
+        if check:
+            st = env.status.cpu().numpy()
+            assert not (st & (self.capi.ST_INVALID | self.capi.ST_INFEASIBLE)).any(), f"{self.tag} step {self.steps} status flags"
+            _same(st & self.capi.PATH_MASK, paths, f"{self.tag} step {self.steps} scheduling path")
+            self.check(f"step {self.steps}", observation)
+        return job, task, mach
+
+    def finish(self, observation=True):
+        while self.steps < self.T:
+            self.step(observation)
+        assert self.info[:, 1].all(), self.tag + ": the episode must be over"
+
+
+def _setup(shape, obs_dtype, left_shift=True, seed=5):
+    """-> (source side after its reset, dirty destination env, instances, modules)"""
+    batch_env, inst, capi = _mods()
+    from oracle.env_oracle import OracleBatch
+    J, M, E, kernel = SHAPES[shape]
+    assert dispatch_kernel(J, M, BS) == kernel and dispatch_kernel(J, M, BD) == kernel
+    odt = np.float32 if obs_dtype == "f32" else np.float64
+    t, p, tt, edge = inst.generate_instances(BS, J, M, E, seed=1000 * seed + J * 100 + M)
+    rs = np.random.RandomState(seed)
+    w3 = rs.dirichlet([1, 1, 1], BS)
+    env = batch_env.DeviceBatchEnv(J, M, E, BS, left_shift=left_shift, obs_dtype=obs_dtype)
+    env.load_instances(t, p, tt, edge=edge); env.scaler_init(); env.reset(w3)
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift); orc.scaler_init()
+    src = Side(env, orc, t, w3, odt, capi, f"{shape} {obs_dtype} source", seed + 1)
+    src.oracle_reset(w3)
+    # the destination: other instances, one finished episode, a scaler with history
+    t2, p2, tt2, edge2 = inst.generate_instances(BD, J, M, E, seed=77 + J * 100 + M)
+    dst = batch_env.DeviceBatchEnv(J, M, E, BD, left_shift=left_shift, obs_dtype=obs_dtype)
+    dst.load_instances(t2, p2, tt2, edge=edge2); dst.scaler_init(); dst.reset(rs.dirichlet([1, 1, 1], BD))
+    a = torch.zeros(BD, dtype=torch.int32, device=dst.device); m = torch.zeros_like(a); j = torch.zeros_like(a)
+    for s in range(J * M):
+        dst.random_actions(11, s, a, m, j); dst.step(a, m)
+    assert bool(dst.info[:, 1].all().item())
+    return src, dst, (t, p, tt, edge), (batch_env, inst, capi, OracleBatch, odt, J, M, E)
+
+
+def _expected(src, prefix, data, mods, left_shift, tag, seed, index=INDEX):
+    """the oracle of a destination forked from `src` by `index`: replicated instances, the source's prefix replayed"""
+    t, p, tt, edge = data
+    OracleBatch, odt, capi = mods[3], mods[4], mods[2]
+    orc = OracleBatch(t[index], p[index], tt[index], edge[index], left_shift=left_shift); orc.scaler_init()
+    side = Side(None, orc, t[index], src.w3[index], odt, capi, tag, seed)
+    side.oracle_reset(src.w3[index])
+    for job, task, mach in prefix:
+        side.oracle_step(job[index], task[index], mach[index])
+    return side
+
+
+@pytest.mark.parametrize("obs_dtype", ["f32", "f64"])
+@pytest.mark.parametrize("point", ["reset", "half", "terminal"])
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_a_fork_equals_the_oracle_at_the_prefix_and_at_every_later_step(shape, point, obs_dtype):
+    src, dst, data, mods = _setup(shape, obs_dtype)
+    T = src.T
+    s0 = {"reset": 0, "half": T // 2, "terminal": T}[point]
+    prefix = [src.step(check=False) for _ in range(s0)]
+    src.check(f"before the fork (step {s0})")
+    dst.fork_from(src.env, INDEX)                                       # all three flags
+    exp = _expected(src, prefix, data, mods, True, f"{shape} {obs_dtype} fork at {s0}", 9)
+    exp.env = dst
+    exp.check("after the fork")
+    _same(dst.status.cpu().numpy(), src.env.status.cpu().numpy()[INDEX], exp.tag + " status")
+    # every copy goes on with its OWN actions, the source beside it with its own: all compared in full after every step
+    while exp.steps < T:
+        exp.step()
+        src.step()
+    assert exp.info[:, 1].all() and src.info[:, 1].all()
+    exp.check("end of the forked episode"); src.check("end of the source's episode")
+    # a second episode on the destination: the scaler state travelled
+    w3 = np.random.RandomState(3).dirichlet([1, 1, 1], BD)
+    dst.scaler_reset_returns(); exp.orc.scaler_reset_returns()
+    dst.reset(w3); exp.oracle_reset(w3)
+    exp.check("second episode reset")
+    exp.finish()
+    dst.close(); src.env.close()
+
+
+@pytest.mark.parametrize("obs_dtype", ["f32", "f64"])
+@pytest.mark.parametrize("shape", ["J6M6E2", "J5M12E2"])
+def test_state_only_steps_correctly_and_the_observation_returns_with_the_next_reset(shape, obs_dtype):
+    """STATE alone, onto a destination that already holds the same instances (at another point of another episode): info, raw,
+    status and state of every later step are equal; the observation is undefined until the next reset, and equal after it"""
+    src, dirty, data, mods = _setup(shape, obs_dtype)
+    batch_env, J, M, E = mods[0], mods[5], mods[6], mods[7]
+    t, p, tt, edge = data
+    dirty.close()
+    T = src.T
+    dst = batch_env.DeviceBatchEnv(J, M, E, BD, obs_dtype=obs_dtype)
+    dst.load_instances(t[INDEX], p[INDEX], tt[INDEX], edge=edge[INDEX]); dst.scaler_init()
+    dst.reset(np.random.RandomState(8).dirichlet([1, 1, 1], BD))
+    a = torch.zeros(BD, dtype=torch.int32, device=dst.device); m = torch.zeros_like(a)
+    for s in range(T // 3):
+        dst.random_actions(5, s, a, m); dst.step(a, m)
+    prefix = [src.step(check=False) for _ in range(T // 2)]
+    dst.fork_from(src.env, INDEX, instance=False, state=True, obs=False)
+    exp = _expected(src, prefix, data, mods, True, f"{shape} {obs_dtype} STATE only", 4)
+    exp.env = dst
+    while exp.steps < T:
+        exp.step(observation=False)
+    assert exp.info[:, 1].all()
+    w3 = np.random.RandomState(6).dirichlet([1, 1, 1], BD)
+    dst.scaler_reset_returns(); exp.orc.scaler_reset_returns()
+    dst.reset(w3); exp.oracle_reset(w3)
+    exp.check("reset after the STATE-only fork")
+    exp.finish()
+    dst.close(); src.env.close()
+
+
+@pytest.mark.parametrize("obs_dtype", ["f32", "f64"])
+@pytest.mark.parametrize("shape", ["J6M6E2", "J3M11E1"])
+def test_instance_only_then_reset_equals_a_freshly_loaded_handle(shape, obs_dtype):
+    src, dst, data, mods = _setup(shape, obs_dtype)
+    capi = mods[2]
+    t, p, tt, edge = data
+    [src.step(check=False) for _ in range(3)]
+    dst.fork_from(src.env, INDEX, instance=True, state=False, obs=False)
+    with pytest.raises(capi.MtfjspError) as e:                          # the constants changed under the old state: reset first
+        dst.step(torch.zeros(BD, dtype=torch.int32, device=dst.device), torch.zeros(BD, dtype=torch.int32, device=dst.device))
+    assert e.value.code == capi.ERR_STATE
+    got = dst.read_instances()
+    for g, w, name in zip(got[:3], (t, p, tt), ("t", "p", "tt")):
+        _same(g, w[INDEX], f"{shape} forked {name}")
+    _same(mods[0].shop_of_machine(got[3]), mods[0].shop_of_machine(edge[INDEX]), f"{shape} forked shops")
+    exp = _expected(src, [], data, mods, True, f"{shape} {obs_dtype} INSTANCE only", 2)
+    exp.env = dst
+    w3 = np.random.RandomState(12).dirichlet([1, 1, 1], BD)
+    dst.scaler_init()
+    dst.reset(w3); exp.oracle_reset(w3)
+    exp.check("reset after the INSTANCE-only fork")
+    exp.finish()                                                        # min_dur / min_pt, means, transposed tt, shops: every constant is used
+    dst.close(); src.env.close()
+
+
+def _bytes(env):
+    """every byte a fork may write: the bound observation and, through the read-out, the state"""
+    capi = _mods()[2]
+    out = [x.cpu().numpy().tobytes() for x in (env.tasks_fea, env.ell_col, env.ell_val, env.m_fea2, env.info, env.raw, env.candidate,
+                                               env.job_mask, env.status)]
+    out += [env.read_state(w).tobytes() for w in (capi.STATE_MACHINE, capi.STATE_START, capi.STATE_FINISH, capi.STATE_ROUTES,
+                                                  capi.STATE_PREV_COSTS, capi.STATE_SCALER, capi.STATE_W3)]
+    out += [np.ascontiguousarray(x).tobytes() for x in env.read_instances()]
+    return out
+
+
+def test_every_error_of_the_contract_returns_its_code_and_writes_nothing():
+    batch_env, inst, capi = _mods()
+    src, dst, data, mods = _setup("J6M6E2", "f64")
+    t, p, tt, edge = data
+    J, M, E = 6, 6, 2
+    L = dst.L
+    idx = torch.as_tensor(INDEX, device=dst.device)
+    before = _bytes(dst)
+
+    def rc(d, s, flags=7, index=idx):
+        return L.mtfjsp_fork(d.h, s.h if s is not None else None, index.data_ptr() if index is not None else None, flags)
+
+    others = dict(n_job=(5, 6, 2, {}), n_machine=(6, 4, 2, {}), n_edge=(6, 6, 3, {}), obs_dtype=(6, 6, 2, dict(obs_dtype="f32")),
+                  left_shift=(6, 6, 2, dict(left_shift=False)))
+    for what, (j, m, e, kw) in others.items():
+        kw = dict(dict(obs_dtype="f64"), **kw)
+        o = batch_env.DeviceBatchEnv(j, m, e, BS, **kw)
+        o.generate_instances(1); o.scaler_init(); o.reset(torch.full((BS, 3), 1 / 3, dtype=torch.float64, device=o.device))
+        assert rc(dst, o) == capi.ERR_ARG, what
+        assert b"differ" in L.mtfjsp_last_error(dst.h)
+        o.close()
+    assert rc(dst, dst) == capi.ERR_ARG                                 # in place
+    assert rc(dst, src.env, 0) == capi.ERR_ARG and rc(dst, src.env, 8) == capi.ERR_ARG
+    assert rc(dst, None) == capi.ERR_ARG and rc(dst, src.env, 7, None) == capi.ERR_ARG
+    fresh = batch_env.DeviceBatchEnv(J, M, E, BS)                        # not loaded
+    assert rc(dst, fresh) == capi.ERR_STATE
+    fresh.load_instances(t, p, tt, edge=edge)                           # loaded, never reset
+    assert rc(dst, fresh, capi.FORK_STATE) == capi.ERR_STATE and rc(dst, fresh, capi.FORK_OBS) == capi.ERR_STATE
+    assert rc(dst, fresh, capi.FORK_INSTANCE | capi.FORK_STATE) == capi.ERR_STATE
+    # OBS without bound observations on either side (handles made through the C interface, nothing bound)
+    def bare(batch):
+        cfg = capi.Config(J, M, E, batch, 1, capi.OBS_F64, 0, 0, 0.99, 0.4, 0.4, 0.2, 1.0)
+        h = C.c_void_p()
+        assert L.mtfjsp_create(C.byref(cfg), C.byref(h)) == 0
+        return h
+    hb = bare(BD)
+    assert L.mtfjsp_fork(hb, src.env.h, idx.data_ptr(), capi.FORK_INSTANCE | capi.FORK_OBS) == capi.ERR_STATE
+    assert L.mtfjsp_fork(hb, src.env.h, idx.data_ptr(), capi.FORK_STATE) == capi.ERR_STATE       # no instances in the destination
+    hs = bare(BS)
+    assert L.mtfjsp_fork(hs, src.env.h, torch.zeros(BS, dtype=torch.int32, device=dst.device).data_ptr(), capi.FORK_INSTANCE | capi.FORK_STATE) == 0
+    assert L.mtfjsp_fork(dst.h, hs, idx.data_ptr(), capi.FORK_OBS) == capi.ERR_STATE             # the source has nothing bound
+    torch.cuda.synchronize()
+    L.mtfjsp_destroy(hb); L.mtfjsp_destroy(hs)
+    after = _bytes(dst)
+    assert all(a == b for a, b in zip(before, after)), "an error return wrote to the destination"
+    fresh.close(); dst.close(); src.env.close()
+
+
+@pytest.mark.parametrize("obs_dtype", ["f32", "f64"])
+def test_an_index_out_of_range_leaves_its_instance_untouched_and_flags_it(obs_dtype):
+    src, dst, data, mods = _setup("J6M6E2", obs_dtype)
+    capi = mods[2]
+    T = src.T
+    prefix = [src.step(check=False) for _ in range(T // 2)]
+    index = INDEX.copy()
+    index[2], index[9] = -1, BS
+    bad = np.array([2, 9])
+    ok = np.setdiff1d(np.arange(BD), bad)
+    fields = ("tasks_fea", "ell_col", "ell_val", "m_fea2", "info", "raw", "candidate", "job_mask")
+
+    def rows(env, sel):
+        out = [getattr(env, f).cpu().numpy().reshape(BD, -1)[sel].tobytes() for f in fields]
+        out += [env.read_state(w).reshape(BD, -1)[sel].tobytes() for w in range(7)]
+        out += [np.ascontiguousarray(x.reshape(BD, -1)[sel]).tobytes() for x in dst.read_instances()]
+        return out
+
+    before, st0 = rows(dst, bad), dst.status.cpu().numpy()
+    dst.fork_from(src.env, index)
+    after, st1 = rows(dst, bad), dst.status.cpu().numpy()
+    assert all(a == b for a, b in zip(before, after)), "an instance with an index out of range was written"
+    _same(st1[bad], st0[bad] | capi.ST_INVALID, "status of the instances with an index out of range")
+    _same(st1[ok], src.env.status.cpu().numpy()[index[ok]], "status of the copied instances")
+    # the rest is right: a handle forked with the valid entries only, compared on those instances
+    good = np.where((index >= 0) & (index < BS), index, 0).astype(np.int32)
+    exp = _expected(src, prefix, data, mods, True, f"J6M6E2 {obs_dtype} partial fork", 1, index=good)
+    obs = lambda x: np.asarray(x, np.float64).astype(exp.odt)           # noqa: E731
+    _same(dst.tasks_fea.cpu().numpy().reshape(BD, -1)[ok], obs(exp.o["tfea"]).reshape(BD, -1)[ok], "tasks_fea")
+    _same(dst.m_fea2.cpu().numpy()[ok], obs(exp.o["mfea2"])[ok], "m_fea2")
+    _same(dst.dense_adj().cpu().numpy()[ok], exp.o["adj"][ok], "dense_adj")
+    _same(dst.candidate.cpu().numpy()[ok], exp.cand[ok], "candidate"); _same(dst.job_mask.cpu().numpy()[ok], exp.mask[ok], "job_mask")
+    _same(dst.info.cpu().numpy()[ok], exp.info[ok], "info"); _same(dst.raw.cpu().numpy()[ok], exp.raw[ok], "raw")
+    so = exp.orc.state()
+    _same(dst.read_state(capi.STATE_MACHINE)[ok], so["mach"][ok], "machines"); _same(dst.read_state(capi.STATE_ROUTES)[ok], so["routes"][ok], "routes")
+    _same_nan(dst.read_state(capi.STATE_START)[ok], so["st"][ok], "start times"); _same_nan(dst.read_state(capi.STATE_FINISH)[ok], so["ft"][ok], "finish times")
+    _same(dst.read_state(capi.STATE_PREV_COSTS)[ok], so["prev"][ok], "previous costs"); _same(dst.read_state(capi.STATE_SCALER)[ok], so["scaler"][ok], "scaler")
+    _same(dst.read_state(capi.STATE_W3)[ok], src.w3[index[ok]], "reward weights")
+    dst.close(); src.env.close()

@@ -1,0 +1,95 @@
+"""GPU: the device's one-step look-ahead (mtfjsp_lookahead_expand / the ordinary step / mtfjsp_lookahead_select,
+baselines.Lookahead and lookahead_baselines) EQUALS the host model of tests/lookahead_ref.py — the same (task, machine) at every step
+of the episode and the winning value bit for bit, for all five columns; no tolerance.  J9M8 has more than 64 copies per instance
+(the strided pass of the selection)."""
+from importlib import import_module
+
+import numpy as np
+import pytest
+import torch
+
+import lookahead_ref as ref
+from env_parity import _same
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = {"J3M4": (3, 4, 2, 7), "J6M6": (6, 6, 2, 5), "J5M12": (5, 12, 2, 2), "J9M8": (9, 8, 2, 2)}
+
+
+def _mods():
+    import mtfjsp_amd  # noqa: F401
+    return (import_module("e2e-mappo-for-mt-fjsp_amd.batch_env"), import_module("e2e-mappo-for-mt-fjsp_amd.baselines"),
+            import_module("e2e-mappo-for-mt-fjsp_amd.capi"))
+
+
+@pytest.mark.parametrize("column", range(5))
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_every_decision_of_the_episode_equals_the_model(shape, column):
+    batch_env, baselines, capi = _mods()
+    J, M, E, B = SHAPES[shape]
+    T = J * M
+    (t, p, tt, edge, w3), task, mach, best = ref.cached_episode(J, M, E, B, column, True)
+    env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=True, obs_dtype="f32", w_cfg=ref.CONFIG_W)
+    env.load_instances(t, p, tt, edge=edge); env.scaler_init(); env.reset(w3)
+    la = baselines.Lookahead(env)
+    for s in range(T):
+        a, m = la.decide(column)
+        tag = f"{shape} column {column} step {s}"
+        _same(a.cpu().numpy(), task[s], tag + " task"); _same(m.cpu().numpy(), mach[s], tag + " machine")
+        _same(la.job.cpu().numpy(), task[s] // M, tag + " job")
+        _same(la.best.cpu().numpy().view(np.int64), best[s].view(np.int64), tag + " best value (bits)")
+        env.step(a, m)
+        assert not (env.status.cpu().numpy() & (capi.ST_INVALID | capi.ST_INFEASIBLE)).any(), tag
+        _same(env.raw.cpu().numpy()[:, column], best[s], tag + " the source's step yields the value the copy promised")
+    assert bool(env.info[:, 1].all().item())
+    la.close(); env.close()
+
+
+@pytest.mark.parametrize("column", [0, 2])
+def test_a_finished_instance_beside_running_ones(column):
+    batch_env, baselines, capi = _mods()
+    J, M, E, B = SHAPES["J3M4"]
+    T = J * M
+    (t, p, tt, edge, w3), task, mach, best = ref.cached_episode(J, M, E, B, column, True)
+    env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=True, obs_dtype="f64", w_cfg=ref.CONFIG_W)
+    env.load_instances(t, p, tt, edge=edge); env.scaler_init(); env.reset(w3)
+    # instance 2 alone plays the model's whole episode: the others get task -1, which the step rejects and leaves untouched
+    only = np.arange(B) == 2
+    for s in range(T):
+        a = torch.as_tensor(np.where(only, task[s], -1).astype(np.int32), device=env.device)
+        m = torch.as_tensor(np.where(only, mach[s], 0).astype(np.int32), device=env.device)
+        env.step(a, m)
+    assert env.info.cpu().numpy()[2, 1] == 1.0
+    la = baselines.Lookahead(env)
+    a, m = la.decide(column)
+    a, m, j, b = a.cpu().numpy(), m.cpu().numpy(), la.job.cpu().numpy(), la.best.cpu().numpy()
+    assert a[2] == -1 and m[2] == -1 and j[2] == -1 and np.isnan(b[2])
+    _same(a[~only], task[0][~only], "running instances: task"); _same(m[~only], mach[0][~only], "running instances: machine")
+    _same(b[~only].view(np.int64), best[0][~only].view(np.int64), "running instances: best value (bits)")
+    la.close(); env.close()
+
+
+@pytest.mark.parametrize("left_shift", [True, False], ids=["left_shift", "no_left_shift"])
+def test_lookahead_baselines_equal_the_oracle_driven_by_the_models_plans(left_shift):
+    from oracle.env_oracle import OracleBatch
+    _, baselines, _ = _mods()
+    J, M, E, B = SHAPES["J6M6"]
+    T = J * M
+    args = dict(n_job=J, n_machine=M, n_edge=E, weight_mk=ref.CONFIG_W[0], weight_ec=ref.CONFIG_W[1], weight_tt=ref.CONFIG_W[2])
+    data = ref.cached_episode(J, M, E, B, 0, left_shift)[0]
+    t, p, tt, edge, w3 = data
+    res = baselines.lookahead_baselines(t, p, tt, edge, args, left_shift=left_shift)
+    assert sorted(res) == sorted([r[0] for r in baselines.LOOKAHEAD_RULES] + [baselines.PLANS])
+    for name, column in baselines.LOOKAHEAD_RULES:
+        _, task, mach, _ = ref.cached_episode(J, M, E, B, column, left_shift)
+        _same(res[baselines.PLANS][name][0], np.ascontiguousarray(task.T), f"{name} plan: tasks")
+        _same(res[baselines.PLANS][name][1], np.ascontiguousarray(mach.T), f"{name} plan: machines")
+        orc = OracleBatch(t, p, tt, edge, left_shift=left_shift, w_cfg=ref.CONFIG_W); orc.scaler_init(); orc.reset(w3)
+        cum = np.zeros((B, 5))
+        for s in range(T):
+            cum += orc.step(task[s], mach[s])[1]
+        prev = orc.state()["prev"]
+        cost, final4, obj = res[name]
+        for k, key in enumerate(("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")):
+            _same(cost[key], cum[:, k], f"{name} {key}")
+        _same(final4, np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1), f"{name} Final_4cost")
