@@ -294,8 +294,9 @@ class Parallel_env(object):
 
     def _step_one(self, i, a, m):
         """per-env gym step of instance i (proxy.step / DisjunctiveGraphJspEnv_singleStep.step, env:716-974): every other instance
-        gets task index -1, which the kernel rejects leaving its STATE untouched (MTFJSP_ST_INVALID; its info / raw reward rows of
-        the last batched step are cleared).  The fused step kernel also applies RewardScaling, which the reference's env.step never
+        gets task index -1, which the kernel rejects leaving its state and observation untouched (include/mtfjsp.h at
+        MTFJSP_ST_INVALID states what a rejected step writes: info = [0, done, 0, 0, 0, 0] and raw = 0 over the rows of the last
+        batched step, status = MTFJSP_ST_INVALID).  The fused step kernel also applies RewardScaling, which the reference's env.step never
         does (only the batched step, pe:255-260): instance i's scaler state is saved before and restored after the launch, so
         mixing proxy steps with DGFJSPEnv_paral_step leaves the scaled rewards exactly the reference's."""
         B, T, M = self.batch_size, self.ntasks, self.nmachines

@@ -58,7 +58,17 @@ enum {
     MTFJSP_PATH_APPEND = 3,          /*   appended */
     MTFJSP_ST_INVALID = 0x100,       /* already scheduled / job predecessor unscheduled / index out of range:
                                         the instance is left untouched (the reference silently corrupts node
-                                        attributes here, env:1496-1528; never reached under the masks) */
+                                        attributes here, env:1496-1528; never reached under the masks).
+                                        A REJECTED step moves nothing of the instance — scheduling state, the 17
+                                        RewardScaling words, tasks_fea, ELL rows, m_fea2, candidate, job_mask — and
+                                        writes only its per-step outputs:
+                                          status  = MTFJSP_ST_INVALID exactly (no path bits, no ST_INFEASIBLE)
+                                          info    = [0, done, 0, 0, 0, 0]
+                                          raw     = [0, 0, 0, 0, 0]
+                                          r4_out  = [0, 0, 0, 0], done_out = done   (mtfjsp_step_record)
+                                        with done = 1 iff all T tasks of the instance are scheduled already (a finished
+                                        instance that keeps receiving actions keeps reporting done), else 0.  The
+                                        other instances of the batch, of the same workgroup included, step as usual */
     MTFJSP_ST_INFEASIBLE = 0x200     /* t[a,m] < 0 chosen (pe:246-248 prints a warning and carries on; so do we) */
 };
 
@@ -153,10 +163,14 @@ int mtfjsp_reset_episode(mtfjsp_handle_t h, uint64_t seed, uint64_t episode, dou
 int mtfjsp_reset_host(mtfjsp_handle_t h, const double *w3_host);
 
 /* = DGFJSPEnv_paral_step (pe:217-268): env.step (env:716-974) + RewardScaling (pe:255-260), fused with
- * the candidate / job-mask update of ppo:202-316.  One launch; writes every bound obs field. */
+ * the candidate / job-mask update of ppo:202-316.  One launch; writes every bound obs field.
+ * Actions are judged per instance: an instance with a bad action (MTFJSP_ST_INVALID above) is skipped — state and observation
+ * untouched, info = [0, done, 0, 0, 0, 0], raw = 0, status = MTFJSP_ST_INVALID, done = 1 once the instance is finished — while
+ * the others step; the device entry points return MTFJSP_OK either way (the caller reads status). */
 int mtfjsp_step(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx);
 /* same launch, additionally recording this step's trajectory entries as f32 for the advantage computation
- * (SURVEY Appendix A rows 11,17-20): r4_out [4,B] = scaled mk, idle, pt, tt (pe:255-262 order) ; done_out [B]. */
+ * (SURVEY Appendix A rows 11,17-20): r4_out [4,B] = scaled mk, idle, pt, tt (pe:255-262 order) ; done_out [B]:
+ * the float32 of info[b][2..5] and of info[b][1].  A rejected instance gets r4_out[:, b] = 0 and done_out[b] = done as above. */
 int mtfjsp_step_record(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4_out, float *done_out);
 /* The step as the TAIL of the launch that selects the machines (Run.py:363-427: machine actor forward, then env.step, nothing in
  * between): mtfjsp_step_params fills an opaque parameter block (mtfjsp_step_params_bytes() bytes) for exactly the step that
@@ -167,7 +181,8 @@ int mtfjsp_step_record(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t
 int32_t mtfjsp_step_params_bytes(void);
 int mtfjsp_step_params(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4_out, float *done_out,
                        void *params_out, int32_t params_bytes);
-/* host variant: returns MTFJSP_ERR_ACTION if any status word carries MTFJSP_ST_INVALID */
+/* host variant: returns MTFJSP_ERR_ACTION if any status word carries MTFJSP_ST_INVALID — AFTER the launch: the valid instances of
+ * the batch have been stepped, the rejected ones hold the outputs above; mtfjsp_last_error names the first rejected instance */
 int mtfjsp_step_host(mtfjsp_handle_t h, const int32_t *task_idx_host, const int32_t *mach_idx_host);
 
 /* = cal_cur_task_machine_feature (pe:152-214): out [B,M,6] obs_dtype, mmask_out [B,M] (1 = infeasible; may be
