@@ -22,6 +22,14 @@ def shop_of_machine(edge):
     return out
 
 
+def step_kernel_for(n_job, n_machine, batch, obs_f32=False, lds_max=160 * 1024):
+    """(name, instances per workgroup, bytes of one instance's LDS region, any diagnostic switch set) of the step kernel a handle of
+    this shape launches where a workgroup may use `lds_max` bytes of LDS (gfx950: 160 KiB): the library's own selection, no GPU needed"""
+    g, nb, ov = C.c_int32(), C.c_int64(), C.c_int32()
+    name = capi.lib().mtfjsp_step_kernel_name_for(n_job, n_machine, batch, int(bool(obs_f32)), lds_max, C.byref(g), C.byref(nb), C.byref(ov))
+    return name.decode(), g.value, nb.value, bool(ov.value)
+
+
 class DeviceBatchEnv:
     def __init__(self, n_job, n_machine, n_edge, batch, left_shift=True, obs_dtype="f64", device=0,
                  gamma=0.99, w_cfg=(0.4, 0.4, 0.2), scaling_divisor=1.0):
@@ -176,6 +184,10 @@ class DeviceBatchEnv:
         """device step that also writes this step's f32 trajectory entries: r4_out [4,B], done_out [B] (contiguous views)"""
         assert r4_out.is_contiguous() and done_out.is_contiguous() and r4_out.dtype == torch.float32
         capi.check(self.L.mtfjsp_step_record(self.h, task_idx.data_ptr(), mach_idx.data_ptr(), r4_out.data_ptr(), done_out.data_ptr()), self.h)
+
+    def step_kernel_name(self):
+        """the step kernel the next step() launches (shape, this device's LDS, the diagnostic switches as they are now)"""
+        return self.L.mtfjsp_step_kernel_name(self.h).decode()
 
     def step_params(self, task_idx, mach_idx, r4_out=None, done_out=None):
         """the parameter block of exactly the step that step() / step_record() with these arguments would launch, for

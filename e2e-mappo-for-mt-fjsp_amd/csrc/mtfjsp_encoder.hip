@@ -4329,7 +4329,7 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
         const EnvParams &EP = e->env_step.P;
         const bool env_tail = with_mheads && e->env_step.armed && e->fuse_env3 && !e->timing && hm_args.sample_mode && ha.sample_mode &&
                               (const void *)hm_args.idx_out == (const void *)EP.mach_idx && (const void *)ha.gathered_out == (const void *)EP.task_idx &&
-                              EP.B == B && EP.M == e->cfg.n_machine && EP.T <= 64 && EP.M * EP.M <= 64 && EP.J <= 64 && fused3_lds_bytes() >= EnvGrpDynLds<1>::bytes;
+                              EP.B == B && EP.M == e->cfg.n_machine && env_one_slot(EP.J, EP.M, EP.T) && fused3_lds_bytes() >= EnvGrpDynLds<1>::bytes;
         if (e->env_step.armed && with_mheads) { e->env_step.armed = false; e->env_step.done = env_tail; }
         launch_heads(e, ha, "job_actor.o_policy", "job_actor.job_critic", with_gat ? &ga : nullptr, env_tail ? &EP : nullptr, with_mheads ? &hm_args : nullptr);
         e->vo_now = false;
@@ -4419,7 +4419,7 @@ static int machine_actor_forward_impl(mtfjsp_encoder_t e, const void *m_fea1, co
         // reads, the shapes agree and the launch is the split-product heads kernel; otherwise the caller steps the environment itself
         const EnvParams &EP = e->env_step.P;
         const bool env_tail = e->env_step.armed && e->fuse_env && !e->timing && !e->bn_mode && !(e->f32_products & 4) && ha.sample_mode &&
-                              (const void *)ha.idx_out == (const void *)EP.mach_idx && EP.B == B && EP.M == M && EP.T <= 64 && EP.M * EP.M <= 64 && EP.J <= 64;
+                              (const void *)ha.idx_out == (const void *)EP.mach_idx && EP.B == B && EP.M == M && env_one_slot(EP.J, EP.M, EP.T);
         e->env_step.armed = false; e->env_step.done = env_tail;
         launch_heads(e, ha, "machine_actor.m_policy", "machine_actor.machine_critic", nullptr, (env_tail && !e->vo_now) ? &EP : nullptr);
         e->vo_now = false;

@@ -594,16 +594,6 @@ __global__ __launch_bounds__(WAVE, 4) void k_env_step(EnvParams P)
 #endif
 #undef DIVM
 }
-static size_t env_step_lds_bytes(int J, int M, int T, bool f32)
-{
-    const int Tp = (T + 7) & ~7;
-    size_t off = (size_t)(4 * T + Tp + M * M + 3 * M + 2 * J + SCAL_N + 8) * sizeof(double);
-    off = (off + 15) & ~(size_t)15;
-    off += (size_t)M * 12 * (f32 ? 4 : 8);
-    off = (off + 15) & ~(size_t)15;
-    off += (size_t)(3 * T + J + 4 * M + 1 + 4) * sizeof(int);
-    return off;
-}
 
 // =================================================================================================
 // k_env_reg — the step kernel for instances with T <= 64 and M*M <= 64 (J6M6E2 and the like): NO LDS.
@@ -953,45 +943,7 @@ __global__ __launch_bounds__(WAVE) void k_env_reg(EnvParams P)
 // of the step per wave, then — after one barrier — the per-instance scalar part (energy / idle sums, rewards, RewardScaling,
 // machine feature row, job mask) once for the whole group on wave 0 with lane = (instance, reward channel)
 // (env_grp_tail, mtfjsp_env_grp.h).  Same operations in the same order: bit-identical to k_env_step.
-#define ENV_LDS_GMAX 8                         // instances (= waves) per workgroup of k_env_step_grp at most
-struct EnvStepLds {                            // layout of one instance's LDS region
-    int T, Tp, M, J, nleaf;
-    // f64 part, offsets in doubles: start | finish | processing energy per task, idle terms in rank order, column m of the transport
-    // times, the acting job's min durations / estimated starts / finishes, per-job maxima, scalars, the acting machine's feature
-    // row, leaf sums of the pairwise energy sum.  (Round 3: 18.0 KB per J20M20 instance instead of 26.7 — durations and the other
-    // transport columns are read from memory by the few lanes that need one, route links are 16-bit — so that 8 instances fit a CU
-    // and 2048 of them run in ONE round of workgroups: 2 x 29 us of dependent chain -> 1 x.)
-    int d_ft, d_pte, d_term, d_ttc, d_mind, d_jste, d_jfte, d_jmax, d_jrow, d_sc, d_mfr, d_leaf, d_end;
-    size_t o_stage, o_link, o_int, o_un, o_in, bytes;          // bytes from the region's start
-    __host__ __device__ EnvStepLds(int J_, int M_, int T_, bool f32, int nleaf_) : T(T_), Tp((T_ + 7) & ~7), M(M_), J(J_), nleaf(nleaf_)
-    {
-        d_ft = T; d_pte = 2 * T; d_term = 3 * T; d_ttc = d_term + Tp; d_mind = d_ttc + M; d_jste = d_mind + M; d_jfte = d_jste + M;
-        d_jmax = d_jfte + M; d_jrow = d_jmax + J; d_sc = d_jrow + J; d_mfr = d_sc + SCAL_N; d_leaf = d_mfr + 8; d_end = d_leaf + nleaf;
-        size_t off = (size_t)d_end * sizeof(double);
-        off = (off + 15) & ~(size_t)15;
-        o_stage = off; off += (size_t)M * 12 * (f32 ? 4 : 8);
-        off = (off + 15) & ~(size_t)15;
-        o_link = off; off += (size_t)3 * T * sizeof(short);     // machine | route predecessor | rank per task
-        off = (off + 15) & ~(size_t)15;
-        o_int = off; off += (size_t)(J + 4 * M + 1 + 4) * sizeof(int);
-        off = (off + 15) & ~(size_t)15;
-        o_un = off; off += 16 * sizeof(double);
-        o_in = off; off += 8 * sizeof(int);
-        bytes = (off + 15) & ~(size_t)15;
-    }
-};
-// numpy's pairwise recursion (n > 128: halves, the left one rounded down to a multiple of 8) as a table the step kernel walks:
-// [2l], [2l+1] = offset, length of leaf l (in order); then nleaf - 1 merges (i, j): leaf-sum slot i += slot j, in post-order, so
-// that the total ends in slot 0.  Depends on T only; built once per handle.
-static int pw_table(int off, int n, int depth, std::vector<short> &leaves, std::vector<short> &merges)
-{
-    if (n <= 128 || depth == 0) { const int idx = (int)leaves.size() / 2; leaves.push_back((short)off); leaves.push_back((short)n); return idx; }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    const int l = pw_table(off, n2, depth - 1, leaves, merges), r = pw_table(off + n2, n - n2, depth - 1, leaves, merges);
-    merges.push_back((short)l); merges.push_back((short)r);
-    return l;
-}
+// (EnvStepLds, the layout of one instance's LDS region, and ENV_LDS_GMAX: mtfjsp_env_select.h)
 struct EnvGrpLdsAcc {
     static constexpr bool kBigT = true;
     const unsigned char *base; EnvStepLds L;
@@ -1964,9 +1916,10 @@ extern "C" int mtfjsp_scaler_reset_returns_masked_host(mtfjsp_handle_t h, const 
     return MTFJSP_OK;
 }
 
-static EnvParams make_params(mtfjsp_env *h)
+static EnvParams make_params(mtfjsp_env *h, const int32_t *task_idx = nullptr, const int32_t *mach_idx = nullptr, float *r4 = nullptr, float *dn = nullptr)
 {
     EnvParams P{};
+    P.task_idx = task_idx; P.mach_idx = mach_idx; P.rec_r4 = r4; P.rec_done = dn;
     P.B = h->cfg.batch; P.J = h->cfg.n_job; P.M = h->cfg.n_machine; P.T = h->T;
     P.left_shift = h->cfg.left_shift; P.obs_f32 = h->cfg.obs_dtype == MTFJSP_OBS_F32;
     P.w_mk = h->cfg.w_mk; P.w_ec = h->cfg.w_ec; P.w_tt = h->cfg.w_tt; P.divisor = h->cfg.scaling_divisor; P.gamma = h->cfg.gamma;
@@ -1986,37 +1939,33 @@ static int check_ready(mtfjsp_env *h, bool need_reset)
     return MTFJSP_OK;
 }
 
-extern "C" int mtfjsp_reset(mtfjsp_handle_t h, const double *w3)
+// mtfjsp_reset and mtfjsp_reset_episode: P = make_params(h) and the entry point's own fields
+static int reset_launch(mtfjsp_env *h, const EnvParams &P)
 {
-    if (!h || !w3) return MTFJSP_ERR_ARG;
     int rc = check_ready(h, false);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    EnvParams P = make_params(h);
-    P.w3 = w3;
-    const size_t lds = env_reset_lds_bytes(P.T, P.obs_f32);
-    if (P.obs_f32) hipLaunchKernelGGL((k_env_reset<float>), dim3(P.B), dim3(WAVE), lds, h->stream, P);
-    else hipLaunchKernelGGL((k_env_reset<double>), dim3(P.B), dim3(WAVE), lds, h->stream, P);
+    static void (*const fn[2])(EnvParams) = {k_env_reset<float>, k_env_reset<double>};
+    hipLaunchKernelGGL(fn[!P.obs_f32], dim3(P.B), dim3(WAVE), env_reset_lds_bytes(P.T, P.obs_f32), h->stream, P);
     HIPCHK(h, hipGetLastError());
     h->was_reset = true;
     return MTFJSP_OK;
+}
+extern "C" int mtfjsp_reset(mtfjsp_handle_t h, const double *w3)
+{
+    if (!h || !w3) return MTFJSP_ERR_ARG;
+    EnvParams P = make_params(h);
+    P.w3 = w3;
+    return reset_launch(h, P);
 }
 // reset of an EPISODE in one launch: scaler_reset_returns + draw_reward_weights + reset (run:283-284, env:1253-1259, pe:87) — what the
 // accelerated rollout issued as three launches per episode
 extern "C" int mtfjsp_reset_episode(mtfjsp_handle_t h, uint64_t seed, uint64_t episode, double *w3_out, int32_t reset_returns)
 {
     if (!h || !w3_out) return MTFJSP_ERR_ARG;
-    int rc = check_ready(h, false);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
     EnvParams P = make_params(h);
     P.w3 = nullptr; P.draw = 1; P.draw_seed = seed; P.draw_episode = episode; P.w3_out = w3_out; P.reset_returns = reset_returns ? 1 : 0;
-    const size_t lds = env_reset_lds_bytes(P.T, P.obs_f32);
-    if (P.obs_f32) hipLaunchKernelGGL((k_env_reset<float>), dim3(P.B), dim3(WAVE), lds, h->stream, P);
-    else hipLaunchKernelGGL((k_env_reset<double>), dim3(P.B), dim3(WAVE), lds, h->stream, P);
-    HIPCHK(h, hipGetLastError());
-    h->was_reset = true;
-    return MTFJSP_OK;
+    return reset_launch(h, P);
 }
 extern "C" int mtfjsp_reset_host(mtfjsp_handle_t h, const double *w3_host)
 {
@@ -2029,16 +1978,34 @@ extern "C" int mtfjsp_reset_host(mtfjsp_handle_t h, const double *w3_host)
     return MTFJSP_OK;
 }
 
-static int step_impl(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4, float *dn);
-extern "C" int mtfjsp_step(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx) { return step_impl(h, task_idx, mach_idx, nullptr, nullptr); }
-extern "C" int mtfjsp_step_record(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4_out, float *done_out)
+// The launch of a step: mtfjsp_env_select.h's rule on this handle and the diagnostic switches as they are NOW (read per call).
+// all = false (mtfjsp_step): MTFJSP_ENV_STEP_G is read only where it bears on the launch — the register path reads two switches per call.
+static EnvStepPlan step_plan(const mtfjsp_env *h, bool all)
 {
-    if (!r4_out || !done_out) return MTFJSP_ERR_ARG;
-    return step_impl(h, task_idx, mach_idx, r4_out, done_out);
+    const char *force = getenv("MTFJSP_ENV_KERNEL"), *lds = getenv("MTFJSP_ENV_LDS"), *g = all ? getenv("MTFJSP_ENV_STEP_G") : nullptr;
+    const auto plan = [&] { return env_step_plan(h->cfg.n_job, h->cfg.n_machine, h->cfg.batch, h->cfg.obs_dtype == MTFJSP_OBS_F32, h->lds_max, h->grp_lds_ok, h->pw_nleaf, force, lds, g); };
+    EnvStepPlan pl = plan();
+    if (!all && pl.lds_inst && (g = getenv("MTFJSP_ENV_STEP_G"))) pl = plan();
+    return pl;
 }
+extern "C" const char *mtfjsp_step_kernel_name(mtfjsp_handle_t h) { return h ? ENV_KERNEL_NAME[step_plan(h, true).kernel] : nullptr; }
+extern "C" const char *mtfjsp_step_kernel_name_for(int32_t n_job, int32_t n_machine, int32_t batch, int32_t obs_f32, int64_t lds_max, int32_t *g_out,
+                                                   int64_t *lds_bytes_out, int32_t *overridden_out)
+{
+    if (n_job < 1 || n_machine < 2 || n_machine > 64 || batch < 1 || (long)n_job * n_machine > 32767 || lds_max < 0) return nullptr;
+    mtfjsp_env e;                                                          // no device is touched: only the fields the rule reads
+    e.cfg.n_job = n_job; e.cfg.n_machine = n_machine; e.cfg.batch = batch; e.cfg.obs_dtype = obs_f32 ? MTFJSP_OBS_F32 : MTFJSP_OBS_F64;
+    e.lds_max = (size_t)lds_max; e.pw_nleaf = pw_nleaf(n_job * n_machine);
+    const EnvStepPlan pl = step_plan(&e, true);
+    if (g_out) *g_out = pl.G;
+    if (lds_bytes_out) *lds_bytes_out = (int64_t)pl.lds_inst;
+    if (overridden_out) *overridden_out = pl.overridden;
+    return ENV_KERNEL_NAME[pl.kernel];
+}
+
 // The parameter block of the step kernel for a launch that runs the step as its own tail (mtfjsp_encoder_arm_env_step: the machine
 // actor's heads kernel).  Returns 1 and fills `out` when this handle's step is the 16-instance register kernel (k_env_grp16) and
-// nothing asks for the stand-alone launch (kernel-time recording, MTFJSP_ENV_KERNEL); 0 when the caller has to call mtfjsp_step /
+// nothing asks for the stand-alone launch (kernel-time recording, a diagnostic switch); 0 when the caller has to call mtfjsp_step /
 // mtfjsp_step_record itself; < 0 on errors.  The step has no host-side state: a parameter block that is never used costs nothing.
 extern "C" int32_t mtfjsp_step_params_bytes(void) { return (int32_t)sizeof(EnvParams); }
 extern "C" int mtfjsp_step_params(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4_out, float *done_out, void *out, int32_t out_bytes)
@@ -2047,21 +2014,65 @@ extern "C" int mtfjsp_step_params(mtfjsp_handle_t h, const int32_t *task_idx, co
     if ((r4_out == nullptr) != (done_out == nullptr)) return MTFJSP_ERR_ARG;
     int rc = check_ready(h, true);
     if (rc) return rc;
-    EnvParams P = make_params(h);
-    P.task_idx = task_idx; P.mach_idx = mach_idx; P.rec_r4 = r4_out; P.rec_done = done_out;
-    const bool eligible = !h->timing && !getenv("MTFJSP_ENV_KERNEL") && !getenv("MTFJSP_ENV_LDS") && P.T <= 64 && P.M * P.M <= 64 && P.J <= 64 && P.B <= EG_SMALL_MAX_B;
-    if (!eligible) return 0;
+    if (h->timing) return 0;
+    const EnvStepPlan pl = step_plan(h, true);
+    if (pl.kernel != ENV_K_GRP16 || pl.overridden) return 0;
+    EnvParams P = make_params(h, task_idx, mach_idx, r4_out, done_out);
     memcpy(out, &P, sizeof(EnvParams));
     return 1;
 }
+#ifdef MTFJSP_STAMP
+// the in-kernel timeline of the step that has just been launched (plan `pl`), every ninth call
+static void stamp_report(mtfjsp_env *h, const EnvParams &P, const EnvStepPlan &pl)
+{
+    static int printed = 0;
+    if (!(getenv("MTFJSP_STAMP_PRINT") && (printed++ % 9) == 4 && printed < 60)) return;
+    (void)hipStreamSynchronize(h->stream);
+    std::vector<unsigned long long> hst((size_t)P.B * 8);
+    (void)hipMemcpy(hst.data(), P.stamps, (size_t)P.B * 64, hipMemcpyDeviceToHost);
+    if (pl.kernel == ENV_K_STEP_GRP) {                                  // s_memrealtime stamps (100 MHz) per instance; slot 7 by the group's first
+        unsigned long long t0 = ~0ull; double r[8] = {0}; int n7 = 0;
+        for (int w = 0; w < P.B; w++) t0 = hst[(size_t)w * 8] < t0 ? hst[(size_t)w * 8] : t0;
+        for (int w = 0; w < P.B; w++) for (int i = 0; i < 8; i++) { if (i == 7 && hst[(size_t)w * 8 + 7] < t0) continue; r[i] += (double)(hst[(size_t)w * 8 + i] - t0) / 100.0; if (i == 7) n7++; }
+        for (int i = 0; i < 7; i++) r[i] /= P.B;
+        r[7] /= n7 ? n7 : 1;
+        printf("STAMP k_env_step_grp B=%d (us since the first wave's start): entry %.2f  loads in LDS %.2f  scheduled %.2f  estimates %.2f  terms+energy sum %.2f  observation+ELL %.2f  wave done %.2f  tail drained %.2f\n",
+               P.B, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
+    } else if (pl.kernel <= ENV_K_GRP4) {                               // grouped register kernels: s_memrealtime stamps (100 MHz) of wave 0 per workgroup
+        const int ng = pl.grid; double r[8] = {0};
+        unsigned long long t0 = ~0ull;
+        for (int w = 0; w < ng; w++) t0 = hst[(size_t)w * 8] < t0 ? hst[(size_t)w * 8] : t0;
+        for (int w = 0; w < ng; w++) for (int i = 0; i < 8; i++) r[i] += (double)(hst[(size_t)w * 8 + i] - t0) / 100.0 / ng;
+#ifdef MTFJSP_STAMP_WAVES
+        if (pl.kernel == ENV_K_GRP16 && ng == 256) {                    // (the per-wave slots are laid out for 256 groups of 16)
+            double e[16] = {0}, f[16] = {0}, c[16] = {0}, dn[16] = {0};
+            for (int w = 0; w < ng; w++) for (int g = 0; g < 16; g++) {
+                e[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4] - t0) / 100.0 / ng; f[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4 + 1] - t0) / 100.0 / ng;
+                c[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4 + 2] - t0) / 100.0 / ng; dn[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4 + 3] - t0) / 100.0 / ng;
+            }
+            for (int g = 0; g < 16; g++) printf("STAMPW wave %2d: entry %.2f first-hop %.2f costs %.2f done %.2f\n", g, e[g], f[g], c[g], dn[g]);
+            double t2[4] = {0};
+            for (int w = 0; w < ng; w++) for (int i = 0; i < 4; i++) t2[i] += (double)(hst[2048 + 256 * 64 + (size_t)w * 4 + i] - t0) / 100.0 / ng;
+            printf("STAMPT scalar-part wave: inputs read %.2f  idle sum done %.2f  rewards + scaling done %.2f  machine row done %.2f\n", t2[0], t2[1], t2[2], t2[3]);
+        }
+#endif
+        printf("STAMP k_env_grp16 B=%d (us since the first workgroup's start, wave 0): entry %.2f  first-hop data %.2f  decision %.2f  per-task costs done %.2f  wave done %.2f  barrier %.2f  scalar-part wave done %.2f  ELL/mask wave done %.2f\n",
+               P.B, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
+    } else {                                                            // k_env_reg, k_env_step: cycle counts per wave
+        double m[8] = {0};
+        for (int w = 0; w < P.B; w++) for (int i = 0; i < 8; i++) m[i] += (double)hst[(size_t)w * 8 + i] / P.B;
+        printf("STAMP k_env B=%d: load %.0f  schedule %.0f  estimate+terms %.0f  lane0-costs %.0f  scaler+info %.0f  observation %.0f  mask %.0f+writeback-issue  drain %.0f  (cycles/wave)\n",
+               P.B, m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
+    }
+}
+#endif
 static int step_impl(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4, float *dn)
 {
     if (!h || !task_idx || !mach_idx) return MTFJSP_ERR_ARG;
     int rc = check_ready(h, true);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    EnvParams P = make_params(h);
-    P.task_idx = task_idx; P.mach_idx = mach_idx; P.rec_r4 = r4; P.rec_done = dn;
+    EnvParams P = make_params(h, task_idx, mach_idx, r4, dn);
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
     if (h->timing) {
         if (h->ev_used == h->ev_pool.size()) {
@@ -2077,100 +2088,26 @@ static int step_impl(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *
     if (!d_st) (void)hipMalloc((void **)&d_st, (size_t)P.B * 64);
     P.stamps = d_st;
 #endif
-    // diagnostic / test overrides of the kernel selection (read per call): MTFJSP_ENV_KERNEL = lds | reg1 | grp16 | grp4
-    const char *force = getenv("MTFJSP_ENV_KERNEL");
-    const bool force_lds = getenv("MTFJSP_ENV_LDS") || (force && (!strcmp(force, "lds") || !strcmp(force, "lds1")));
-    const bool force_reg1 = force && !strcmp(force, "reg1");
-    const bool reg_ok = P.T <= 64 && P.M * P.M <= 64 && P.J <= 64 && !force_lds;
-    const bool reg2_ok = !reg_ok && P.T <= 128 && P.M * P.M <= 128 && P.M <= 16 && P.J <= 64 && !force_lds && !force_reg1;
-    if (reg2_ok) {                                                        // register kernel with two task slots per lane
-        const bool small = force && !strcmp(force, "grp16") ? true : force && !strcmp(force, "grp4") ? false : P.B <= EG_SMALL_MAX_B / 2;
-        if (small) {
-            const int grid = (P.B + EG_SMALL - 1) / EG_SMALL;
-            if (P.obs_f32) hipLaunchKernelGGL((k_env_grp16x2<float>), dim3(grid), dim3(EG_SMALL * WAVE), 0, h->stream, P);
-            else hipLaunchKernelGGL((k_env_grp16x2<double>), dim3(grid), dim3(EG_SMALL * WAVE), 0, h->stream, P);
-        } else {
-            const int grid = (P.B + EG_LARGE - 1) / EG_LARGE;
-            if (P.obs_f32) hipLaunchKernelGGL((k_env_grp4x2<float>), dim3(grid), dim3(EG_LARGE * WAVE), 0, h->stream, P);
-            else hipLaunchKernelGGL((k_env_grp4x2<double>), dim3(grid), dim3(EG_LARGE * WAVE), 0, h->stream, P);
-        }
-    } else if (reg_ok && !force_reg1) {                                   // register kernel, groups of instances per workgroup
-        const bool small = force && !strcmp(force, "grp16") ? true : force && !strcmp(force, "grp4") ? false : P.B <= EG_SMALL_MAX_B;
-        if (small) {
-            const int grid = (P.B + EG_SMALL - 1) / EG_SMALL;
-            if (P.obs_f32) hipLaunchKernelGGL((k_env_grp16<float>), dim3(grid), dim3(EG_SMALL * WAVE), 0, h->stream, P);
-            else hipLaunchKernelGGL((k_env_grp16<double>), dim3(grid), dim3(EG_SMALL * WAVE), 0, h->stream, P);
-        } else {
-            const int grid = (P.B + EG_LARGE - 1) / EG_LARGE;
-            if (P.obs_f32) hipLaunchKernelGGL((k_env_grp4<float>), dim3(grid), dim3(EG_LARGE * WAVE), 0, h->stream, P);
-            else hipLaunchKernelGGL((k_env_grp4<double>), dim3(grid), dim3(EG_LARGE * WAVE), 0, h->stream, P);
-        }
-    } else if (reg_ok) {                                                  // one instance per workgroup (the A/B reference of the grouped form)
-        if (P.obs_f32) hipLaunchKernelGGL((k_env_reg<float>), dim3(P.B), dim3(WAVE), 0, h->stream, P);
-        else hipLaunchKernelGGL((k_env_reg<double>), dim3(P.B), dim3(WAVE), 0, h->stream, P);
-    } else {
-        // LDS kernel: groups of G instances per workgroup where at least two instances' regions fit (MTFJSP_ENV_STEP_G overrides;
-        // 1 = the one-instance kernel k_env_step)
-        const EnvStepLds LL(P.J, P.M, P.T, P.obs_f32 != 0, P.pw_nleaf);
-        const int gmax = h->grp_lds_ok ? (int)((h->lds_max - 512) / LL.bytes) : 1;
-        int G = gmax >= 8 ? 8 : gmax >= 4 ? 4 : gmax >= 2 ? 2 : 1;
-        if (const char *gs = getenv("MTFJSP_ENV_STEP_G")) { G = atoi(gs); G = G < 1 ? 1 : G > ENV_LDS_GMAX ? ENV_LDS_GMAX : G; G = G > gmax ? (gmax < 1 ? 1 : gmax) : G; }
-        if (force && !strcmp(force, "lds1")) G = 1;
-        if (G > 1) {
-            const size_t lds_g = (size_t)G * LL.bytes;
-            const int grid = (P.B + G - 1) / G;
-            if (P.obs_f32) hipLaunchKernelGGL((k_env_step_grp<float>), dim3(grid), dim3(G * WAVE), lds_g, h->stream, P, G);
-            else hipLaunchKernelGGL((k_env_step_grp<double>), dim3(grid), dim3(G * WAVE), lds_g, h->stream, P, G);
-        } else {
-            const size_t lds_s = env_step_lds_bytes(P.J, P.M, P.T, P.obs_f32);
-            if (P.obs_f32) hipLaunchKernelGGL((k_env_step<float>), dim3(P.B), dim3(WAVE), lds_s, h->stream, P);
-            else hipLaunchKernelGGL((k_env_step<double>), dim3(P.B), dim3(WAVE), lds_s, h->stream, P);
-        }
-    }
+    // one row per EnvKernel, columns {f32, f64} (the code object holds the kernels in the order of this table); k_env_step_grp takes its G as well
+    static void (*const fn[ENV_K_COUNT][2])(EnvParams) = {
+        {k_env_grp16x2<float>, k_env_grp16x2<double>}, {k_env_grp4x2<float>, k_env_grp4x2<double>}, {k_env_grp16<float>, k_env_grp16<double>},
+        {k_env_grp4<float>, k_env_grp4<double>}, {k_env_reg<float>, k_env_reg<double>}, {nullptr, nullptr}, {k_env_step<float>, k_env_step<double>}};
+    static void (*const fn_grp[2])(EnvParams, int) = {k_env_step_grp<float>, k_env_step_grp<double>};
+    const EnvStepPlan pl = step_plan(h, false);
+    if (pl.kernel == ENV_K_STEP_GRP) hipLaunchKernelGGL(fn_grp[!P.obs_f32], dim3(pl.grid), dim3(pl.block), pl.lds, h->stream, P, pl.G);
+    else hipLaunchKernelGGL(fn[pl.kernel][!P.obs_f32], dim3(pl.grid), dim3(pl.block), pl.lds, h->stream, P);
     if (ev) HIPCHK(h, hipEventRecord(ev->second, h->stream));
 #ifdef MTFJSP_STAMP
-    static int printed = 0;
-    if (getenv("MTFJSP_STAMP_PRINT") && (printed++ % 9) == 4 && printed < 60) {
-        (void)hipStreamSynchronize(h->stream);
-        std::vector<unsigned long long> hst((size_t)P.B * 8);
-        (void)hipMemcpy(hst.data(), d_st, (size_t)P.B * 64, hipMemcpyDeviceToHost);
-        double m[8] = {0};
-        for (int w = 0; w < P.B; w++) for (int i = 0; i < 8; i++) m[i] += (double)hst[(size_t)w * 8 + i] / P.B;
-        if (P.T > 128) {                                                    // grouped LDS kernel: s_memrealtime stamps (100 MHz) per instance; slot 7 by the group's first
-            unsigned long long t0 = ~0ull; double r[8] = {0}; int n7 = 0;
-            for (int w = 0; w < P.B; w++) t0 = hst[(size_t)w * 8] < t0 ? hst[(size_t)w * 8] : t0;
-            for (int w = 0; w < P.B; w++) for (int i = 0; i < 8; i++) { if (i == 7 && hst[(size_t)w * 8 + 7] < t0) continue; r[i] += (double)(hst[(size_t)w * 8 + i] - t0) / 100.0; if (i == 7) n7++; }
-            for (int i = 0; i < 7; i++) r[i] /= P.B;
-            r[7] /= n7 ? n7 : 1;
-            printf("STAMP k_env_step_grp B=%d (us since the first wave's start): entry %.2f  loads in LDS %.2f  scheduled %.2f  estimates %.2f  terms+energy sum %.2f  observation+ELL %.2f  wave done %.2f  tail drained %.2f\n",
-                   P.B, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
-        } else if (hst[1] > 1000000000ull) {                                // grouped kernel: s_memrealtime stamps (100 MHz) of wave 0 per workgroup
-            const int ng = (P.B + 15) / 16; double r[8] = {0};
-            unsigned long long t0 = ~0ull;
-            for (int w = 0; w < ng; w++) t0 = hst[(size_t)w * 8] < t0 ? hst[(size_t)w * 8] : t0;
-            for (int w = 0; w < ng; w++) for (int i = 0; i < 8; i++) r[i] += (double)(hst[(size_t)w * 8 + i] - t0) / 100.0 / ng;
-#ifdef MTFJSP_STAMP_WAVES
-            if (P.B == 4096) {
-                double e[16] = {0}, f[16] = {0}, c[16] = {0}, dn[16] = {0};
-                for (int w = 0; w < ng; w++) for (int g = 0; g < 16; g++) {
-                    e[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4] - t0) / 100.0 / ng; f[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4 + 1] - t0) / 100.0 / ng;
-                    c[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4 + 2] - t0) / 100.0 / ng; dn[g] += (double)(hst[2048 + (size_t)w * 64 + g * 4 + 3] - t0) / 100.0 / ng;
-                }
-                for (int g = 0; g < 16; g++) printf("STAMPW wave %2d: entry %.2f first-hop %.2f costs %.2f done %.2f\n", g, e[g], f[g], c[g], dn[g]);
-                double t2[4] = {0};
-                for (int w = 0; w < ng; w++) for (int i = 0; i < 4; i++) t2[i] += (double)(hst[2048 + 256 * 64 + (size_t)w * 4 + i] - t0) / 100.0 / ng;
-                printf("STAMPT scalar-part wave: inputs read %.2f  idle sum done %.2f  rewards + scaling done %.2f  machine row done %.2f\n", t2[0], t2[1], t2[2], t2[3]);
-            }
-#endif
-            printf("STAMP k_env_grp16 B=%d (us since the first workgroup's start, wave 0): entry %.2f  first-hop data %.2f  decision %.2f  per-task costs done %.2f  wave done %.2f  barrier %.2f  scalar-part wave done %.2f  ELL/mask wave done %.2f\n",
-                   P.B, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
-        } else
-        printf("STAMP k_env B=%d: load %.0f  schedule %.0f  estimate+terms %.0f  lane0-costs %.0f  scaler+info %.0f  observation %.0f  mask %.0f+writeback-issue  drain %.0f  (cycles/wave)\n",
-               P.B, m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
-    }
+    stamp_report(h, P, pl);
 #endif
     HIPCHK(h, hipGetLastError());
     return MTFJSP_OK;
+}
+extern "C" int mtfjsp_step(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx) { return step_impl(h, task_idx, mach_idx, nullptr, nullptr); }
+extern "C" int mtfjsp_step_record(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4_out, float *done_out)
+{
+    if (!r4_out || !done_out) return MTFJSP_ERR_ARG;
+    return step_impl(h, task_idx, mach_idx, r4_out, done_out);
 }
 extern "C" int mtfjsp_step_host(mtfjsp_handle_t h, const int32_t *task_host, const int32_t *mach_host)
 {

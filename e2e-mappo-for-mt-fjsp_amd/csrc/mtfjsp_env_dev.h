@@ -4,10 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/mtfjsp.h"
+#include "mtfjsp_env_select.h"     // WAVE, SCAL_N, the group sizes and the launch selection
 
-#define WAVE 64
-#define SCAL_N 28          // doubles of per-instance scalar state
-// scalar slots
+// scalar slots (SCAL_N doubles per instance)
 #define S_MK_PREV 0
 #define S_E1_PREV 1
 #define S_TR_PREV 2

@@ -14,16 +14,10 @@
 //     energy sum, pt:54-124 per channel), so the results are bit-identical to k_env_reg.
 // Nothing in the per-task part waits for the scalar part.
 #pragma once
-// Instances (= waves) per workgroup; the scalar part uses 4 lanes per instance.  Two builds (measured, tools/env_variants.py):
-// 16 instances and 4 waves per SIMD (no spills) while all waves of the batch are resident at once (<= 8192 instances: 14.4 us at
-// 4096 against 16.1 us for k_env_reg); 4 instances and 8 waves per SIMD for chip-filling batches, where occupancy and short
-// barrier waits matter more than the amortisation (262 144 instances: 335 us = 0.78 of the copy rate against 442 us = 0.59).
+// Instances (= waves) per workgroup: EG_SMALL, EG_LARGE and the batch at which the launch changes over (mtfjsp_env_select.h).
 #ifndef EG_ABL
 #define EG_ABL 0           // timing ablations of the diagnostic builds (tools/ablate_env.sh): wrong results, never in the product
 #endif
-#define EG_SMALL 16
-#define EG_LARGE 4
-#define EG_SMALL_MAX_B 8192
 enum { U_R0 = 0, U_NEWTR, U_D, U_PK, U_FTTAIL, U_STK, U_TAIL = 8 };     // s_un slots (8..15: ragged tail of the pairwise energy sum)
 enum { I_VALID = 0, I_STATUS, I_NSCHED, I_M, I_JA, I_A, I_NK, I_LASTM, I_MERGED, I_F4A };   // s_in slots (12 per instance)
 

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import capi
-from .batch_env import DeviceBatchEnv
+from .batch_env import DeviceBatchEnv, step_kernel_for
 from .instances import generate_instances, random_weights
 
 
@@ -135,18 +135,9 @@ class Rollout:
                 "observation, job mask); batched reset every T steps")
 
     def env_kernel_name(self):
-        """which step kernel mtfjsp_step dispatches to for this shape (csrc/mtfjsp_env.hip launch selection)"""
-        force = os.environ.get("MTFJSP_ENV_KERNEL", "")
-        lds = bool(os.environ.get("MTFJSP_ENV_LDS")) or force in ("lds", "lds1")
-        one = self.T <= 64 and self.M * self.M <= 64 and self.J <= 64 and not lds
-        two = (not one) and self.T <= 128 and self.M * self.M <= 128 and self.M <= 16 and self.J <= 64 and not lds and force != "reg1"
-        if two:
-            return "k_env_grp16x2" if (force == "grp16" or (force != "grp4" and self.B <= 4096)) else "k_env_grp4x2"
-        if not one:
-            return "k_env_step" if force == "lds1" else "k_env_step_grp"
-        if force == "reg1":
-            return "k_env_reg"
-        return "k_env_grp16" if (force == "grp16" or (force != "grp4" and self.B <= 8192)) else "k_env_grp4"
+        """which step kernel mtfjsp_step launches: the library's own selection, asked of the live handle — or, on a stand-in that only
+        carries J, M, B (the tests' walks of their case tables), of the shape with f64 observations and gfx950's LDS"""
+        return self.env.step_kernel_name() if hasattr(self, "env") else step_kernel_for(self.J, self.M, self.B)[0]
 
     def _refill_w3(self):
         self.w3_pool.copy_(torch.as_tensor(np.stack([random_weights(self.B, rng=self._w3_rng) for _ in range(self._w3_pool_n)])))

@@ -181,6 +181,14 @@ int mtfjsp_step_record(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t
 int32_t mtfjsp_step_params_bytes(void);
 int mtfjsp_step_params(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t *mach_idx, float *r4_out, float *done_out,
                        void *params_out, int32_t params_bytes);
+/* The step kernel the next mtfjsp_step on this handle launches ("k_env_grp16", ...: the launch selection itself, on the handle's shape,
+ * its device's LDS capacity and the diagnostic switches MTFJSP_ENV_KERNEL / MTFJSP_ENV_LDS / MTFJSP_ENV_STEP_G as they are NOW — they are
+ * read on every call).  mtfjsp_step_kernel_name_for: the same for a shape without a handle, where a workgroup may use lds_max bytes of
+ * LDS (gfx950: 160 KiB); no device is touched.  Optional outputs: instances per workgroup, bytes of one instance's LDS region (0: register
+ * kernels), whether a switch is set.  NULL for a shape mtfjsp_create rejects. */
+const char *mtfjsp_step_kernel_name(mtfjsp_handle_t h);
+const char *mtfjsp_step_kernel_name_for(int32_t n_job, int32_t n_machine, int32_t batch, int32_t obs_f32, int64_t lds_max,
+                                        int32_t *group_out, int64_t *lds_bytes_out, int32_t *overridden_out);
 /* host variant: returns MTFJSP_ERR_ACTION if any status word carries MTFJSP_ST_INVALID — AFTER the launch: the valid instances of
  * the batch have been stepped, the rejected ones hold the outputs above; mtfjsp_last_error names the first rejected instance */
 int mtfjsp_step_host(mtfjsp_handle_t h, const int32_t *task_idx_host, const int32_t *mach_idx_host);

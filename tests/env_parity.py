@@ -19,8 +19,8 @@ _SELECTION_VARS = ("MTFJSP_ENV_KERNEL", "MTFJSP_ENV_LDS", "MTFJSP_ENV_STEP_G")
 
 
 def dispatch_kernel(J, M, B, force=None):
-    """the step kernel mtfjsp_step launches for this shape: Rollout.env_kernel_name (rollout.py restates the launch selection of
-    csrc/mtfjsp_env.hip) on a stand-in carrying T, M, J, B, with MTFJSP_ENV_KERNEL = force (None: the default dispatch)"""
+    """the step kernel mtfjsp_step launches for this shape: Rollout.env_kernel_name (the library's own launch selection, no handle
+    needed) on a stand-in carrying T, M, J, B, with MTFJSP_ENV_KERNEL = force (None: the default dispatch)"""
     import mtfjsp_amd  # noqa: F401
     rollout = import_module("e2e-mappo-for-mt-fjsp_amd.rollout")
     saved = {k: os.environ.pop(k, None) for k in _SELECTION_VARS}
@@ -73,8 +73,6 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
             monkeypatch.setenv("MTFJSP_ENV_KERNEL", force)
     else:
         assert not force and not any(os.environ.get(k) for k in _SELECTION_VARS), "forcing a kernel needs monkeypatch"
-    if expect_kernel is not None:
-        assert dispatch_kernel(J, M, B, force) == expect_kernel, (dispatch_kernel(J, M, B, force), expect_kernel)
     T = J * M
     odt = np.float32 if obs_dtype == "f32" else np.float64
     case = f"J{J}M{M}E{E} B={B} {obs_dtype} force={force} left_shift={left_shift}"
@@ -86,6 +84,8 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
     feas = t >= 0
     rs = np.random.RandomState(seed)
     env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=left_shift, obs_dtype=obs_dtype)
+    if expect_kernel is not None:                    # the live handle's own answer: this device's LDS, the switches as set above
+        assert env.step_kernel_name() == expect_kernel, (env.step_kernel_name(), expect_kernel)
     env.load_instances(t, p, tt, edge=edge)
     env.scaler_init()
     orc = OracleBatch(t, p, tt, edge, left_shift=left_shift)

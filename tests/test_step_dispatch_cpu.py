@@ -1,0 +1,113 @@
+"""CPU: the library's one statement of the step-kernel selection (csrc/mtfjsp_env_select.h, asked through the handle-free entry
+mtfjsp_step_kernel_name_for) against the Python rule it replaced, at the LDS capacity boundary, under MTFJSP_ENV_STEP_G, and in the
+two fields mtfjsp_step_params consults for the fused tail.  No handle, no device."""
+import os
+from importlib import import_module
+from types import SimpleNamespace
+
+import pytest
+
+import mtfjsp_amd  # noqa: F401
+from env_parity import _SELECTION_VARS
+
+batch_env = import_module("e2e-mappo-for-mt-fjsp_amd.batch_env")
+plan = batch_env.step_kernel_for
+LDS = 160 * 1024
+LDS_KERNELS = ("k_env_step_grp", "k_env_step")
+
+
+def old_rule(self):
+    """rollout.Rollout.env_kernel_name as it stood before the library answered: the model.  It knows nothing of LDS capacity"""
+    force = os.environ.get("MTFJSP_ENV_KERNEL", "")
+    lds = bool(os.environ.get("MTFJSP_ENV_LDS")) or force in ("lds", "lds1")
+    one = self.T <= 64 and self.M * self.M <= 64 and self.J <= 64 and not lds
+    two = (not one) and self.T <= 128 and self.M * self.M <= 128 and self.M <= 16 and self.J <= 64 and not lds and force != "reg1"
+    if two:
+        return "k_env_grp16x2" if (force == "grp16" or (force != "grp4" and self.B <= 4096)) else "k_env_grp4x2"
+    if not one:
+        return "k_env_step" if force == "lds1" else "k_env_step_grp"
+    if force == "reg1":
+        return "k_env_reg"
+    return "k_env_grp16" if (force == "grp16" or (force != "grp4" and self.B <= 8192)) else "k_env_grp4"
+
+
+@pytest.fixture
+def switches(monkeypatch):
+    for k in _SELECTION_VARS:
+        monkeypatch.delenv(k, raising=False)
+    return monkeypatch
+
+
+SHAPES = [(J, M) for J in range(1, 41) for M in list(range(2, 25)) + [32, 64] if J * M <= 32767]
+BATCHES = (1, 15, 16, 17, 4096, 4097, 8192, 8193)
+
+
+def test_the_library_rule_equals_the_old_python_rule_wherever_two_regions_fit(switches):
+    seen, refused = set(), set()
+    for force in (None, "grp16", "grp4", "reg1", "lds", "lds1"):
+        for env_lds in (None, "1"):
+            for k, v in (("MTFJSP_ENV_KERNEL", force), ("MTFJSP_ENV_LDS", env_lds)):
+                switches.setenv(k, v) if v else switches.delenv(k, raising=False)
+            for J, M in SHAPES:
+                for B in BATCHES:
+                    name, G, nbytes, overridden = plan(J, M, B, False, LDS)
+                    want = old_rule(SimpleNamespace(J=J, M=M, T=J * M, B=B))
+                    case = (J, M, B, force, env_lds, name, G, nbytes)
+                    assert overridden == bool(force or env_lds), case
+                    assert (nbytes > 0) == (name in LDS_KERNELS), case
+                    if G >= 2 or name not in LDS_KERNELS or force == "lds1":
+                        assert name == want, (case, want)
+                    else:                          # the one thing the old rule did not know: a second region does not fit
+                        assert 2 * nbytes + 512 > LDS and want == "k_env_step_grp" and (name, G) == ("k_env_step", 1), (case, want)
+                        refused.add((J, M))
+                    seen.add(name)
+    assert len(SHAPES) == 40 * 25 and seen == set(LDS_KERNELS) | {"k_env_grp16", "k_env_grp4", "k_env_grp16x2", "k_env_grp4x2", "k_env_reg"}
+    assert refused and all(J * M > 1000 for J, M in refused) and len(refused) < len(SHAPES) // 20, sorted(refused)
+
+
+def test_lds_boundary_is_step_impls_quotient(switches):
+    """gmax = (lds_max - 512) / bytes of one region; G = 8, 4, 2 or 1 instance(s) per workgroup, and 1 is k_env_step"""
+    J = M = 20
+    nbytes = plan(J, M, 2048, False, LDS)[2]
+    assert 8 * 1024 < nbytes < 32 * 1024
+    for lds_max, want in [(2 * nbytes + 511, ("k_env_step", 1)), (2 * nbytes + 512, ("k_env_step_grp", 2)), (4 * nbytes + 511, ("k_env_step_grp", 2)),
+                          (4 * nbytes + 512, ("k_env_step_grp", 4)), (8 * nbytes + 511, ("k_env_step_grp", 4)), (8 * nbytes + 512, ("k_env_step_grp", 8)),
+                          (64 * nbytes, ("k_env_step_grp", 8))]:
+        got = plan(J, M, 2048, False, lds_max)
+        assert got[:2] == want and got[2] == nbytes and not got[3], (lds_max, got, want)
+
+
+@pytest.mark.parametrize("regions", [8, 5])
+def test_step_g_is_clamped_to_1_the_kernels_maximum_and_what_fits(switches, regions):
+    J = M = 20
+    nbytes = plan(J, M, 64, True, LDS)[2]
+    lds_max = regions * nbytes + 512                # gmax == regions
+    for value, want in [("0", ("k_env_step", 1)), ("1", ("k_env_step", 1)), ("3", ("k_env_step_grp", 3)), ("99", ("k_env_step_grp", min(8, regions)))]:
+        switches.setenv("MTFJSP_ENV_STEP_G", value)
+        assert plan(J, M, 64, True, lds_max) == want + (nbytes, True), (value, regions)
+    switches.setenv("MTFJSP_ENV_KERNEL", "lds1")     # lds1 wins over MTFJSP_ENV_STEP_G
+    assert plan(J, M, 64, True, lds_max)[:2] == ("k_env_step", 1)
+
+
+def fused_tail(J, M, B):
+    """the plan fields mtfjsp_step_params consults (it also wants kernel-time recording off)"""
+    name, _, _, overridden = plan(J, M, B, True, LDS)
+    return name == "k_env_grp16" and not overridden
+
+
+def test_fused_tail_truth_table(switches):
+    assert fused_tail(6, 6, 8192) and fused_tail(8, 8, 19)
+    assert not fused_tail(6, 6, 8193)
+    assert not fused_tail(7, 9, 19)                  # M * M > 64
+    for k, v in (("MTFJSP_ENV_KERNEL", "grp16"), ("MTFJSP_ENV_LDS", "1"), ("MTFJSP_ENV_STEP_G", "2")):
+        switches.setenv(k, v)
+        assert not fused_tail(6, 6, 8192) and not fused_tail(8, 8, 19), k
+        switches.delenv(k)
+    assert fused_tail(6, 6, 8192)
+
+
+def test_shapes_no_handle_takes_have_no_name():
+    L = import_module("e2e-mappo-for-mt-fjsp_amd.capi").lib()
+    for J, M, B in [(0, 6, 1), (6, 1, 1), (6, 65, 1), (6, 6, 0), (600, 64, 1)]:
+        assert L.mtfjsp_step_kernel_name_for(J, M, B, 0, LDS, None, None, None) is None
+    assert L.mtfjsp_step_kernel_name_for(6, 6, 1, 0, LDS, None, None, None) == b"k_env_grp16"
