@@ -228,3 +228,176 @@ def lookahead_baselines(t, p, tt, edge, args, rules=LOOKAHEAD_RULES, device=0, o
         env.close()
     out[PLANS] = plans
     return out
+
+
+# ---- beam search (csrc/mtfjsp_beam.hip): the look-ahead's children, the W best of them kept per instance instead of one.  (name,
+# column of the raw rewards whose running sum is the score: as LOOKAHEAD_RULES)
+BEAM_RULES = [("BS_IT", 2), ("BS_TT", 4), ("BS_MK", 1), ("BS_EC", 3), ("BS_R", 0)]
+BEAM_MAX_WIDTH, BEAM_MAX_CANDIDATES = 64, 8192
+BEAM_SCRATCH_BATCH = 262144          # the chip-filling batch: what one pass of beam_baselines keeps in flight
+
+
+class BeamSearch:
+    """Beam search of width `width` from the states `src` (a reset DeviceBatchEnv of N instances) holds now: a beam handle of N*W
+    instances (slot w of instance n = n*W + w) and a scratch handle of N*W*T (child (j, m) of every slot).  Constants and state are
+    forked from `src` once, here (and again by `restart`); the scores start as [0, -inf, ...] per instance: one live slot.
+    `advance(column)` is one decision — expand, one ordinary step of the scratch handle, the children's signatures (with `dedupe`:
+    children that are the same partial schedule reached in another order are merged into the best of them), the selection of the
+    W best children by score + raw[column] into row s of the history, and the fork of the winners into the beam — six launches,
+    no read-back.  `run` drives whole episodes and reads the best plan out through the back-pointers."""
+
+    def __init__(self, src, width, dedupe=True):
+        W = int(width)
+        if not 1 <= W <= BEAM_MAX_WIDTH or W * src.T > BEAM_MAX_CANDIDATES:
+            raise ValueError(f"beam width must be 1..{BEAM_MAX_WIDTH} with width * n_job * n_machine <= {BEAM_MAX_CANDIDATES}")
+        self.src, self.W, self.dedupe = src, W, bool(dedupe)
+        N, T, dev = src.B, src.T, src.device
+        self.N, self.T = N, T
+        kw = dict(left_shift=src.left_shift, obs_dtype="f32" if src.obs_f32 else "f64", device=dev.index or 0, gamma=src.gamma,
+                  w_cfg=src.w_cfg, scaling_divisor=src.scaling_divisor)
+        self.beam = DeviceBatchEnv(src.J, src.M, src.E, N * W, **kw)
+        self.scratch = DeviceBatchEnv(src.J, src.M, src.E, N * W * T, **kw)
+        self._beam_index = torch.arange(N * W, dtype=torch.int32, device=dev) // W
+        self.scratch.fork_from(src, torch.arange(N * W * T, dtype=torch.int32, device=dev) // (W * T), instance=True, state=False, obs=False)
+        self.task_c = torch.empty(N * W * T, dtype=torch.int32, device=dev)
+        self.mach_c = torch.empty(N * W * T, dtype=torch.int32, device=dev)
+        self.sig = torch.zeros(N * W * T, dtype=torch.int64, device=dev)        # (the 64-bit signatures, as int64 words)
+        self.score = torch.empty(N * W, dtype=torch.float64, device=dev)
+        self._score_next = torch.empty_like(self.score)
+        self._alloc_history(T)
+        self.restart()
+
+    def _alloc_history(self, cap):
+        dev, NW = self.src.device, self.N * self.W
+        old = getattr(self, "hist", None)
+        # rows of (parent, from_slot, task, mach): row s = what decision s's selection wrote
+        self.hist = {k: torch.full((cap, NW), -1, dtype=torch.int32, device=dev) for k in ("parent", "from_slot", "task", "mach")}
+        if old is not None:
+            for k, v in old.items():
+                self.hist[k][:v.shape[0]].copy_(v)
+
+    def restart(self):
+        """take `src`'s present state again: every slot a copy of its instance, one live slot, no history"""
+        self.beam.fork_from(self.src, self._beam_index, instance=True, state=True, obs=False)
+        self.score.fill_(float("-inf"))
+        self.score.view(self.N, self.W)[:, 0] = 0.0
+        self.s = 0
+
+    def advance(self, column):
+        """one decision of every instance; -> the step's history row index.  `self.score` [N*W] then holds the new scores."""
+        L, s = self.src.L, self.s
+        if s >= self.hist["task"].shape[0]:
+            self._alloc_history(2 * s)
+        capi.check(L.mtfjsp_lookahead_expand(self.scratch.h, self.beam.h, self.task_c.data_ptr(), self.mach_c.data_ptr()), self.scratch.h)
+        self.scratch.step(self.task_c, self.mach_c)
+        if self.dedupe:
+            self.scratch.state_signature(self.sig)
+        h = self.hist
+        capi.check(L.mtfjsp_beam_select(self.scratch.h, self.beam.h, self.W, int(column), self.score.data_ptr(),
+                                        C.c_void_p(self.sig.data_ptr() if self.dedupe else None), h["parent"][s].data_ptr(),
+                                        h["from_slot"][s].data_ptr(), h["task"][s].data_ptr(), h["mach"][s].data_ptr(),
+                                        self._score_next.data_ptr()), self.scratch.h)
+        self.beam.fork_from(self.scratch, h["parent"][s], instance=False, state=True, obs=False)
+        self.score, self._score_next = self._score_next, self.score
+        self.s = s + 1
+        return s
+
+    def plans(self, start_slot=None):
+        """-> (task[N,s], mach[N,s]) int32 device tensors: the decisions that led to slot start_slot[n] (host sequence or int32
+        device tensor [N]; None: slot 0, the best) of the present beam, -1 where the slot is empty or the instance had finished"""
+        if self.s < 1:
+            raise ValueError("no decision has been taken yet")
+        dev = self.src.device
+        if start_slot is not None and not torch.is_tensor(start_slot):
+            start_slot = torch.as_tensor(np.ascontiguousarray(start_slot, np.int32), device=dev)
+        if start_slot is not None:
+            assert start_slot.is_cuda and start_slot.dtype == torch.int32 and start_slot.is_contiguous() and start_slot.shape == (self.N,)
+        task = torch.empty(self.N, self.s, dtype=torch.int32, device=dev)
+        mach = torch.empty(self.N, self.s, dtype=torch.int32, device=dev)
+        h = self.hist
+        capi.check(self.src.L.mtfjsp_beam_backtrack(self.beam.h, self.W, self.s, h["from_slot"].data_ptr(), h["task"].data_ptr(), h["mach"].data_ptr(),
+                                                    C.c_void_p(start_slot.data_ptr() if start_slot is not None else None),
+                                                    task.data_ptr(), mach.data_ptr()), self.beam.h)
+        return task, mach
+
+    def run(self, column, steps=None):
+        """`steps` (default T: the whole episode) decisions -> (task[N,steps], mach[N,steps], score[N,W]): the best slot's plan and
+        every slot's score (the running sum of raw[column]; -inf: empty)"""
+        for _ in range(self.T if steps is None else int(steps)):
+            self.advance(column)
+        task, mach = self.plans()
+        return task, mach, self.score.view(self.N, self.W)
+
+    def close(self):
+        self.scratch.close()
+        self.beam.close()
+
+
+def beam_baselines(t, p, tt, edge, args, rules=BEAM_RULES, width=8, dedupe=True, device=0, obs_dtype="f32", left_shift=False, chunk=None):
+    """Beam search `rules` ((name, column) each) of width `width` on the N instances t, p [N,T,M], tt [N,M,M], edge [N,E,M/E]; args
+    as for `pdr_baselines`.  Per rule: a `BeamSearch` over the whole episode (score = the running sum of raw[column]; ties to the
+    lowest (slot, job, machine); with `dedupe`, children that are one partial schedule are merged), then the best plan is replayed on the plain handle step by
+    step, as `lookahead_baselines` steps its choices.  chunk: source instances per pass (None: the largest with
+    chunk * width * T <= BEAM_SCRATCH_BATCH); the results do not depend on it.
+    -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, and under PLANS {name: (task[N,T], mach[N,T])}."""
+    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
+    T, W = J * M, int(width)
+    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
+    names = [r[0] for r in rules]
+    if len(set(names)) != len(rules) or PLANS in names:
+        raise ValueError("rule names must be distinct")
+    if any(int(r[1]) not in range(5) for r in rules):
+        raise ValueError("a beam rule's column must be 0..4")
+    t, p, tt, edge = np.asarray(t, np.float64), np.asarray(p, np.float64), np.asarray(tt, np.float64), np.asarray(edge)
+    N = t.shape[0]
+    chunk = max(1, BEAM_SCRATCH_BATCH // (W * T)) if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    scal = args.get("reward_scaling", {}) or {}
+    parts = {name: [] for name in names}
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        n = hi - lo
+        env = DeviceBatchEnv(J, M, E, n, left_shift=left_shift, obs_dtype=obs_dtype, device=device, w_cfg=w,
+                             scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+        bs = None
+        try:
+            env.load_instances(t[lo:hi], p[lo:hi], tt[lo:hi], edge=edge[lo:hi])
+            dev = env.device
+            w3 = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n, 1)
+            for name, column in rules:
+                env.scaler_init()                                       # the scaled components are produced but not used here
+                env.reset(w3)                                           # pdrs:675 reset(Random_weight_type="eval")
+                if bs is None:
+                    bs = BeamSearch(env, W, dedupe)
+                else:
+                    bs.restart()
+                task, mach, _ = bs.run(int(column), T)
+                ts, ms = task.t().contiguous(), mach.t().contiguous()   # [T,n]: row s = the actions of step s
+                cum = torch.zeros(n, 5, dtype=torch.float64, device=dev)
+                bad = torch.zeros(n, dtype=torch.int32, device=dev)
+                for s in range(T):
+                    env.step(ts[s], ms[s])
+                    cum += env.raw                                      # reward, r_mk, r_idle, r_pt, r_tt, in step order
+                    bad |= env.status
+                torch.cuda.synchronize(dev)
+                n_bad = int((bad & (capi.ST_INVALID | capi.ST_INFEASIBLE)).ne(0).sum().item())
+                if n_bad:
+                    raise RuntimeError(f"beam-search rollout: {n_bad} instance(s) met an invalid action or an infeasible machine")
+                if not bool(env.info[:, 1].all().item()):
+                    raise RuntimeError("beam-search rollout: an episode did not finish after T steps")
+                parts[name].append((cum.cpu().numpy(), env.read_state(capi.STATE_PREV_COSTS), task.cpu().numpy(), mach.cpu().numpy()))
+        finally:
+            if bs is not None:
+                bs.close()
+            env.close()
+    out, plans = {}, {}
+    for name in names:
+        c, prev, task, mach = (np.concatenate([x[k] for x in parts[name]]) for k in range(4))
+        cost = {"opr_Gt": c[:, 0], "opr_mk": c[:, 1], "opr_idleT": c[:, 2], "opr_pt": c[:, 3], "opr_transT": c[:, 4]}
+        final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
+        obj = w[0] * final4[:, 0] + w[1] * (final4[:, 1] + final4[:, 3]) + w[2] * final4[:, 2]
+        out[name] = (cost, final4, obj)
+        plans[name] = (task, mach)
+    out[PLANS] = plans
+    return out

@@ -131,6 +131,15 @@ class DeviceBatchEnv:
         self._fork_index = index                                        # alive until the launch has run
         capi.check(self.L.mtfjsp_fork(self.h, src.h, index.data_ptr(), flags), self.h)
 
+    def state_signature(self, out=None):
+        """64-bit order-independent signature of every instance's partial schedule (mtfjsp_state_signature: one launch, nothing read
+        back) -> int64 device tensor [B] holding the unsigned words (`.cpu().numpy().view(np.uint64)`); 0 for a fresh instance"""
+        if out is None:
+            out = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (self.B,)
+        capi.check(self.L.mtfjsp_state_signature(self.h, out.data_ptr()), self.h)
+        return out
+
     def scaler_init(self):
         capi.check(self.L.mtfjsp_scaler_init(self.h), self.h)
 

@@ -79,6 +79,9 @@ PROTOTYPES = {
     "mtfjsp_fork": (_I, [_VP, _VP, _VP, C.c_int32]),
     "mtfjsp_lookahead_expand": (_I, [_VP, _VP, _VP, _VP]),
     "mtfjsp_lookahead_select": (_I, [_VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
+    "mtfjsp_state_signature": (_I, [_VP, _VP]),
+    "mtfjsp_beam_select": (_I, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mtfjsp_beam_backtrack": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_export_dense_adj": (_I, [_VP, _VP]),
     "mtfjsp_export_dense_adj_host": (_I, [_VP, _VP]),
     "mtfjsp_valid_action_mask": (_I, [_VP, _VP]),

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""The greedy policy, the 12 priority dispatch rules of the reference's test_all.py and the one-step look-ahead rules on the SAME instances, one table
-(paper Tables V / VI).  The instances are generated on the device; the rules are planned there by k_pdr_plan and replayed by the
-step kernel with left shift off; the look-ahead rules (baselines.lookahead_baselines) try every (job, machine) on a forked copy per step.
+"""The greedy policy, the 12 priority dispatch rules of the reference's test_all.py, the one-step look-ahead rules and beam search on the SAME
+instances, one table (paper Tables V / VI).  The instances are generated on the device; the rules are planned there by k_pdr_plan and replayed by the
+step kernel with left shift off; the look-ahead rules (baselines.lookahead_baselines) try every (job, machine) on a forked copy per step; beam search
+(baselines.beam_baselines, W = 1, 4, 16) keeps the W best partial schedules per instance instead of one.
 
     python examples/pdr_baselines.py [--instances 1024] [--size 6 6 2]
 """
@@ -38,15 +39,19 @@ t, p, tt, edge = env.read_instances()
 t0 = time.perf_counter()
 look = baselines.lookahead_baselines(t, p, tt, edge, args)                          # 5 rules, N*T forked copies per decision
 t_look = time.perf_counter() - t0
+t0 = time.perf_counter()
+beams = {w: baselines.beam_baselines(t, p, tt, edge, args, width=w) for w in (1, 4, 16)}     # 5 rules each, N*W*T copies per decision
+t_beam = time.perf_counter() - t0
 weights = encoder.random_init_weights(seed=0)            # or (torch.load(job_actor.pth), torch.load(machine_actor.pth))
 t0 = time.perf_counter()
 _, final4, obj = evaluate.validate_cost_batched(weights, t, p, tt, edge, args)
 t_policy = time.perf_counter() - t0
 
 print(f"{N} instances J{J}M{M}E{E}: 12 rules in {t_rules * 1e3:.1f} ms, {len(baselines.LOOKAHEAD_RULES)} look-ahead rules in {t_look * 1e3:.1f} ms, "
-      f"greedy policy in {t_policy * 1e3:.1f} ms")
+      f"beam search at W = 1, 4, 16 in {t_beam * 1e3:.1f} ms, greedy policy in {t_policy * 1e3:.1f} ms")
 print(f"{'method':<16}{'objective':>12}{'makespan':>12}{'energy':>12}{'transport':>12}{'idle':>12}")
 rows = [("policy (greedy)", final4, obj)] + [(name, rules[name][1], rules[name][2]) for name, _, _ in baselines.RULES]
 rows += [(name, look[name][1], look[name][2]) for name, _ in baselines.LOOKAHEAD_RULES]
+rows += [(f"{name} W={w}", beams[w][name][1], beams[w][name][2]) for w in (1, 4, 16) for name, _ in baselines.BEAM_RULES]
 for name, f4, ob in rows:
     print(f"{name:<16}{ob.mean():>12.2f}{f4[:, 0].mean():>12.2f}{f4[:, 1].mean():>12.2f}{f4[:, 2].mean():>12.2f}{f4[:, 3].mean():>12.2f}")

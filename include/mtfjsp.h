@@ -252,6 +252,53 @@ int mtfjsp_lookahead_expand(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_
 int mtfjsp_lookahead_select(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_t column, int32_t *task_out, int32_t *mach_out,
                             int32_t *job_out, double *best_out);
 
+/* ------------------------------------------------------------------ beam search on the fork */
+/* Beam search over (job, machine) decisions: keep the W best partial schedules ("slots") of each of N source instances, expand
+ * each into its T children, keep the best W again.  beam holds N*W instances (slot w of source n = instance n*W + w), scratch
+ * N*W*T with its constants forked once (index i -> i / (W*T) of the source set).  One decision is mtfjsp_lookahead_expand(scratch,
+ * beam, ...), mtfjsp_step(scratch, ...), optionally mtfjsp_state_signature(scratch, sig), mtfjsp_beam_select and
+ * mtfjsp_fork(beam, scratch, parent_out, MTFJSP_FORK_STATE); after the last one mtfjsp_beam_backtrack reads the plans out.
+ * The reference has no search (its only look-ahead is the greedy pdrs:465-540).
+ *
+ * mtfjsp_state_signature: sig_out [batch] (device, u64) = a 64-bit signature of every instance's PARTIAL SCHEDULE that does not
+ * depend on the order in which its decisions were taken: the sum mod 2^64 over the scheduled tasks k of
+ *     mix(mix(bits64(start_k)) + ((uint64)k << 32 | (uint64)machine_k << 16 | (uint64)position_k in its machine's route)),
+ * mix = the splitmix64 finaliser (z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31);
+ * an unscheduled task contributes 0, so a freshly reset instance has signature 0.  Equal partial schedules (the same tasks on the
+ * same machines at the same positions and start times) have equal signatures; distinct ones collide with probability about 2^-64.
+ * With left shift off any two decisions on different machines commute, so every order in which one partial schedule can be reached gives one signature.
+ * NOT covered, deliberately: the words that remember the previous step (the merged-edge node and its transport time), the 17
+ * RewardScaling words and the previous-step costs — two states that agree in the schedule but differ there count as equal.
+ * Merging by signature is therefore a search heuristic: a false merge costs one beam slot and never corrupts a state.
+ * One launch on h's stream (one wavefront per instance, lanes over tasks), nothing read back.  MTFJSP_ERR_STATE: h never reset.
+ *
+ * mtfjsp_beam_select: candidate c = w*T + r of source n (r = j*n_machine + m: slot w tries job j's next task on machine m) is
+ * scratch instance g = (n*W + w)*T + r.  It is eligible iff score_in[n*W + w] != -inf (-inf marks an empty slot) and status[g]
+ * carries neither MTFJSP_ST_INVALID nor MTFJSP_ST_INFEASIBLE; its value is score_in[n*W + w] + raw[g][column] — one binary64
+ * addition, so a slot's score is the running sum of its one-step rewards in step order; a NaN value is never selected.  Ranks
+ * k = 0..W-1 in turn take the eligible candidate of the largest value, the lowest c among equals, and remove it; where sig
+ * (device u64 [N*W*T], what mtfjsp_state_signature(scratch) wrote; may be NULL) is given, every candidate with the pick's
+ * signature is removed with it (duplicates are merged into their best, lowest-c representative).  Outputs, device [N*W], at
+ * n*W + k: parent_out = g (the index of the following mtfjsp_fork), from_slot_out = w, task_out / mach_out = the child's action
+ * (formed from beam's job records as mtfjsp_lookahead_select forms it), score_out = the value.  A rank left without a candidate
+ * writes -1, -1, -1, -1, -inf: the fork leaves that slot untouched and the score marks it empty.  An instance without any
+ * candidate to pick (finished) keeps its beam: parent -1, from_slot = k, task = mach = -1, score_out = score_in.
+ * 1 <= W <= 64, beam.batch % W == 0, W*T <= 8192 (the candidates live in one workgroup's LDS), column 0..4, scratch.batch ==
+ * beam.batch*T, score_out != score_in (every rank reads all parent scores): otherwise MTFJSP_ERR_ARG and nothing is written.
+ * One launch, one workgroup per source instance, on beam's stream; it reads scratch's bound status and raw: ordering between the
+ * handles' streams is the caller's duty, as for the look-ahead.
+ *
+ * mtfjsp_beam_backtrack: h = the beam handle (N = batch / W).  hist_from_slot, hist_task, hist_mach: device int32 [S, N*W], row s
+ * = what decision s's mtfjsp_beam_select wrote (hand it pointers into these arrays).  start_slot: device int32 [N], or NULL for
+ * slot 0 — the best, since ranks come out in order.  task_plan, mach_plan: device int32 [N, S]; with k = start_slot[n], for
+ * s = S-1 .. 0: plan[n][s] = hist[s][n*W + k], k = hist_from_slot[s][n*W + k].  A slot outside [0, W) met on the way (an empty
+ * rank) writes -1 for that and every earlier step.  One launch, one thread per source instance, on h's stream. */
+int mtfjsp_state_signature(mtfjsp_handle_t h, uint64_t *sig_out);
+int mtfjsp_beam_select(mtfjsp_handle_t scratch, mtfjsp_handle_t beam, int32_t W, int32_t column, const double *score_in, const uint64_t *sig,
+                       int32_t *parent_out, int32_t *from_slot_out, int32_t *task_out, int32_t *mach_out, double *score_out);
+int mtfjsp_beam_backtrack(mtfjsp_handle_t h, int32_t W, int32_t S, const int32_t *hist_from_slot, const int32_t *hist_task,
+                          const int32_t *hist_mach, const int32_t *start_slot, int32_t *task_plan, int32_t *mach_plan);
+
 /* ------------------------------------------------------------------ dispatch-rule baselines */
 /* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
  * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"
