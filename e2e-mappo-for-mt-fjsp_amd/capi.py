@@ -117,6 +117,9 @@ PROTOTYPES = {
     "mtfjsp_hostgen_transport": (_I, [_VP, C.POINTER(C.c_int32), C.c_int64, _I, _VP, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int64, _VP]),
     "mtfjsp_encoder_check": (_I, [_VP, C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_resident_failures": (_I, [_VP, C.POINTER(C.c_int64)]),
+    "mtfjsp_gin_res_kernel_name_for": (C.c_char_p, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mtfjsp_encoder_gin_res_kernel_name": (C.c_char_p, [_VP]),
+    "mtfjsp_encoder_peek_gin_res_host": (_I, [_VP, _VP, C.c_int64, _VP, _VP]),
     "mtfjsp_encoder_range_fallbacks": (_I, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_peek_nodes_host": (_I, [_VP, _VP, C.c_int64]),
     "mtfjsp_encoder_timing_begin": (_I, [_VP]),
@@ -157,3 +160,13 @@ def check(rc, handle=None, enc=False):
         L = lib()
         msg = (L.mtfjsp_encoder_last_error(handle) if enc else L.mtfjsp_last_error(handle)) or b""
         raise MtfjspError(rc, msg.decode())
+
+
+def gin_res_kernel_for(batch, n_job, n_machine, num_cu=256, candidates=None, node_output=False):
+    """(kernel name or None, instances per workgroup, workgroups): which instantiation of the single-launch GIN kernel serves a forward of this
+    shape — the library's own rule (csrc/mtfjsp_gin_res_select.h), no GPU needed.  candidates: per instance (default n_job, the job actor; 0: the
+    global critic).  MTFJSP_GIN_RES_GENERIC=1 in the environment forces the run-time kernel."""
+    ipc, grid = C.c_int32(0), C.c_int32(0)
+    name = lib().mtfjsp_gin_res_kernel_name_for(batch, n_job * n_machine, n_job, n_job if candidates is None else candidates, num_cu,
+                                                int(bool(node_output)), C.byref(ipc), C.byref(grid))
+    return (name.decode() if name else None), ipc.value, grid.value

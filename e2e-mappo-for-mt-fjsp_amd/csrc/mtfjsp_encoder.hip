@@ -2906,6 +2906,7 @@ struct mtfjsp_encoder {
                        (getenv("MTFJSP_HEADS_F32MFMA") ? 4 : 0) | (getenv("MTFJSP_GIN0_VALU") ? 8 : 0);
     // resident GIN kernel (mtfjsp_gin_resident.h): eligibility decided at create time, then verified by a census launch
     bool res_ok = false; int res_ipc = 0, res_grid = 0;
+    int res_last_kernel = -1;               // GinResKernel of the last single-launch forward (mtfjsp_encoder_gin_res_kernel_name)
     double *res_stats = nullptr;            // [2 sets][GR_STATS_SET] 64-bit count-carrying fixed-point words (mtfjsp_gin_resident.h); forward n uses set n & 1 and zeroes the other one
     unsigned long long *res_bar = nullptr;  // [17 * 16] barrier words
     unsigned *res_fail = nullptr;           // device address of *res_fail_host
@@ -3028,16 +3029,32 @@ static int res_alloc_fail_word(mtfjsp_encoder *e)
     e->res_fail_host[0] = 0u; e->res_fail_host[1] = 0u;
     return 0;
 }
-// census: every workgroup must be resident at once for the grid barriers to complete (bounded spins report it).  Synchronises the device.
+// Every launch of the single-launch GIN kernel: the instantiation mtfjsp_gin_res_select.h's rule names.
+static void gin_res_launch(GinResKernel k, int grid, hipStream_t stream, const GinResArgs &a)
+{
+    if (k == GIN_RES_K_T36J6X16) hipLaunchKernelGGL(k_gin_res_t36j6x16, dim3(grid), dim3(256), gin_res_lds_bytes(), stream, a);
+    else hipLaunchKernelGGL(k_gin_res, dim3(grid), dim3(256), gin_res_lds_bytes(), stream, a);
+}
+// the rule on this handle for a forward with J candidates per instance (0: none); MTFJSP_GIN_RES_GENERIC as it is NOW (read per call)
+static GinResPlan gin_res_plan_of(const mtfjsp_encoder *e, int J, bool h_nodes, bool ignore_env = false)
+{
+    return gin_res_plan(e->cfg.batch, e->T, e->cfg.n_job, J, e->num_cu, h_nodes, ignore_env ? nullptr : getenv("MTFJSP_GIN_RES_GENERIC"));
+}
+// census: every workgroup must be resident at once for the grid barriers to complete (bounded spins report it) — for each instantiation
+// this handle can launch (the run-time kernel always; the fixed-shape one where the job actor's forward has its shape).  Synchronises the device.
 static bool res_census(mtfjsp_encoder *e)
 {
     if (hipDeviceSynchronize() != hipSuccess) return false;
     if (hipMemset(e->res_bar, 0, (size_t)17 * 16 * 8) != hipSuccess) return false;      // fresh barrier words (a timed-out launch leaves them inconsistent)
     e->res_epoch = 0;
     *e->res_fail_host = 0u;
-    GinResArgs a{};
-    a.bar = e->res_bar; a.epoch = e->res_epoch++; a.fail = e->res_fail; a.barrier_only = 1;
-    hipLaunchKernelGGL(k_gin_res, dim3(e->res_grid), dim3(256), gin_res_lds_bytes(), nullptr, a);
+    const GinResKernel fixed = gin_res_plan_of(e, e->cfg.n_job, false, true).kernel;
+    for (int k = 0; k < GIN_RES_K_COUNT; k++) {
+        if (k != GIN_RES_K_ANY && k != fixed) continue;
+        GinResArgs a{};
+        a.bar = e->res_bar; a.epoch = e->res_epoch++; a.fail = e->res_fail; a.barrier_only = 1;
+        gin_res_launch((GinResKernel)k, e->res_grid, nullptr, a);
+    }
     if (hipDeviceSynchronize() != hipSuccess || *e->res_fail_host) {
         (void)hipMemset(e->res_bar, 0, (size_t)17 * 16 * 8); e->res_epoch = 0; *e->res_fail_host = 0u;
         return false;
@@ -3161,13 +3178,11 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
     e->fuse_mheads = false;
 #endif
     {   // resident GIN kernel: whole instances per workgroup, at most 576 rows, one workgroup per CU
-        const int T = e->T, B = cfg->batch;
-        if (!getenv("MTFJSP_NO_RESIDENT_GIN") && T >= GR_MINT && T <= GR_MAXT) {
-            const int ipc = (B + e->num_cu - 1) / e->num_cu;
-            const int grid = (B + ipc - 1) / ipc;
-            // (grid + 7) / 8 <= 63: a count-carrying statistics word holds the arrivals of one dispatch group in 6 bits (gr_fix_encode)
-            if (ipc * T <= GR_ROWS && ipc <= GR_MAXIPC && grid <= e->num_cu && (grid + 7) / 8 <= 63 && ipc * cfg->n_job <= GR_MAXCAND &&
-                hipFuncSetAttribute((const void *)k_gin_res, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess) {
+        const GinResPlan pl = gin_res_plan_of(e, cfg->n_job, false, true);          // (eligibility, ipc and grid do not depend on the forward)
+        if (!getenv("MTFJSP_NO_RESIDENT_GIN") && pl.eligible) {
+            const int ipc = pl.ipc, grid = pl.grid;
+            if (hipFuncSetAttribute((const void *)k_gin_res, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess &&
+                hipFuncSetAttribute((const void *)k_gin_res_t36j6x16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess) {
                 int rc = dalloc(e, &e->res_stats, (size_t)2 * GR_STATS_SET) | dalloc(e, &e->res_bar, (size_t)17 * 16) |
                          dalloc(e, &e->res_zspill, (size_t)grid * 4 * (GR_NT - GR_NRES) * 1024);
                 if (!rc && hipMemset(e->res_stats, 0, (size_t)2 * GR_STATS_SET * 8) == hipSuccess &&
@@ -3753,8 +3768,12 @@ static int run_gin_resident(mtfjsp_encoder *e, const std::string &pre, const voi
     a.stamps = d_st;
 #endif
     {
+        // (the step's forward, the post-terminal forward and the values-only forward all come through here: one rule, one instantiation per shape)
+        const GinResPlan pl = gin_res_plan_of(e, a.J, h_nodes != nullptr);
+        if (!pl.eligible || pl.ipc != e->res_ipc || pl.grid != e->res_grid) { e->err = "resident GIN: the launch plan does not match the handle"; return MTFJSP_ERR_STATE; }
+        e->res_last_kernel = (int)pl.kernel;
         Timed t(e, "gin_resident");
-        hipLaunchKernelGGL(k_gin_res, dim3(e->res_grid), dim3(256), gin_res_lds_bytes(), e->stream, a);
+        gin_res_launch(pl.kernel, e->res_grid, e->stream, a);
     }
 #ifdef GR_STAMP
     static int printed = 0;
@@ -4529,6 +4548,18 @@ extern "C" int mtfjsp_encoder_check(mtfjsp_encoder_t e, int32_t *gin_resident_ou
     if (gin_resident_out) *gin_resident_out = (e->res_ok && !e->reduce_fn && !(e->f32_products & (1 | 8 | 16))) ? 1 : 0;
     return rc;
 }
+extern "C" const char *mtfjsp_gin_res_kernel_name_for(int32_t batch, int32_t rows_per_instance, int32_t n_job, int32_t candidates, int32_t num_cu,
+                                                      int32_t node_output, int32_t *ipc_out, int32_t *grid_out)
+{
+    const GinResPlan pl = gin_res_plan(batch, rows_per_instance, n_job, candidates, num_cu, node_output != 0, getenv("MTFJSP_GIN_RES_GENERIC"));
+    if (ipc_out) *ipc_out = pl.ipc;
+    if (grid_out) *grid_out = pl.grid;
+    return pl.eligible ? GIN_RES_KERNEL_NAME[pl.kernel] : nullptr;
+}
+extern "C" const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e)
+{
+    return e && e->res_last_kernel >= 0 ? GIN_RES_KERNEL_NAME[e->res_last_kernel] : nullptr;
+}
 extern "C" int mtfjsp_encoder_resident_failures(mtfjsp_encoder_t e, int64_t *count_out)
 {
     if (!e || !count_out) return MTFJSP_ERR_ARG;
@@ -4544,6 +4575,19 @@ extern "C" int mtfjsp_encoder_peek_nodes_host(mtfjsp_encoder_t e, float *out_hos
     HIPCHK(e, hipSetDevice(e->cfg.device_id));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipMemcpy(out_host, e->node, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    return MTFJSP_OK;
+}
+extern "C" int mtfjsp_encoder_peek_gin_res_host(mtfjsp_encoder_t e, float *cand_feat_host, int64_t count, uint64_t *stats_host, uint32_t *flags_host)
+{
+    if (!e || count < 0 || count > (int64_t)e->cfg.batch * e->cfg.n_job * HD) return MTFJSP_ERR_ARG;
+    if (!e->res_eligible || e->res_epoch == 0) { e->err = "no single-launch GIN forward on this handle yet"; return MTFJSP_ERR_STATE; }
+    HIPCHK(e, hipSetDevice(e->cfg.device_id));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (cand_feat_host) HIPCHK(e, hipMemcpy(cand_feat_host, e->cand_feat, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    if (stats_host)                                                // the set the last launch accumulated into (the launch after it zeroes the other one)
+        HIPCHK(e, hipMemcpy(stats_host, reinterpret_cast<unsigned long long *>(e->res_stats) + (size_t)((e->res_epoch - 1) & 1) * GR_STATS_SET,
+                            (size_t)GR_STATS_SET * 8, hipMemcpyDeviceToHost));
+    if (flags_host) { flags_host[0] = e->res_fail_host[0]; flags_host[1] = e->res_fail_host[1]; }
     return MTFJSP_OK;
 }
 extern "C" int mtfjsp_encoder_range_fallbacks(mtfjsp_encoder_t e, int64_t *count_out, int32_t *product_mode_out)

@@ -38,22 +38,27 @@
 // f32 in a ring of 6 row tiles (192 rows, XOR-swizzled); with T <= 65 rows per instance the neighbours of tile rt lie in tiles
 // rt-2..rt+2.  Eligibility (host): 16 <= T <= 65 and ceil(B / 256) instances * T <= 576 rows per workgroup.
 // The bias of a Linear that feeds a BatchNorm cancels exactly (BN(z + b) = BN(z)), so no bias is added anywhere here.
-#pragma once
+//
+// One body, two instantiations.  The kernel's text (the second part of this file) is compiled once per (GR_KERNEL, GR_SHAPE) pair: the first
+// part — arguments, sizes, helpers — includes the file again with the pair set.  (The body stays a __global__ function of its own rather
+// than a template called from two kernels: inlined from a device function the same text schedules differently and spills.)
+#ifndef GR_KERNEL
+#ifndef MTFJSP_GIN_RESIDENT_H
+#define MTFJSP_GIN_RESIDENT_H
 #include <type_traits>
 #include <utility>
+#include "mtfjsp_gin_res_select.h"        // GR_NT, GR_ROWS, the eligibility limits and which instantiation serves a shape
 
 #ifndef GR_ABL                            // diagnostic timing ablations (wrong results): 1 no plane production, 2 no matrix products, 4 no statistics,
                                           // 8 no plane writes, 16 no pooling, 32 no candidate gather
 #define GR_ABL 0
 #endif
-#define GR_NT 18                          // row tiles per workgroup (576 rows)
 #ifndef GR_NRES
 #define GR_NRES 16                        // ... of which this many stay in registers; the others go through zspill (see below)
 #endif
 #ifndef GR_VRES
 #define GR_VRES 1                         // 1: row tiles GR_NRES.. stay on chip too — in the VECTOR registers that used to stage their round trip through global
 #endif                                    // memory (the matrix instructions on them are written out with vector-register accumulators); 0: the round trip
-#define GR_ROWS (32 * GR_NT)
 #define GR_RING 6                         // row tiles in the f32 ring of the aggregation layer
 #define GR_NBAR 6                         // grid barriers per launch
 #ifndef GR_GRP
@@ -68,11 +73,40 @@
 #define GR_ROWB 272                       // plane row pitch in bytes (256 + 16: conflict-free 16-byte operand reads)
 #define GR_PLANE (32 * GR_ROWB)
 #define GR_TILE (2 * GR_PLANE)                // a tile buffer: the (high | low) f16 planes of 32 rows
-#define GR_MAXCAND 384
 #define GR_MAXWARM 10
-#define GR_MAXT 65                        // rows per instance: the in-edge sources of a tile lie within two tiles of it
-#define GR_MINT 16                        // ... and a 16-row run spans at most two instances (pooling)
-#define GR_MAXIPC 64                      // instances per workgroup (u8 instance ids; pool accumulators in the ring area)
+// What the fixed-shape instantiation (GrShapeFixed below) drops or moves, one switch each for A/B builds (-DGR_FX_...=0 is the run-time code):
+#ifndef GR_FX_DROP
+#define GR_FX_DROP 1                      // row-valid selects and s_zero, the prologue's validity clamps, the divisions by J and T, the node-output test, the
+#endif                                    // run-time `left` of the pooling, candidate-store addresses from one base
+#ifndef GR_FX_TAIL
+#define GR_FX_TAIL 1                      // pooled tail with a constant trip count, every read issued before the first use
+#endif
+#ifndef GR_FX_SETUP
+#define GR_FX_SETUP 1                     // the final phase's set-up (s_wtab, slot[], the warm request) inside the last boundary, behind its atomic; needs
+#endif                                    // GR_FOLD_DPP (the boundary's LDS fold parks its sums in the ring area the table lives in)
+// The shape as compile-time parameters of the ONE kernel body.  GrShapeAny: everything read from GinResArgs (any 16 <= T <= 65, any
+// instances-per-workgroup count, a partly filled last workgroup, optional node output).  GrShapeFixed: T rows per instance, J candidates
+// per instance (A.candidate given), IPC instances in EVERY workgroup (B % IPC == 0, IPC * T == GR_ROWS), no node output.
+struct GrShapeAny { static constexpr bool FIXED = false; static constexpr int T = 0, J = 0, IPC = 0; };
+template <int T_, int J_, int IPC_> struct GrShapeFixed {
+    static constexpr bool FIXED = true; static constexpr int T = T_, J = J_, IPC = IPC_;
+    static_assert(T_ >= GR_MINT && T_ <= GR_MAXT && IPC_ * T_ == GR_ROWS && IPC_ * J_ <= GR_MAXCAND && (IPC_ * 128) % 256 == 0, "fixed shape: full 576-row workgroups");
+};
+typedef GrShapeFixed<GIN_RES_FX_T, GIN_RES_FX_J, GIN_RES_FX_IPC> GrShapeHeadline;
+// rows of the instance of a lane's first row (16 h of tile 0) still ahead at tile rt (the pooling's `left`, as a constant)
+constexpr int gr_left_at(int T, int h, int rt)
+{
+    int left = ((16 * h) / T + 1) * T - 16 * h;
+    for (int i = 0; i < rt; i++) { left -= 32; if (left <= 0) left += T; if (left <= 0) left += T; }
+    return left;
+}
+// 16-row chunks an instance of T rows can touch when instances start at multiples of T
+constexpr int gr_max_chunks(int T)
+{
+    int m = 0;
+    for (int i = 0; i < 16; i++) { const int r0 = i * T, c = ((r0 + T - 1) >> 4) - (r0 >> 4) + 1; m = c > m ? c : m; }
+    return m;
+}
 
 #ifndef GR_MIX
 #define GR_MIX 2                          // 1: the low operand piece as fma(f16 high piece, -1, x) = v_fma_mix_f32 (no separate f16 -> f32 conversion); same bits
@@ -276,11 +310,26 @@ __device__ __forceinline__ void gr_grid_barrier(unsigned long long *bar, unsigne
     __syncthreads();
 }
 
-#ifdef MTFJSP_GIN_RES_DECL_ONLY
-__global__ __launch_bounds__(256) void k_gin_res(GinResArgs A);
-#else
-__global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
+__global__ __launch_bounds__(256) void k_gin_res(GinResArgs A);                 // GrShapeAny
+__global__ __launch_bounds__(256) void k_gin_res_t36j6x16(GinResArgs A);        // GrShapeHeadline (mtfjsp_gin_res_select.h says when)
+#ifndef MTFJSP_GIN_RES_DECL_ONLY
+#define GR_KERNEL k_gin_res
+#define GR_SHAPE GrShapeAny
+#include "mtfjsp_gin_resident.h"
+#undef GR_KERNEL
+#undef GR_SHAPE
+#define GR_KERNEL k_gin_res_t36j6x16
+#define GR_SHAPE GrShapeHeadline
+#include "mtfjsp_gin_resident.h"
+#undef GR_KERNEL
+#undef GR_SHAPE
+#endif
+#endif                                    // MTFJSP_GIN_RESIDENT_H
+#else                                     // ---------------------------------------------------------------- the kernel, shape GR_SHAPE
+__global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
 {
+    typedef GR_SHAPE SH;
+    constexpr bool FXD = SH::FIXED && GR_FX_DROP, FXT = SH::FIXED && GR_FX_TAIL, FXS = SH::FIXED && GR_FX_SETUP && GR_FOLD_DPP;
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char *s_planes = smem + GR_OFF_PLANES;
     float *s_ring = reinterpret_cast<float *>(smem + GR_OFF_RING);
@@ -300,9 +349,10 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
         for (int k = 0; k < GR_NBAR; k++) gr_grid_barrier(A.bar, gen0 + k + 1, nblk, A.fail, s_flag);
         return;
     }
-    const int T = A.T;
-    const int inst0 = blockIdx.x * A.ipc;
-    const int ninst = A.B - inst0 < A.ipc ? A.B - inst0 : A.ipc;
+    const int T = FXD ? SH::T : A.T, Jn = FXD ? SH::J : A.J;
+    const int inst0 = blockIdx.x * (FXD ? SH::IPC : A.ipc);
+    const int ninst = FXD ? SH::IPC : A.B - inst0 < A.ipc ? A.B - inst0 : A.ipc;
+    const bool have_cand = FXD || A.candidate;
     const int nrows = ninst * T;
     const size_t grow0 = (size_t)inst0 * T;                       // first global row of this workgroup
     // (every workgroup computes all GR_NT tiles: rows >= nrows are zero inputs, masked out of the BatchNorm sums and never
@@ -319,7 +369,7 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
 #pragma unroll
         for (int k = 0; k < (GR_MAXCAND + 255) / 256; k++) {
             const int i = tid + 256 * k;
-            cand_pre[k] = (A.candidate && i < ninst * A.J) ? A.candidate[(size_t)inst0 * A.J + i] : -1;
+            cand_pre[k] = (have_cand && i < ninst * Jn) ? A.candidate[(size_t)inst0 * Jn + i] : -1;
         }
         // Every request of the prologue goes out before the first of them is waited for (round 5: as `for (i = tid; i < n; i += 256)` loops
         // with a run-time bound the feature and adjacency copies were compiled into load -> s_waitcnt vmcnt(0) -> LDS store per iteration:
@@ -383,15 +433,15 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
         if (tid == 0) s_flag[1] = 0u;
         if (tid < 5 * (GR_NT / GR_GRP)) s_cnt[tid] = 0u;
         for (int i = tid; i < 2 * GR_TILE / 16; i += 256) reinterpret_cast<float4 *>(s_planes)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (A.candidate) {                                        // row -> candidate slot (ac:197-207 gathers h of one row per job)
+        if (have_cand) {                                          // row -> candidate slot (ac:197-207 gathers h of one row per job)
             LDS_BARRIER();                                        // (s_rowcand is LDS; __syncthreads() would also wait for the weight request above)
 #pragma unroll
             for (int k = 0; k < (GR_MAXCAND + 255) / 256; k++) {
                 const int i = tid + 256 * k, c = cand_pre[k];
-                if (i < ninst * A.J && c >= 0 && c < T && atomicExch(&s_rowcand[(i / A.J) * T + c], i) != -1) s_flag[1] = 1u;   // two slots on one row: fixed up at the end
+                if (i < ninst * Jn && c >= 0 && c < T && atomicExch(&s_rowcand[(i / Jn) * T + c], i) != -1) s_flag[1] = 1u;   // two slots on one row: fixed up at the end
             }
         }
-        s_zero[tid] = 0.f;
+        if constexpr (!FXD) s_zero[tid] = 0.f;
     }
     // 18 tiles x 16 accumulators = 288 values per lane, but only 256 accumulation registers exist and the matrix instructions
     // need one 16-register tuple of them to work in: left to itself hipcc keeps two values per tile in scratch memory and the
@@ -426,7 +476,12 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
     // layer: left alone, hipcc forms all 18 tiles' once and keeps them for five layers — through scratch memory (128 reloads, 47
     // stores per wave) and SGPR spill lanes (~570 v_readlane / v_writelane).  nrows_l is the same number made opaque at the top of each
     // layer (and so is the lane's row index n_l), so each layer forms its own (an or, a compare, two selects and two adds per tile).
+    // (Fixed shape: every row of every workgroup is valid — no select, no s_zero.)
     int nrows_l = nrows, n_l = n;
+    auto bn_of = [&](int rt) __attribute__((always_inline)) -> const float * {
+        if constexpr (FXD) return s_bn;
+        else return rt * 32 + n_l < nrows_l ? s_bn : s_zero;     // rows >= nrows: scale = shift = 0 -> zero planes
+    };
     bool timed_out = false;                                       // a statistics wait of this launch gave up: everything after it is garbage
     gr_h8 wf[2][8];
     bf16x8 w0f[3];                                                // (first Linear only)
@@ -541,7 +596,7 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
     auto produce_quarter = [&](auto Tc, auto Gc, unsigned char *pbuf) __attribute__((always_inline)) {
         constexpr int rt = decltype(Tc)::value, g = decltype(Gc)::value;
         unsigned char *dst = pbuf + n * GR_ROWB + (32 * wave + 8 * g + 4 * h) * 2;
-        const float *bn = rt * 32 + n_l < nrows_l ? s_bn : s_zero;  // rows >= nrows: scale = shift = 0 -> zero planes
+        const float *bn = bn_of(rt);
         const float4 s4 = *reinterpret_cast<const float4 *>(bn + 32 * wave + 8 * g + 4 * h);        // scale | shift of these 4 columns
         const float4 h4 = *reinterpret_cast<const float4 *>(bn + HD + 32 * wave + 8 * g + 4 * h);
         const f32x16 &a = GR_TILEVAL(rt);
@@ -573,7 +628,7 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
         constexpr bool STATS = RT > 0 && (GR_VRES || RT - 1 < GR_NRES) && !(GR_ABL & 4);     // (a spilled tile's sums are taken when it is stored)
         const unsigned char *xa = plane_buf(RT % (2 * GR_LOOK)) + n * GR_ROWB + 16 * h;
         unsigned char *pnext = plane_buf(PT % (2 * GR_LOOK));
-        const float *bn = PT * 32 + n_l < nrows_l ? s_bn : s_zero;          // rows >= nrows: scale = shift = 0 -> zero planes
+        const float *bn = bn_of(PT);
         gr_h8 xf[2][2];
 #pragma unroll
         for (int p = 0; p < 2; p++) xf[0][p] = *reinterpret_cast<const gr_h8 *>(xa + p * GR_PLANE);
@@ -672,6 +727,40 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
         if constexpr (RT > 0 && (GR_VRES || RT - 1 < GR_NRES)) stats_tile(std::integral_constant<int, RT - 1>{});
         __builtin_amdgcn_sched_barrier(0);
     };
+    // Set-up of the final phase (pool + candidate gather): nothing here depends on the last boundary's statistics.  Run-time shape: behind
+    // that boundary.  Fixed shape (GR_FX_SETUP): inside it, behind its atomic — where the earlier boundaries request the next layer's weights
+    // — so that it runs while the boundary waits for the other workgroups; the boundary's own LDS barrier then also publishes s_wtab.
+    // The table's ring area (past the plane buffers 2, 3 of the layers without aggregation) is free there with GR_FOLD_DPP.
+    float *s_wtab = s_ring + 1024 + 4 * (2 * 32 * 36);            // [17][16]: row j = 1 for the first j of a chunk's 16 rows, 0 for the others (pool_tile)
+    static_assert(!(GR_FX_SETUP && GR_FOLD_DPP) || (1024 + 4 * (2 * 32 * 36)) * 4 >= (2 * GR_LOOK - 2) * GR_TILE, "s_wtab lies past the plane buffers in the ring area");
+    unsigned warm_word = 0;
+    int slot[GR_NT];                                              // candidate slot of this lane's row in every tile (-1: none)
+    auto final_setup_a = [&]() __attribute__((always_inline)) {
+        int tid_s = tid;
+        if constexpr (FXS) asm volatile("" : "+v"(tid_s));           // (inside the boundary: indices formed here, not kept from the prologue in scratch memory)
+        for (int i = tid_s; i < 17 * 16; i += 256) s_wtab[i] = (i & 15) < (i >> 4) ? 1.0f : 0.0f;
+        // ONE request per thread on behalf of the next launch (GinResArgs::warm): thread (blockIdx / 8) * 256 + tid of this XCD's workgroups
+        // takes that line of the concatenated buffers (lines beyond the XCD's thread count are not requested); the word is dropped behind
+        // the last tile, where it has long arrived — no wait of this phase can be held up by it
+        if (A.nwarm > 0) {
+            unsigned l = (blockIdx.x >> 3) * 256u + (unsigned)tid_s;
+            const unsigned char *wp = reinterpret_cast<const unsigned char *>(A.warm[0]);
+            bool found = false;
+            for (int w = 0; w < A.nwarm; w++) {
+                const unsigned nl = A.warm_lines[w];
+                if (!found && l < nl) { wp = reinterpret_cast<const unsigned char *>(A.warm[w]) + (size_t)l * 128; found = true; }
+                if (!found) l -= nl;
+            }
+            warm_word = *reinterpret_cast<const unsigned *>(wp);
+        }
+    };
+    auto final_setup_b = [&]() __attribute__((always_inline)) {
+#ifndef GR_KEEP_MASKS
+        asm volatile("" : "+v"(n_l));                                 // (the row indices of this phase are formed here, not kept from the layers)
+#endif
+#pragma unroll
+        for (int rt = 0; rt < GR_NT; rt++) slot[rt] = (GR_ABL & 32) ? -1 : s_rowcand[rt * 32 + n_l];
+    };
     // this workgroup's column sums -> its dispatch group's accumulators, grid barrier `k` (which folds the groups into the totals),
     // then the BatchNorm scale / shift of the NEXT layer's input from the complete sums
     auto layer_boundary = [&](auto Kc) __attribute__((always_inline)) {
@@ -684,7 +773,10 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
 #if GR_FOLD_DPP
         (void)fold_stats;
         const float colsum = fold_stats_dpp();                    // lane n of a half wave: value n of its 32 (see above)
-        const int kind = n >> 4, scol = 32 * wave + 8 * ((n & 15) >> 2) + 4 * h + (n & 3);
+        int lane_b = lane;
+        if constexpr (FXS && k == 5) asm volatile("" : "+v"(lane_b));   // (the boundary that holds the final phase's set-up forms its word index afresh: one register pair less across the layers)
+        const int n_b = lane_b & 31, h_b = lane_b >> 5;
+        const int kind = n_b >> 4, scol = 32 * wave + 8 * ((n_b & 15) >> 2) + 4 * h_b + (n_b & 3);
         constexpr int PAIR = 16;                                  // the lane holding the other kind of the same column
 #else
         const float colsum = fold_stats();                        // (GR_VRES 0: tile 17's sums were taken when it was stored)
@@ -712,6 +804,7 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
         // statistics' atomics queue behind 64 KB of loads in the in-order memory pipeline and every boundary gets 0.4 to 1.9 us longer.)
         const float ga = A.gamma[k][scol], be = A.beta[k][scol];
         if constexpr (k < 5) load_weights(k + 1);
+        else if constexpr (FXS) { final_setup_a(); final_setup_b(); }
         GR_STAMP_AT(5 + 4 * k);
         // every thread collects its own (column, kind) from the 8 dispatch groups: a word is complete when it carries its group's size
         // in the count field
@@ -779,7 +872,7 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
             const float2 y = *reinterpret_cast<const float2 *>(s_feat + n1 * 12 + fo);
             // gcn:125-153 (A_w @ h) / nnz_row on the raw features; small-integer weights, <= 3 terms: f32 FMA chain
             float v[4] = {__builtin_fmaf(w1, y.x, __builtin_fmaf(w0, x.x, o.x)) * inv, __builtin_fmaf(w1, y.y, __builtin_fmaf(w0, x.y, o.y)) * inv, 0.f, 0.f};
-            if (row >= nrows) { v[0] = 0.f; v[1] = 0.f; }
+            if (!FXD && row >= nrows) { v[0] = 0.f; v[1] = 0.f; }
             uint2 p0, p1, p2;
             split3x4(v, p0, p1, p2);                              // elements 2, 3 are padding
             unsigned char *d = s_planes + r * GR_ROWB + 32 * (rt & 7) + 4 * fk;
@@ -814,7 +907,8 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
     gr_static_for<5>([&](auto Lc) __attribute__((always_inline)) {
         constexpr int layer = decltype(Lc)::value + 1;
 #ifndef GR_KEEP_MASKS                     // (A/B: -DGR_KEEP_MASKS is the code before this change)
-        asm volatile("" : "+s"(nrows_l), "+v"(n_l));
+        if constexpr (FXD) asm volatile("" : "+v"(n_l));
+        else asm volatile("" : "+s"(nrows_l), "+v"(n_l));
 #endif
         if constexpr (layer != 3) {
             gr_static_for<GR_LOOK>([&](auto Ic) __attribute__((always_inline)) { produce_tile(Ic, plane_buf(decltype(Ic)::value)); });
@@ -851,7 +945,7 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
                 float *base = s_ring + ((rt % GR_RING) * 32 + n) * HD;
                 gr_static_for<4>([&](auto Gc) __attribute__((always_inline)) {
                     constexpr int g = decltype(Gc)::value;
-                    const float *bn = rt * 32 + n_l < nrows_l ? s_bn : s_zero;
+                    const float *bn = bn_of(rt);
                     const float4 s4 = *reinterpret_cast<const float4 *>(bn + 32 * wave + 8 * g + 4 * h);
                     const float4 h4 = *reinterpret_cast<const float4 *>(bn + HD + 32 * wave + 8 * g + 4 * h);
                     const f32x16 &a = GR_TILEVAL(rt);
@@ -909,7 +1003,7 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
                 for (int p = 0; p < 2; p++) xf[0][p] = *reinterpret_cast<const gr_h8 *>(xa + p * GR_PLANE);
                 AggRow r = agg_row(NEXT ? RT + 1 : RT);
                 unsigned char *dst = s_planes + ((RT + 1) & 1) * GR_TILE + n * GR_ROWB + (32 * wave + 4 * h) * 2;
-                const float *bnw = WT * 32 + n_l < nrows_l ? s_bn : s_zero;
+                const float *bnw = bn_of(WT);
                 float *hbase = s_ring + ((WT % GR_RING) * 32 + n) * HD;
                 float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f), h4 = s4;
                 if constexpr (WH) {
@@ -1012,57 +1106,53 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
     // instance are added in a fixed order at the end (deterministic, no atomics).  Candidate rows and the optional node
     // embeddings go out straight from the registers (16 bytes per lane and column group).
     {
+        // (this phase forms its lane-derived indices afresh: kept from the top of the kernel they would cross all six layers in scratch memory)
+        int lane_f = lane;
+        asm volatile("" : "+v"(lane_f));
+        const int n_f = lane_f & 31, h_f = lane_f >> 5;
         float *s_part = reinterpret_cast<float *>(s_planes);      // [2 * GR_NT chunks][2 segments][128] = 36 KB: the plane buffers and the first 2 KB of the ring area
         static_assert(2 * GR_NT * 2 * HD * 4 <= 2 * GR_TILE + 4096, "partial pool sums: plane buffers + 4 KB");
         float *tb = s_ring + 1024 + wave * (2 * 32 * 36);         // transposition buffers: ring area past those 4 KB
-        float *s_wtab = s_ring + 1024 + 4 * (2 * 32 * 36);        // [17][16]: row j = 1 for the first j of a chunk's 16 rows, 0 for the others (pool_tile)
-        for (int i = tid; i < 17 * 16; i += 256) s_wtab[i] = (i & 15) < (i >> 4) ? 1.0f : 0.0f;
-        // ONE request per thread on behalf of the next launch (GinResArgs::warm): thread (blockIdx / 8) * 256 + tid of this XCD's workgroups
-        // takes that line of the concatenated buffers (lines beyond the XCD's thread count are not requested); the word is dropped behind
-        // the last tile, where it has long arrived — no wait of this phase can be held up by it
-        unsigned warm_word = 0;
-        if (A.nwarm > 0) {
-            unsigned l = (blockIdx.x >> 3) * 256u + (unsigned)tid;
-            const unsigned char *wp = reinterpret_cast<const unsigned char *>(A.warm[0]);
-            bool found = false;
-            for (int w = 0; w < A.nwarm; w++) {
-                const unsigned nl = A.warm_lines[w];
-                if (!found && l < nl) { wp = reinterpret_cast<const unsigned char *>(A.warm[w]) + (size_t)l * 128; found = true; }
-                if (!found) l -= nl;
-            }
-            warm_word = *reinterpret_cast<const unsigned *>(wp);
-        }
+        if constexpr (!FXS) final_setup_a();
         float4 S[4], Hs[4];
 #pragma unroll
         for (int g = 0; g < 4; g++) {
-            S[g] = *reinterpret_cast<const float4 *>(s_bn + 32 * wave + 8 * g + 4 * h);
-            Hs[g] = *reinterpret_cast<const float4 *>(s_bn + HD + 32 * wave + 8 * g + 4 * h);
+            S[g] = *reinterpret_cast<const float4 *>(s_bn + 32 * wave + 8 * g + 4 * h_f);
+            Hs[g] = *reinterpret_cast<const float4 *>(s_bn + HD + 32 * wave + 8 * g + 4 * h_f);
         }
         if constexpr (GR_NT - GR_NRES >= 1) zload(std::integral_constant<int, 0>{});
         if constexpr (GR_NT - GR_NRES >= 2) zload(std::integral_constant<int, 1>{});
-        const int c = lane & 31;
-        int left = ((16 * h) / T + 1) * T - 16 * h;                   // rows of the instance of this lane's first row (16h of tile 0) still ahead
-        int slot[GR_NT];                                              // candidate slot of this lane's row in every tile (-1: none)
-#ifndef GR_KEEP_MASKS
-        asm volatile("" : "+v"(n_l));                                 // (the row indices of this phase are formed here, not kept from the layers)
-#endif
-#pragma unroll
-        for (int rt = 0; rt < GR_NT; rt++) slot[rt] = (GR_ABL & 32) ? -1 : s_rowcand[rt * 32 + n_l];
-        LDS_BARRIER();                                                // the plane buffers are no longer read
+        const int c = lane_f & 31;
+        int left = ((16 * h_f) / T + 1) * T - 16 * h_f;                   // rows of the instance of this lane's first row (16h of tile 0) still ahead
+        // (fixed shape: a constant per tile and half wave, gr_left_at)
+        auto left_at = [&](auto Rc) __attribute__((always_inline)) {
+            constexpr int rt = decltype(Rc)::value;
+            constexpr int FT = FXD ? SH::T : GR_MINT;
+            if constexpr (FXD) return h_f ? gr_left_at(FT, 1, rt) : gr_left_at(FT, 0, rt);
+            else return left;
+        };
+        if constexpr (!FXS) { final_setup_b(); LDS_BARRIER(); }       // the plane buffers are no longer read (fixed shape: the last boundary's barrier)
+        // candidate rows: one base for the workgroup, a 32-bit offset per row
+        unsigned char *const cbase = reinterpret_cast<unsigned char *>(A.cand_feat + (size_t)inst0 * Jn * HD);
+        const unsigned coff = (unsigned)(32 * wave + 4 * h_f) * 4u;
         GR_STAMP_AT(28);
         // gcn:192 for one tile: rows 16h .. 16h+15 of column c from the transposition buffer, split at the instance boundary
         // pool_load: the requests (a chunk's 16 values of column c, its weights) — issued a tile's BatchNorm + ReLU ahead of pool_math, which
         // would otherwise meet an LDS round trip with nothing to cover it (one wave per SIMD)
         float x[16];
         float4 w0, w1, w2, w3;
-        auto pool_load = [&](int rt) __attribute__((always_inline)) {
-            const float *rb = tb + (rt & 1) * (32 * 36) + (16 * h) * 36 + c;
+        auto pool_load = [&](auto Rc) __attribute__((always_inline)) {
+            constexpr int rt = decltype(Rc)::value;
+            const int lf = left_at(Rc);
+            const float *rb = tb + (rt & 1) * (32 * 36) + (16 * h_f) * 36 + c;
 #pragma unroll
             for (int i = 0; i < 16; i++) x[i] = rb[i * 36];
-            const float4 *wt = reinterpret_cast<const float4 *>(s_wtab + (left < 16 ? left : 16) * 16);
+            const float4 *wt = reinterpret_cast<const float4 *>(s_wtab + (lf < 16 ? lf : 16) * 16);
             w0 = wt[0]; w1 = wt[1]; w2 = wt[2]; w3 = wt[3];
         };
-        auto pool_math = [&](int rt) __attribute__((always_inline)) {
+        auto pool_math = [&](auto Rc) __attribute__((always_inline)) {
+            constexpr int rt = decltype(Rc)::value;
+            const int lf = left_at(Rc);
             // the chunk's total by a pairwise tree of two-wide adds, the part in front of the instance boundary by two-wide FMAs against the
             // 0 / 1 weights of row `left` of s_wtab (round 5: the weights were formed per value — a subtraction, a clamp and an FMA each, 48
             // vector instructions per tile where the vector unit is what this phase waits for), the rest as their difference
@@ -1078,16 +1168,18 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
                                      gr_add2(gr_add2(f32x2{x[8], x[9]}, f32x2{x[10], x[11]}), gr_add2(f32x2{x[12], x[13]}, f32x2{x[14], x[15]})));
             const float tot = t2[0] + t2[1];
             const float sa = sa2[0] + sa2[1];
-            float *pp = s_part + ((2 * rt + h) * 2) * HD + 32 * wave + c;
-            pp[0] = left >= 16 ? tot : sa; pp[HD] = left >= 16 ? 0.f : tot - sa;
-            left -= 32;                                               // on to this lane's rows of the next tile (T >= 16: at most two instances further)
-            if (left <= 0) left += T;
-            if (left <= 0) left += T;
+            float *pp = s_part + ((2 * rt + h_f) * 2) * HD + 32 * wave + c;
+            pp[0] = lf >= 16 ? tot : sa; pp[HD] = lf >= 16 ? 0.f : tot - sa;
+            if constexpr (!FXD) {
+                left -= 32;                                           // on to this lane's rows of the next tile (T >= 16: at most two instances further)
+                if (left <= 0) left += T;
+                if (left <= 0) left += T;
+            }
         };
         gr_static_for<GR_NT>([&](auto Tc) __attribute__((always_inline)) {
             constexpr int rt = decltype(Tc)::value;
             const f32x16 &a = GR_TILEVAL(rt);
-            if constexpr (rt > 0) { if (!(GR_ABL & 16)) pool_load(rt - 1); }     // one tile behind: its writes have landed (the other buffer)
+            if constexpr (rt > 0) { if (!(GR_ABL & 16)) pool_load(std::integral_constant<int, rt - 1>{}); }     // one tile behind: its writes have landed (the other buffer)
             float4 v[4];
 #pragma unroll
             for (int g = 0; g < 4; g++) {
@@ -1097,21 +1189,22 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
             }
             float *wb = tb + (rt & 1) * (32 * 36);
 #pragma unroll
-            for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(wb + n * 36 + 8 * g + 4 * h) = v[g];
+            for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(wb + n_f * 36 + 8 * g + 4 * h_f) = v[g];
             if (slot[rt] >= 0) {
-                float *d = A.cand_feat + ((size_t)inst0 * A.J + slot[rt]) * HD + 32 * wave + 4 * h;
+                float *d = FXD ? reinterpret_cast<float *>(cbase + ((unsigned)slot[rt] * (unsigned)(HD * 4) + coff))
+                               : A.cand_feat + ((size_t)inst0 * Jn + slot[rt]) * HD + 32 * wave + 4 * h_f;
 #pragma unroll
                 for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(d + 8 * g) = v[g];
             }
-            if (A.h_nodes && rt * 32 + n_l < nrows) {
-                float *d = A.h_nodes + (grow0 + rt * 32 + n_l) * HD + 32 * wave + 4 * h;
+            if (!FXD && A.h_nodes && rt * 32 + n_l < nrows) {
+                float *d = A.h_nodes + (grow0 + rt * 32 + n_l) * HD + 32 * wave + 4 * h_f;
 #pragma unroll
                 for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(d + 8 * g) = v[g];
             }
-            if constexpr (rt > 0) { if (!(GR_ABL & 16)) pool_math(rt - 1); }
+            if constexpr (rt > 0) { if (!(GR_ABL & 16)) pool_math(std::integral_constant<int, rt - 1>{}); }
             __builtin_amdgcn_sched_barrier(0);
         });
-        if (!(GR_ABL & 16)) { pool_load(GR_NT - 1); pool_math(GR_NT - 1); }
+        if (!(GR_ABL & 16)) { pool_load(std::integral_constant<int, GR_NT - 1>{}); pool_math(std::integral_constant<int, GR_NT - 1>{}); }
         asm volatile("" :: "v"(warm_word));
         GR_STAMP_AT(29);
         LDS_BARRIER();
@@ -1120,6 +1213,34 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
         // instance not added — instead of a loop with a run-time trip count whose reads each waited for the one before: 2.0 -> ~0.7 us of this phase's tail.
         // Same additions in the same order.)
         static_assert(GR_MAXT <= 65, "an instance spans at most five 16-row chunks");
+        if constexpr (FXT) {
+            // (an opaque copy of the thread index: tid + 256 k is what the prologue's copies use too, and hipcc would keep those seven registers
+            // for the whole kernel — through scratch memory)
+            int tid_f = tid;
+            asm volatile("" : "+v"(tid_f));
+            // fixed shape: SH::IPC * HD / 256 items per thread and at most NCH chunks per instance, every read requested before the first sum
+            constexpr int FT = FXT ? SH::T : GR_MINT, NIT = FXT ? SH::IPC * HD / 256 : 1, NCH = gr_max_chunks(FT);     // (the other shape: placeholders, not compiled in)
+            float pv[NIT][NCH];
+#pragma unroll
+            for (int it = 0; it < NIT; it++) {
+                const int item = tid_f + 256 * it, inst = item >> 7, col = item & (HD - 1);
+                const int r0 = inst * FT, k0 = r0 >> 4, k1 = (r0 + FT - 1) >> 4;
+#pragma unroll
+                for (int kk = 0; kk < NCH; kk++) {
+                    const int k = k0 + kk < k1 ? k0 + kk : k1;
+                    pv[it][kk] = s_part[(2 * k + (16 * k < r0 ? 1 : 0)) * HD + col];
+                }
+            }
+#pragma unroll
+            for (int it = 0; it < NIT; it++) {
+                const int item = tid_f + 256 * it, inst = item >> 7;
+                const int r0 = inst * FT, k0 = r0 >> 4, k1 = (r0 + FT - 1) >> 4;
+                float sum = 0.f;
+#pragma unroll
+                for (int kk = 0; kk < NCH; kk++) sum = k0 + kk <= k1 ? sum + pv[it][kk] : sum;
+                A.pooled[(size_t)inst0 * HD + item] = sum * invT;
+            }
+        } else
         for (int item = tid; item < ninst * HD; item += 256) {
             const int inst = item >> 7, col = item & (HD - 1);
             const int r0 = inst * T, k0 = r0 >> 4, k1 = (r0 + T - 1) >> 4;
@@ -1134,16 +1255,16 @@ __global__ __launch_bounds__(256) void k_gin_res(GinResArgs A)
             for (int kk = 0; kk < 5; kk++) sum = k0 + kk <= k1 ? sum + pv[kk] : sum;
             A.pooled[(size_t)inst0 * HD + item] = sum * invT;
         }
-        if (A.candidate && s_flag[1]) {                               // (malformed input) slots that share a row: copy from the slot that was written
+        if (have_cand && s_flag[1]) {                               // (malformed input) slots that share a row: copy from the slot that was written
             __threadfence();
             __syncthreads();
-            for (int i = wave; i < ninst * A.J; i += 4) {
-                const int cnd = A.candidate[(size_t)inst0 * A.J + i];
+            for (int i = wave; i < ninst * Jn; i += 4) {
+                const int cnd = A.candidate[(size_t)inst0 * Jn + i];
                 if (cnd < 0 || cnd >= T) continue;
-                const int win = s_rowcand[(i / A.J) * T + cnd];
+                const int win = s_rowcand[(i / Jn) * T + cnd];
                 if (win != i) {
-                    const float2 x = *reinterpret_cast<const float2 *>(A.cand_feat + ((size_t)inst0 * A.J + win) * HD + 2 * lane);
-                    *reinterpret_cast<float2 *>(A.cand_feat + ((size_t)inst0 * A.J + i) * HD + 2 * lane) = x;
+                    const float2 x = *reinterpret_cast<const float2 *>(A.cand_feat + ((size_t)inst0 * Jn + win) * HD + 2 * lane_f);
+                    *reinterpret_cast<float2 *>(A.cand_feat + ((size_t)inst0 * Jn + i) * HD + 2 * lane_f) = x;
                 }
             }
         }

@@ -210,6 +210,19 @@ class Encoder:
         capi.check(self.L.mtfjsp_encoder_peek_nodes_host(self.h, out.ctypes.data, out.size), self.h, enc=True)
         return out
 
+    def gin_res_kernel_name(self):
+        """the instantiation of the single-launch GIN kernel this handle's last forward ran (None: none yet)"""
+        name = self.L.mtfjsp_encoder_gin_res_kernel_name(self.h)
+        return name.decode() if name else None
+
+    def peek_gin_res(self):
+        """diagnostic: (cand_feat [B*J,128] f32, statistics words [6,8,128,2] u64, (time-out, range) words) of the last single-launch GIN forward"""
+        cand = np.empty((self.B * self.J, 128), dtype=np.float32)
+        stats = np.empty((6, 8, 128, 2), dtype=np.uint64)
+        flags = np.zeros(2, dtype=np.uint32)
+        capi.check(self.L.mtfjsp_encoder_peek_gin_res_host(self.h, cand.ctypes.data, cand.size, stats.ctypes.data, flags.ctypes.data), self.h, enc=True)
+        return cand, stats, flags
+
     def range_fallbacks(self):
         """-> (times the handle left the f16 split products because an activation exceeded their range, product mode in force)"""
         n, m = C.c_int64(0), C.c_int32(0)

@@ -538,6 +538,21 @@ int mtfjsp_encoder_range_fallbacks(mtfjsp_encoder_t e, int64_t *count_out, int32
  * written by the separate GAT launches (k_gat3x, k_headsx_gat3x) and by the global critic; the three-in-one launch keeps its node
  * rows in LDS (round 6) and leaves the buffer alone unless MTFJSP_FUSED3_NODES_HBM=1. */
 int mtfjsp_encoder_peek_nodes_host(mtfjsp_encoder_t e, float *out_host, int64_t count);
+/* Which instantiation of the single-launch GIN kernel serves a forward — the library's one statement of the rule (csrc/mtfjsp_gin_res_select.h; every
+ * launch goes through it).  No GPU involved.  batch instances of rows_per_instance (= n_job * n_machine) node rows on num_cu compute units; n_job bounds
+ * the candidate table; candidates = candidates per instance of the forward (n_job for the job actor, 0 for the global critic); node_output != 0 when
+ * the node embeddings are requested.  "k_gin_res_t36j6x16" — the body compiled for T = 36, J = 6, 16 instances in every workgroup, no node output —
+ * serves exactly that shape (batch a multiple of 16 with ceil(batch / num_cu) == 16); "k_gin_res", the same body with the shape read at run time, everything
+ * else that is eligible; NULL where the shape is not eligible for the single launch (the streaming launches run).  MTFJSP_GIN_RES_GENERIC=1 in the
+ * environment (read per call, by the launches too) forces "k_gin_res": A/B runs and the parity test.  *ipc_out / *grid_out (may be NULL): instances per
+ * workgroup and workgroups.  mtfjsp_encoder_gin_res_kernel_name: the instantiation the handle's last single-launch forward ran (NULL: none yet). */
+const char *mtfjsp_gin_res_kernel_name_for(int32_t batch, int32_t rows_per_instance, int32_t n_job, int32_t candidates, int32_t num_cu,
+                                           int32_t node_output, int32_t *ipc_out, int32_t *grid_out);
+const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e);
+/* diagnostic (tests): what the handle's last single-launch GIN forward left, copied to host memory after synchronising the stream — the first `count`
+ * floats of the candidate rows [B*J,128]; the 6 x 8 x 128 x 2 count-carrying statistics words of its six boundaries (csrc/mtfjsp_gin_resident.h,
+ * gr_fix_encode); the (time-out, range) words.  Any of the three pointers may be NULL. */
+int mtfjsp_encoder_peek_gin_res_host(mtfjsp_encoder_t e, float *cand_feat_host, int64_t count, uint64_t *stats_host, uint32_t *flags_host);
 /* number of statistics-exchange time-outs of the single-launch kernels reported on this handle so far */
 int mtfjsp_encoder_resident_failures(mtfjsp_encoder_t e, int64_t *count_out);
 int mtfjsp_encoder_timing_begin(mtfjsp_encoder_t e);
