@@ -45,6 +45,7 @@ def lib():
         L.or_batch_job_mask_state.argtypes = [C.c_void_p, _ip, _bp]
         L.or_batch_state.argtypes = [C.c_void_p, _ip, _bp, _dp, _dp, _ip, _dp, _dp]
         L.or_batch_valid_action_mask.argtypes = [C.c_void_p, _bp]
+        L.or_batch_ties.argtypes = [C.c_void_p, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")]
         L.or_batch_bench.restype = C.c_long
         L.or_batch_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.or_batch_bench_blocks.restype = C.c_long
@@ -159,6 +160,13 @@ class OracleBatch:
         if n < 0:
             raise ValueError("or_batch_bench_blocks: n_job > 64")
         return n, s1.value, s2.value
+
+    def ties(self):
+        """[B,3] decisive ties per instance since its last reset, at the three comparisons that choose the scheduling path:
+        lb_ft == arrival(first), lb_ft == arrival(next) with a gap that fits, gap == duration"""
+        out = np.zeros((self.B, 3), np.int64)
+        self.L.or_batch_ties(self.h, out)
+        return out
 
     def valid_action_mask(self):
         m = np.zeros((self.B, self.T), np.uint8)

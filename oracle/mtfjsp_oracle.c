@@ -56,6 +56,10 @@ typedef struct {
     double *st_e, *ft_e, *pt_e;    /* [T] last estimate */
     double last_rewards[5];
     int last_path;                 /* 0 empty,1 front,2 between,3 append,-1 invalid */
+    /* decisive ties of schedule()'s three comparisons since the last reset — places where flipping that comparison alone
+     * (<= for <, > for >=, < for <=) changes the branch: lb_ft == f_st ; lb_ft == nst with gap >= d ; gap == d.
+     * Counted only: nothing reads them back into a result */
+    long ties[3];
     /* A8 scaler */
     double sc_R[4], sc_mean[4], sc_S[4], sc_std[4];
     long sc_n;
@@ -297,6 +301,7 @@ void or_env_reset(Env *e, const double *w3)
     e->trans_prev = e->idle_prev = 0.0;
     e->last_path = -1;
     for (int i = 0; i < 5; i++) e->last_rewards[i] = 0.0;
+    e->ties[0] = e->ties[1] = e->ties[2] = 0;
 }
 
 /* ---------------------------------------------------------------- A3 schedule (env:1476-1685) */
@@ -343,6 +348,7 @@ static int schedule(Env *e, int k, int m, double d)
     double lb_ft = lb_st + d;
     int f = r[0];
     double f_st = arrival(e, f);
+    if (lb_ft == f_st) e->ties[0]++;
     if (lb_ft <= f_st) {                                         /* env:1548-1576 */
         insert_front(e, k, m);
         double x = tr(e, k, f);
@@ -356,6 +362,8 @@ static int schedule(Env *e, int k, int m, double d)
         double nst = arrival(e, N);
         if (lb_ft > nst) continue;
         double gap = nst - e->h.ft[P];
+        if (lb_ft == nst && gap >= d) e->ties[1]++;
+        if (gap == d) e->ties[2]++;
         if (gap < d) continue;
         double a = arrival(e, k);
         double x = tr(e, P, k);
@@ -700,6 +708,11 @@ void or_batch_state(Batch *b, int *mach, unsigned char *sched, double *st, doubl
         or_env_state(b->env[i], mach + (long)i * T, sched + (long)i * T, st + (long)i * T, ft + (long)i * T, routes + (long)i * M * T, prev4 + i * 4);
         if (scaler17) or_scaler_state(b->env[i], scaler17 + i * 17);
     }
+}
+/* decisive ties per env since its last reset: [B*3] = front test, next-arrival test, gap test (see Env.ties) */
+void or_batch_ties(Batch *b, long *out)
+{
+    for (int i = 0; i < b->B; i++) for (int k = 0; k < 3; k++) out[i * 3 + k] = b->env[i]->ties[k];
 }
 void or_batch_valid_action_mask(Batch *b, unsigned char *mask)
 {

@@ -17,6 +17,9 @@ What is pinned:
          random-init weights), training-mode BatchNorm
   N4     Instance_Dataset generator stream (legacy numpy RNG)
 
+  ties   the same outputs on small-integer times (tests/env_parity.py::integer_data), where the three comparisons that choose
+         the scheduling path meet exact equality
+
 Usage:  python oracle/ref_harness/gen_golden.py [--only NAME] [--out DIR]
 """
 import argparse
@@ -33,6 +36,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(HERE, "..", "..", "tests"))
+sys.path.insert(0, os.path.join(HERE, "..", ".."))
 from bootstrap import bootstrap, default_config, AttrDict  # noqa: E402
 
 REF = bootstrap(models=True)
@@ -113,7 +118,9 @@ def scaler_state(s):
 
 def run_trace(ins, n_job, n_machine, n_edge, B, episodes, policy, left_shift=True,
               act_seed=0, w_seed=0, keep_every=1):
-    """Drive the reference exactly like Run.py does, with a scripted policy."""
+    """Drive the reference exactly like Run.py does, with a scripted policy.  policy="blocks": the mask-free action stream of
+    tests/env_parity.py::Actions (a job is kept for a run of steps, else redrawn among the unfinished ones with p = 0.3; all
+    randomness drawn up front), checked here against the reference's own candidate bookkeeping."""
     J, M, T = n_job, n_machine, n_job * n_machine
     cfg = default_config(J, M, n_edge, B)
     t_all, p_all, tt_all, edge_all = [np.asarray(x[:B]) for x in ins]
@@ -159,12 +166,19 @@ def run_trace(ins, n_job, n_machine, n_edge, B, episodes, policy, left_shift=Tru
                                   "raw_rewards", "cand", "mask", "mach", "sched", "st", "ft", "routes", "prev",
                                   "scaler", "vmask")}
         kept = []
+        if policy == "blocks":
+            from env_parity import Actions
+            scripted = Actions("blocks", rs, J, M, B, feas)
         for step in range(T):
             # ---- scripted policy
             remaining = np.array([[d[j] for j in range(J)] for d in ppo.remaining_m_batch])
             job_a = np.zeros(B, np.int64)
             m_a = np.zeros(B, np.int64)
-            for b in range(B):
+            if policy == "blocks":
+                jb, tb, mb = scripted.next(step, None, None)
+                assert (remaining[np.arange(B), jb] > 0).all() and np.array_equal(cand[np.arange(B), jb], tb)
+                job_a[:], m_a[:] = jb, mb
+            for b in range(0 if policy == "blocks" else B):      # the policies that draw from the reference's bookkeeping
                 if policy == "free":
                     ok = np.flatnonzero(remaining[b] > 0)
                 else:
@@ -332,6 +346,10 @@ def encoder_vectors(ins, weights, B=16, steps=(0, 17), seed=0, size=(6, 6, 2), k
     return out
 
 
+# name: J, M, B, generator seed, action seed, keep_every
+TIE_TRACES = {"trace_j6m6e2_int_b8_blocks": (6, 6, 8, 21, 1, 1), "trace_j10m10e2_int_b2_blocks": (10, 10, 2, 22, 2, 5)}
+
+
 # ------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -401,6 +419,16 @@ def main():
         d, sp = run_trace(ins, 20, 20, 4, 1, episodes=1, policy="free", act_seed=7, w_seed=7, keep_every=20)
         speed["J20M20E4_B1"] = sp
         save("trace_j20m20e4_b1_free", d)
+    if want("ties"):
+        # integer times: exact ties at the three comparisons that choose the scheduling path (env:1548, 1587-1604).  The action
+        # seeds are the first for which the oracle's counters (OracleBatch.ties) see each of the three kinds in each trace;
+        # tests/test_env_insertions_cpu.py asserts it
+        from env_parity import integer_data
+        for name, (j, m, b, gen_seed, act_seed, every) in TIE_TRACES.items():
+            t_, p_, tt_, edge_ = ref_generate(b, j, m, 2, gen_seed)
+            ins = list(integer_data(t_, p_, tt_)) + [edge_]
+            d, _ = run_trace(ins, j, m, 2, b, episodes=1, policy="blocks", act_seed=act_seed, w_seed=act_seed, keep_every=every)
+            save(name, d)
     if want("enc"):
         save("encoder_j6m6e2_top1", encoder_vectors(ev, "top1"))
         save("encoder_j6m6e2_rand", encoder_vectors([x[50:] for x in ev], "rand", B=8, steps=(0, 9), seed=123))

@@ -7,6 +7,14 @@ row stays wrong until that job acts again: a comparison at a few steps can miss 
 The dtype contract (tests/test_env_hip_golden.py): with obs_dtype="f32" tasks_fea, m_fea2 and m_fea1 are float32 and np.array_equal to
 oracle_f64.astype(np.float32) — round to nearest, what actor_critic.py:143's `.float()` does; everything else stays f64 / integer and
 bit-equal.  With "f64" every float is bit-equal.  No tolerance appears anywhere.
+
+Two parameters choose what the kernels are shown.  policy: "mask" draws the job from the unmasked jobs — the round-robin job mask
+keeps all jobs in lockstep, so an operation almost never fits before or between the operations already on its machine; "blocks" and
+"jobseq" ignore the mask (any job with operations left, as the reference's `free` traces do) and send 4 to 13 % of all steps down the
+front insertion and 21 to 50 % down the gap insertion.  data: "generated" times are products of uniform doubles and never equal;
+"integer" times (integer_data) tie everywhere, which is the only input on which `<=` differs from `<` in the three comparisons that
+choose the scheduling path.  oracle_walk runs the oracle alone over the same instances and actions: tests/test_env_insertions_cpu.py
+uses it to prove that a case reaches what it is about.
 """
 import os
 from importlib import import_module
@@ -44,6 +52,101 @@ def random_valid(rs, cand, mask, feas):
     return job, task, mach
 
 
+POLICIES = ("mask", "blocks", "jobseq")
+DATA = ("generated", "integer")
+
+
+def integer_data(t, p, tt):
+    """small-integer times from a generated instance: durations 1..9 and powers with the sign (negative = infeasible machine)
+    kept, transport floor(tt/7) — still symmetric with a zero diagonal, zero between some different machines.  Every value is
+    exact in float32"""
+    ti = np.sign(t) * np.ceil(np.abs(t) * 9 / 120)
+    pi = np.sign(p) * np.ceil(np.abs(p) / 6)
+    return ti, pi, np.floor(tt / 7)
+
+
+def parity_instances(J, M, E, B, seed, data="generated"):
+    """the instances of a run_parity case: -> t, p, tt, edge"""
+    import mtfjsp_amd  # noqa: F401
+    inst = import_module("e2e-mappo-for-mt-fjsp_amd.instances")
+    assert data in DATA
+    t, p, tt, edge = inst.generate_instances(B, J, M, E, seed=1000 * seed + J * 100 + M)
+    if data == "integer":
+        t, p, tt = integer_data(t, p, tt)
+    return t, p, tt, edge
+
+
+class Actions:
+    """the action stream of one episode.  "mask": random_valid on the shared RandomState, as before.  The mask-free policies keep
+    their own per-job counters (task = job * M + done[job]) and take all randomness from one array U[T, B, 3] of random_sample drawn
+    up front — column 0 the redraw decision, 1 the job, 2 the machine, index = int(U * len(choices)) — so that no instance's state
+    reaches another instance's actions (rs.choice consumes a state-dependent number of words).
+    "blocks": the previous job is kept while it has operations left, except with probability 0.3, or at step 0, a job is drawn
+    uniformly among the unfinished ones.  "jobseq": a per-instance random permutation of the jobs, each finished before the next"""
+
+    def __init__(self, policy, rs, J, M, B, feas):
+        assert policy in POLICIES
+        self.policy, self.rs, self.J, self.M, self.B, self.feas = policy, rs, J, M, B, feas
+        if policy != "mask":
+            self.U = rs.random_sample((J * M, B, 3))
+            self.done = np.zeros((B, J), np.int64)
+            self.prev = np.full(B, -1, np.int64)
+            self.order = np.argsort(self.U[:J, :, 1], axis=0, kind="stable").T     # [B, J]: jobseq's permutations
+
+    def next(self, s, cand, mask):
+        """-> job, task, machine [B] int32 of step s; cand, mask: the oracle's candidate and job mask (read by "mask" only)"""
+        if self.policy == "mask":
+            return random_valid(self.rs, cand, mask, self.feas)
+        B, M, U, done = self.B, self.M, self.U[s], self.done
+        job = np.zeros(B, np.int32)
+        for b in range(B):
+            if self.policy == "jobseq":
+                job[b] = self.order[b, s // M]
+            elif s == 0 or done[b, self.prev[b]] == M or U[b, 0] < 0.3:
+                ok = np.flatnonzero(done[b] < M)
+                job[b] = ok[int(U[b, 1] * len(ok))]
+            else:
+                job[b] = self.prev[b]
+        ar = np.arange(B)
+        task = (job * M + done[ar, job]).astype(np.int32)
+        mach = np.zeros(B, np.int32)
+        for b in range(B):
+            fm = np.flatnonzero(self.feas[b, task[b]])
+            mach[b] = fm[int(U[b, 2] * len(fm))]
+        done[ar, job] += 1
+        self.prev = job.astype(np.int64)
+        return job, task, mach
+
+
+def oracle_walk(J, M, E, B, left_shift=True, episodes=1, seed=0, policy="mask", data="generated"):
+    """the oracle alone over run_parity's instances and actions (no device, no reset_episode): -> dict of paths [episodes, T, B],
+    ties [episodes, B, 3] (OracleBatch.ties at each episode's end) and actions [episodes, T, B, 3] = job, task, machine"""
+    from oracle.env_oracle import OracleBatch
+    T = J * M
+    t, p, tt, edge = parity_instances(J, M, E, B, seed, data)
+    feas = t >= 0
+    rs = np.random.RandomState(seed)
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift)
+    orc.scaler_init()
+    paths, ties, actions = [], [], []
+    for ep in range(episodes):
+        w3 = rs.dirichlet([1, 1, 1], B)
+        if ep > 0:
+            orc.scaler_reset_returns()
+        orc.reset(w3)
+        cand, mask = orc.job_mask_state()
+        act = Actions(policy, rs, J, M, B, feas)
+        for s in range(T):
+            job, task, mach = act.next(s, cand, mask)
+            info, _, pth = orc.step(task, mach)
+            cand, mask = orc.job_mask_update(job)
+            paths.append(pth); actions.append(np.stack([job, task, mach], 1))
+        assert info[:, 1].all()
+        ties.append(orc.ties())
+    return dict(paths=np.array(paths).reshape(episodes, T, B), ties=np.array(ties),
+                actions=np.array(actions, np.int32).reshape(episodes, T, B, 3))
+
+
 def _same(got, want, what):
     got, want = np.asarray(got), np.asarray(want)
     assert got.dtype == want.dtype, f"{what}: dtype {got.dtype}, expected {want.dtype}"
@@ -55,17 +158,17 @@ def _same(got, want, what):
 
 
 def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force=None, monkeypatch=None, expect_kernel=None,
-               second_reset="reset"):
-    """-> number of compared steps.  force: MTFJSP_ENV_KERNEL for the handle's launches (needs monkeypatch).  expect_kernel: the kernel
+               second_reset="reset", policy="mask", data="generated"):
+    """-> number of compared steps.  policy, data: the action stream and the instance times (module docstring).
+    force: MTFJSP_ENV_KERNEL for the handle's launches (needs monkeypatch).  expect_kernel: the kernel
     the case is about; asserted against the dispatch.  second_reset: how episodes after the first begin — "reset" (scaler_reset_returns
     + reset with fresh weights) or "reset_episode" (the one-launch form; the weights it draws are fed to the oracle's reset).  Every
     later reset runs over the terminal state of the episode before: it must rewrite every row of a dirty observation buffer."""
     import mtfjsp_amd  # noqa: F401
     batch_env = import_module("e2e-mappo-for-mt-fjsp_amd.batch_env")
-    inst = import_module("e2e-mappo-for-mt-fjsp_amd.instances")
     capi = import_module("e2e-mappo-for-mt-fjsp_amd.capi")
     from oracle.env_oracle import OracleBatch
-    assert obs_dtype in ("f32", "f64") and second_reset in ("reset", "reset_episode")
+    assert obs_dtype in ("f32", "f64") and second_reset in ("reset", "reset_episode") and policy in POLICIES and data in DATA
     if monkeypatch is not None:
         for k in _SELECTION_VARS:
             monkeypatch.delenv(k, raising=False)
@@ -75,12 +178,12 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
         assert not force and not any(os.environ.get(k) for k in _SELECTION_VARS), "forcing a kernel needs monkeypatch"
     T = J * M
     odt = np.float32 if obs_dtype == "f32" else np.float64
-    case = f"J{J}M{M}E{E} B={B} {obs_dtype} force={force} left_shift={left_shift}"
+    case = f"J{J}M{M}E{E} B={B} {obs_dtype} force={force} left_shift={left_shift} policy={policy} data={data}"
 
     def obs(x):                                      # the oracle's f64 observation in the handle's observation type
         return np.asarray(x, np.float64).astype(odt)
 
-    t, p, tt, edge = inst.generate_instances(B, J, M, E, seed=1000 * seed + J * 100 + M)
+    t, p, tt, edge = parity_instances(J, M, E, B, seed, data)
     feas = t >= 0
     rs = np.random.RandomState(seed)
     env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=left_shift, obs_dtype=obs_dtype)
@@ -114,9 +217,10 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
         check_observation(o, tag)
         cand, mask = orc.job_mask_state()
         _same(env.candidate.cpu().numpy(), cand, tag + " candidate"); _same(env.job_mask.cpu().numpy(), mask, tag + " job_mask")
+        act = Actions(policy, rs, J, M, B, feas)
         for s in range(T):
             tag = f"{case} episode {ep} step {s}"
-            job, task, mach = random_valid(rs, cand, mask, feas)
+            job, task, mach = act.next(s, cand, mask)
             mm = ~feas[np.arange(B), task]
             mf1 = env.observe_mfea1(task, mm).cpu().numpy()               # before the step, with the machine mask (run:258-259)
             _same(mf1, obs(orc.mfea1(task, mm, o["tfea"])), tag + " m_fea1")

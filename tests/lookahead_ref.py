@@ -45,28 +45,40 @@ def model_step(t, p, tt, edge, w3, prefix, column, left_shift=True, w_cfg=(0.4, 
     return task_c[np.arange(B), pick].astype(np.int32), mm[pick].astype(np.int32), best, values, valid
 
 
-def model_episode(t, p, tt, edge, w3, column, left_shift=True, w_cfg=(0.4, 0.4, 0.2)):
-    """-> (task[T,B], mach[T,B], best[T,B]): the model's whole episode"""
+def model_episode(t, p, tt, edge, w3, column, left_shift=True, w_cfg=(0.4, 0.4, 0.2), shared=None):
+    """-> (task[T,B], mach[T,B], best[T,B]): the model's whole episode.  shared: a list that receives, per step, how many
+    instances had their maximum at more than one counting replica (the decisions that "first index" made)"""
     T = np.asarray(t).shape[1]
     prefix, best = [], []
     for _ in range(T):
-        a, m, b, _, _ = model_step(t, p, tt, edge, w3, prefix, column, left_shift, w_cfg)
+        a, m, b, values, valid = model_step(t, p, tt, edge, w3, prefix, column, left_shift, w_cfg)
         prefix.append((a, m)); best.append(b)
+        if shared is not None:
+            shared.append(int(((valid & (values == b[:, None])).sum(1) > 1).sum()))
     return np.stack([x[0] for x in prefix]), np.stack([x[1] for x in prefix]), np.stack(best)
 
 
 CONFIG_W = (0.4, 0.4, 0.2)
 
 
+SHARED_MAXIMA = {}                    # cached_episode's arguments -> decisions of that episode whose maximum several replicas shared
+
+
 @functools.lru_cache(maxsize=None)
-def cached_episode(J, M, E, B, column, left_shift):
-    """the model's episode on the test instances of a shape, computed once per session and shared; reward weights = CONFIG_W"""
+def cached_episode(J, M, E, B, column, left_shift, data="generated"):
+    """the model's episode on the test instances of a shape, computed once per session and shared; reward weights = CONFIG_W.
+    data="integer": the same instances with small-integer times (env_parity.integer_data), where replicas tie"""
     from importlib import import_module
     import mtfjsp_amd  # noqa: F401
     inst = import_module("e2e-mappo-for-mt-fjsp_amd.instances")
     t, p, tt, edge = inst.generate_instances(B, J, M, E, seed=4200 + J * 100 + M)
+    if data == "integer":
+        from env_parity import integer_data
+        t, p, tt = integer_data(t, p, tt)
     w3 = np.tile(np.array([CONFIG_W]), (B, 1))
-    task, mach, best = model_episode(t, p, tt, edge, w3, column, left_shift, CONFIG_W)
+    shared = []
+    task, mach, best = model_episode(t, p, tt, edge, w3, column, left_shift, CONFIG_W, shared)
+    SHARED_MAXIMA[(J, M, E, B, column, left_shift, data)] = sum(shared)
     for x in (t, p, tt, edge, w3, task, mach, best):
         x.setflags(write=False)
     return (t, p, tt, edge, w3), task, mach, best

@@ -25,10 +25,24 @@ def _mods():
 @pytest.mark.parametrize("column", range(5))
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_every_decision_of_the_episode_equals_the_model(shape, column):
+    _every_decision(shape, column, "generated")
+
+
+@pytest.mark.parametrize("column", range(5))
+def test_every_decision_on_integer_times_equals_the_model(column):
+    """J6M6 x 5 with small-integer times (env_parity.integer_data), left shift on: many candidates promise the same value, and the
+    selection has to break the tie as the model does — the lowest index.  The forked copies also take the insertion paths on exact
+    ties.  Against the host model, as above; there is no reference fixture for this case"""
+    _every_decision("J6M6", column, "integer")
+    J, M, E, B = SHAPES["J6M6"]
+    assert ref.SHARED_MAXIMA[(J, M, E, B, column, True, "integer")] >= B, "the model's maxima must be shared ones"
+
+
+def _every_decision(shape, column, data):
     batch_env, baselines, capi = _mods()
     J, M, E, B = SHAPES[shape]
     T = J * M
-    (t, p, tt, edge, w3), task, mach, best = ref.cached_episode(J, M, E, B, column, True)
+    (t, p, tt, edge, w3), task, mach, best = ref.cached_episode(J, M, E, B, column, True, data)
     env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=True, obs_dtype="f32", w_cfg=ref.CONFIG_W)
     env.load_instances(t, p, tt, edge=edge); env.scaler_init(); env.reset(w3)
     la = baselines.Lookahead(env)

@@ -91,10 +91,30 @@ def test_full_size_all_rules_in_one_batch(J, M, E, N):
     """(6) host-generated instances (with infeasible machines), B = 12 N: plans equal the restatement on every instance, every
     planned machine is feasible, no invalid / infeasible status, done after exactly T steps; every 8th instance's final costs
     and path words equal the CPU environment without left shift."""
+    t, p, tt, edge = instances.generate_instances(N, J, M, E, seed=31)
+    _all_rules_in_one_batch(J, M, E, N, t, p, tt, edge, every=8)
+
+
+def test_integer_times_break_argmin_and_argmax_ties_at_the_first_index():
+    """small-integer times (env_parity.integer_data): the minimum of a task's row is shared by several machines in about half of
+    all rows, and some jobs start with the same total work, so SPT / SEC and the work-remaining rules decide by "first index" —
+    which generated times, products of uniform doubles, never ask of them.  J6M6 x 64, all 12 rules, every instance against the
+    restatement and the CPU environment (no reference fixture: the restatement is the yardstick, as at full size)"""
+    from env_parity import integer_data
+    J, M, E, N = 6, 6, 2, 64
+    t, p, tt, edge = instances.generate_instances(N, J, M, E, seed=31)
+    t, p, tt = integer_data(t, p, tt)
+    for x in (np.where(t < 0, np.inf, t), np.where(t < 0, np.inf, t * np.abs(p))):         # SPT, SEC: a shared row minimum
+        assert ((x == x.min(-1, keepdims=True)).sum(-1) > 1).mean() > 0.1
+    refer = np.sum(ref.task_values(t, p, 2).reshape(N, J, M), axis=2)                       # jobs with the same total work
+    assert any(len(set(r)) < J for r in refer.tolist())
+    _all_rules_in_one_batch(J, M, E, N, t, p, tt, edge, every=1)
+
+
+def _all_rules_in_one_batch(J, M, E, N, t, p, tt, edge, every):
     import torch
     from oracle.env_oracle import OracleBatch          # checker
     T, B = J * M, 12 * N
-    t, p, tt, edge = instances.generate_instances(N, J, M, E, seed=31)
     assert (t < 0).any(), "the set must contain infeasible machines"
     rng = np.random.RandomState(5)
     mor = np.stack([np.stack([rng.permutation(J) for _ in range(M)]) for _ in range(N)]).astype(np.int32)
@@ -112,7 +132,7 @@ def test_full_size_all_rules_in_one_batch(J, M, E, N):
     assert len(bad) == 0
     assert np.array_equal(np.sort(task, 1), np.tile(np.arange(T), (B, 1))), "every task exactly once"
     assert (tb[np.arange(B)[:, None], task, mach] > 0).all(), "a planned machine cannot process its task"
-    sub = np.arange(0, B, 8)
+    sub = np.arange(0, B, every)
     orc = OracleBatch(tb[sub], pb[sub], ttb[sub], eb[sub], left_shift=False)
     orc.scaler_init()
     orc.reset(w3[sub])

@@ -8,7 +8,9 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TRACES = ["trace_j6m6e2_train16_mask", "trace_j6m6e2_eval16_free", "trace_j6m6e2_eval8_sticky",
           "trace_j6m6e2_eval4_noleftshift", "trace_j10m6e2_b3_free", "trace_j10m10e2_b2_free",
-          "trace_j10m10e2_b2_mask", "trace_j20m20e4_b1_free"]
+          "trace_j10m10e2_b2_mask", "trace_j20m20e4_b1_free",
+          # integer times, mask-free "blocks" actions: exact ties at the three comparisons that choose the scheduling path
+          "trace_j6m6e2_int_b8_blocks", "trace_j10m10e2_int_b2_blocks"]
 
 
 def load(name):
