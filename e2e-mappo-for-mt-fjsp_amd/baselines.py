@@ -401,3 +401,43 @@ def beam_baselines(t, p, tt, edge, args, rules=BEAM_RULES, width=8, dedupe=True,
         plans[name] = (task, mach)
     out[PLANS] = plans
     return out
+
+
+# ---- the random dispatch rule as best-of-K (csrc/mtfjsp_group.hip): K uniformly random episodes per instance, the best kept
+RANDOM_BEST, RANDOM_MEAN = "RANDOM_BEST", "RANDOM_MEAN"
+
+
+class _RandomPolicy:
+    """`evaluate.best_of_k_rollout`'s policy without an encoder: `env.random_actions` (a uniform unmasked job, a uniform feasible
+    machine; Philox keyed by (seed, step, index of the copy inside the handle))"""
+
+    def __init__(self, seed):
+        self.seed = int(seed)
+
+    def open(self, batch):
+        pass
+
+    def begin(self):
+        pass
+
+    def decide(self, env, s, task_row, mach_row, job):
+        env.random_actions(self.seed, s, task_row, mach_row, job)
+
+    def close(self):
+        pass
+
+
+def random_baselines(t, p, tt, edge, args, K=1, seed=0, device=0, obs_dtype="f32", left_shift=False, chunk=None):
+    """The random dispatch rule on the N instances t, p [N,T,M], tt [N,M,M], edge [N,E,M/E] (args as for `pdr_baselines`): K random
+    episodes per instance side by side — the K-copy handle, final costs, best copy and fork of `evaluate.sample_best_of_k`, with the
+    actions of `DeviceBatchEnv.random_actions(seed, step)` in place of the actors.  The stream is keyed by a copy's index inside
+    the handle: the results are a function of (seed, K, chunk), chunk = instances per pass (None: all N).
+    -> {"RANDOM_BEST": (cost_dict_cumsum, Final_4cost, Objective) of every instance's best episode (smallest Objective, lowest copy
+    on ties), "RANDOM_MEAN": the same three as means over the K episodes (taken on the host)} in `pdr_baselines`' layout, and under
+    PLANS {"RANDOM_BEST": (task[N,T], mach[N,T])}."""
+    from .evaluate import COST_KEYS, best_of_k_rollout
+    r = best_of_k_rollout(t, p, tt, edge, args, K, _RandomPolicy(seed), chunk=chunk, device=device, obs_dtype=obs_dtype, left_shift=left_shift,
+                          what="random-rule")
+    mean_cost = {key: r["cum"][:, :, i].mean(axis=1) for i, key in enumerate(COST_KEYS)}
+    return {RANDOM_BEST: r["best"], RANDOM_MEAN: (mean_cost, r["final4"].mean(axis=1), r["obj"].mean(axis=1)),
+            PLANS: {RANDOM_BEST: r["plans"]}}

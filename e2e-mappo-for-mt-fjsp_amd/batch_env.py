@@ -140,6 +140,51 @@ class DeviceBatchEnv:
         capi.check(self.L.mtfjsp_state_signature(self.h, out.data_ptr()), self.h)
         return out
 
+    # ---- groups of copies (csrc/mtfjsp_group.hip): best-of-K evaluation on the fork
+    def final_costs(self, out=None, done=None):
+        """-> (cost4 [B,4] f64, done [B] uint8) device tensors: makespan, processing energy / T, transport time, idle time of every
+        instance's schedule as it stands (`validate_cost_batched`'s Final_4cost, formed on the device) and whether all T
+        operations are scheduled (mtfjsp_final_costs: one launch, nothing read back)"""
+        if out is None:
+            out = torch.empty(self.B, 4, dtype=torch.float64, device=self.device)
+        if done is None:
+            done = torch.empty(self.B, dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.shape == (self.B, 4)
+        assert done.is_cuda and done.dtype == torch.uint8 and done.is_contiguous() and done.shape == (self.B,)
+        capi.check(self.L.mtfjsp_final_costs(self.h, out.data_ptr(), done.data_ptr()), self.h)
+        return out, done
+
+    def group_reduce(self, N, K, cost4, done, w_cfg, obj=True, best=True, best_obj=True, front=True):
+        """N groups of K copies (copy c of group n = element n*K + c of cost4 [N*K,4] f64 and done [N*K] uint8, device tensors
+        from any source; this handle gives the device and the stream only).  w_cfg = (w_mk, w_ec, w_tt).  A copy is eligible iff
+        done and none of its three objectives (makespan, energy + idle, transport) is NaN.
+        -> (obj [N*K] f64: w_mk*mk + w_ec*ec + w_tt*tt in `validate_cost_batched`'s order, NaN where not eligible;
+            best [N] int32: n*K + c of the eligible copy with the smallest obj, lowest c on ties, -1 without one;
+            best_obj [N] f64: its obj, NaN without one;
+            front [N*K] uint8: 1 iff eligible and not dominated inside its group, of exact duplicates the lowest c)
+        device tensors; an output switched off (False) is None and is not computed.  An output may also be given as a tensor to
+        write into.  1 <= K <= 4096.  One launch (mtfjsp_group_reduce), nothing read back."""
+        N, K = int(N), int(K)
+        assert cost4.is_cuda and cost4.dtype == torch.float64 and cost4.is_contiguous() and cost4.numel() == N * K * 4
+        assert done.is_cuda and done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == N * K
+        dev = self.device
+
+        def buf(x, n, dt):
+            if x is None or x is False:
+                return None
+            if x is True:
+                return torch.empty(n, dtype=dt, device=dev)
+            assert x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == n
+            return x
+        # (an out-of-range N or K is the library's MTFJSP_ERR_ARG; the buffers below are then never written)
+        obj = buf(obj, max(N * K, 0), torch.float64); best = buf(best, max(N, 0), torch.int32)
+        best_obj = buf(best_obj, max(N, 0), torch.float64); front = buf(front, max(N * K, 0), torch.uint8)
+        w = (C.c_double * 3)(*[float(x) for x in w_cfg])
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else None)     # noqa: E731
+        capi.check(self.L.mtfjsp_group_reduce(self.h, N, K, cost4.data_ptr(), done.data_ptr(), w, ptr(obj), ptr(best), ptr(best_obj),
+                                              ptr(front)), self.h)
+        return obj, best, best_obj, front
+
     def scaler_init(self):
         capi.check(self.L.mtfjsp_scaler_init(self.h), self.h)
 

@@ -82,6 +82,8 @@ PROTOTYPES = {
     "mtfjsp_state_signature": (_I, [_VP, _VP]),
     "mtfjsp_beam_select": (_I, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_beam_backtrack": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mtfjsp_final_costs": (_I, [_VP, _VP, _VP]),
+    "mtfjsp_group_reduce": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_export_dense_adj": (_I, [_VP, _VP]),
     "mtfjsp_export_dense_adj_host": (_I, [_VP, _VP]),
     "mtfjsp_valid_action_mask": (_I, [_VP, _VP]),

@@ -113,7 +113,7 @@ __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t 
     }
 }
 
-// host side: what the library's other translation units (mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip) see of a handle; defined in mtfjsp_env.hip
+// host side: what the library's other translation units (mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip) see of a handle; defined in mtfjsp_env.hip
 struct EnvHostView {
     int B, J, M, T, device_id;
     bool loaded;
@@ -125,6 +125,7 @@ struct EnvHostView {
     const TaskSD *sd;                  // [B,T] per-task records: start, duration
     const TaskPL *pl;                  // [B,T] per-task records: energy, route links
     mtfjsp_obs_t obs;                  // the bound observation (valid with obs_bound)
+    const double *scal;                // [B,SCAL_N] per-instance scalar state (slots above)
 };
 __attribute__((visibility("hidden"))) void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v);
 __attribute__((visibility("hidden"))) int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg);   // sets mtfjsp_last_error, returns code

@@ -77,3 +77,156 @@ def validate_cost_batched(weights, t, p, tt, edge, args, greedy=True, device=0, 
     final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
     obj = args["weight_mk"] * final4[:, 0] + args["weight_ec"] * (final4[:, 1] + final4[:, 3]) + args["weight_tt"] * final4[:, 2]
     return cost, final4, obj
+
+
+COST_KEYS = ("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")
+
+
+def best_of_k_rollout(t, p, tt, edge, args, K, policy, w3=None, chunk=None, device=0, obs_dtype="f32", left_shift=True, what="best-of-K",
+                      on_event=None):
+    """The K-copy rollout behind `sample_best_of_k` and `baselines.random_baselines`: N instances, K copies of each side by side in
+    one handle of n*K (n = chunk or N instances per pass; copy c of instance i = element i*K + c), every copy playing its own
+    episode with the actions `policy.decide(env, s, task_row, mach_row, job)` writes into row s of the [T, n*K] histories; then the final
+    costs, the best copy and the Pareto front per instance on the device (csrc/mtfjsp_group.hip) and a fork of the best copies into an
+    n-instance handle, from which their schedules are read.  policy: `open(batch)` once before the first pass, `begin()` at every
+    pass's reset, `decide(...)` per step, `close()` at the end.  on_event(event, env, first_instance, hist_task, hist_mach) (tests): called
+    with "reset" after every pass's reset and with "end" after its last step, the handle of copies and the [T, n*K] device histories.
+    -> the dict `sample_best_of_k` documents, plus `cum` [N,K,5]: every copy's summed raw rewards."""
+    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
+    T, K = J * M, int(K)
+    if not 1 <= K <= 4096:
+        raise ValueError("K must be 1..4096")
+    t = np.asarray(t, np.float64)
+    N = t.shape[0]
+    n = N if chunk is None else int(chunk)
+    if n < 1:
+        raise ValueError("chunk must be at least 1")
+    n = min(n, N)
+    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
+    scal = args.get("reward_scaling", {}) or {}
+    kw = dict(left_shift=left_shift, obs_dtype=obs_dtype, device=device, w_cfg=w, scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+    src = DeviceBatchEnv(J, M, E, N, **kw)
+    env = top = None
+    opened = False
+    parts = []
+    try:
+        src.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
+        dev = src.device
+        env = DeviceBatchEnv(J, M, E, n * K, **kw)                     # the copies
+        top = DeviceBatchEnv(J, M, E, n, **kw)                         # the best copy of every instance
+        policy.open(n * K)
+        opened = True
+        if w3 is None:
+            w3_all = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n * K, 1)
+        else:
+            w3_k = torch.as_tensor(np.ascontiguousarray(w3, np.float64), device=dev)
+            if tuple(w3_k.shape) != (K, 3):
+                raise ValueError("w3 must be [K,3]")
+            w3_all = w3_k.repeat(n, 1).contiguous()                     # copy c of every instance resets with w3[c]
+        copy_of = torch.arange(n * K, dtype=torch.int32, device=dev) // K
+        inst_of = torch.arange(n, dtype=torch.int32, device=dev)
+        hist_task = torch.empty(T, n * K, dtype=torch.int32, device=dev)
+        hist_mach = torch.empty(T, n * K, dtype=torch.int32, device=dev)
+        job = torch.zeros(n * K, dtype=torch.int32, device=dev)
+        cum = torch.empty(n * K, 5, dtype=torch.float64, device=dev)
+        bad = torch.empty(n * K, dtype=torch.int32, device=dev)
+        for lo in range(0, N, n):
+            m = min(n, N - lo)                                          # a last, smaller chunk is padded with copies of its last instance
+            env.fork_from(src, torch.clamp(copy_of + lo, max=N - 1), instance=True, state=False, obs=False)
+            top.fork_from(src, torch.clamp(inst_of + lo, max=N - 1), instance=True, state=False, obs=False)
+            env.scaler_init()                                           # the scaled components are produced but not used here
+            env.reset(w3_all)
+            policy.begin()
+            if on_event is not None:
+                on_event("reset", env, lo, hist_task, hist_mach)
+            cum.zero_(); bad.zero_()
+            for s in range(T):
+                policy.decide(env, s, hist_task[s], hist_mach[s], job)
+                env.step(hist_task[s], hist_mach[s])
+                bad |= env.status
+                cum += env.raw                                          # reward, r_mk, r_idle, r_pt, r_tt (env:1051-1171), unscaled
+            if on_event is not None:
+                on_event("end", env, lo, hist_task, hist_mach)
+            cost4, done = env.final_costs()
+            obj, best, best_obj, front = env.group_reduce(n, K, cost4, done, w)
+            top.fork_from(env, best, instance=False, state=True, obs=False)
+            pick = best.clamp(min=0).long()
+            best_cum, best_c4 = cum.index_select(0, pick), cost4.index_select(0, pick)
+            plan_t, plan_m = hist_task.index_select(1, pick).t().contiguous(), hist_mach.index_select(1, pick).t().contiguous()
+            torch.cuda.synchronize(dev)
+            if int((bad[:m * K] & capi.ST_INVALID).ne(0).sum().item()) != 0:
+                raise RuntimeError(f"{what} evaluation produced an invalid action")
+            if not bool(done[:m * K].all().item()) or int(best[:m].min().item()) < 0:
+                raise RuntimeError(f"{what} evaluation: an episode did not finish")
+            host = lambda x, k=m: x[:k].cpu().numpy()                   # noqa: E731
+            parts.append(dict(
+                best_copy=host(best).astype(np.int64) + lo * K, best_obj=host(best_obj), best_cum=host(best_cum), best_c4=host(best_c4),
+                obj=host(obj, m * K).reshape(m, K), final4=host(cost4, m * K).reshape(m, K, 4), front=host(front, m * K).reshape(m, K).astype(bool),
+                cum=host(cum, m * K).reshape(m, K, 5), plan_t=host(plan_t), plan_m=host(plan_m),
+                machine=top.read_state(capi.STATE_MACHINE)[:m], start=top.read_state(capi.STATE_START)[:m],
+                finish=top.read_state(capi.STATE_FINISH)[:m]))
+    finally:
+        if opened:
+            policy.close()
+        for e in (top, env, src):
+            if e is not None:
+                e.close()
+    r = {k: np.concatenate([x[k] for x in parts]) for k in parts[0]}
+    cost = {key: r["best_cum"][:, i] for i, key in enumerate(COST_KEYS)}
+    return {"best": (cost, r["best_c4"], r["best_obj"]), "best_copy": r["best_copy"], "obj": r["obj"], "final4": r["final4"],
+            "front": r["front"], "cum": r["cum"], "plans": (r["plan_t"], r["plan_m"]),
+            "schedule": {"machine": r["machine"], "start": r["start"], "finish": r["finish"]}}
+
+
+class _SampledPolicy:
+    """`best_of_k_rollout`'s policy: one `ActorPair` of the copies' batch with per-instance BatchNorm"""
+
+    def __init__(self, weights, J, M, greedy, seed, device, obs_dtype):
+        self.cfg, self.actor = (weights, J, M, greedy, seed, device, obs_dtype), None
+
+    def open(self, batch):
+        from . import encoder as enc_mod
+        weights, J, M, greedy, seed, device, obs_dtype = self.cfg
+        self.actor = enc_mod.ActorPair(J, M, batch, device=device, obs_dtype=obs_dtype, weights=weights, greedy=greedy, seed=seed)
+        self.actor.enc.set_bn_mode(True)
+
+    def begin(self):
+        self.actor.begin_episode()
+
+    def decide(self, env, s, task_row, mach_row, job):
+        self.actor.act(env, s, task_row, mach_row, job)                 # the actions land in the history rows: no copies
+
+    def close(self):
+        if self.actor is not None:
+            self.actor.enc.set_bn_mode(False)
+            self.actor.enc.close()
+
+
+def sample_best_of_k(weights, t, p, tt, edge, args, K, seed=0, greedy=False, w3=None, chunk=None, device=0, obs_dtype="f32",
+                     left_shift=True, on_event=None):
+    """Best-of-K evaluation of the policy: K schedules per instance drawn from the actors (`greedy=False`; the Philox sampler of
+    `ActorPair`, keyed by (seed, decision, index of the copy inside the handle)), the best of them kept — and, the policy being
+    conditioned on the preference weights, the Pareto front of the K (makespan, energy, transport) points of every instance.
+    The reference evaluates one greedy schedule per instance (validate.py:60-297).
+
+    weights, t, p, tt, edge, args: as for `validate_cost_batched`; N instances.  The instances are loaded once; a handle of n*K
+    copies (n = chunk or N instances per pass) takes its constants from them by the explicit-index fork, runs T decisions with
+    per-instance BatchNorm (a copy's forward does not depend on its neighbours), and the reductions over the copies run on the
+    device: only [n]- and [n*K]-sized scalars, the best plans and the n best schedules are read back per pass.
+    w3 [K,3]: copy c is reset with the preference w3[c] — what the policy sees in columns 9-11 of tasks_fea — instead of args'
+    weights; `best` and `obj` are measured with args' weights either way.
+    Reproducibility: the sampler is keyed by a copy's index INSIDE THE HANDLE, so the samples — and with them every result — are a
+    function of (seed, K, chunk), not of (seed, K) alone; the same (seed, K, chunk) gives the same results bit for bit.  With
+    greedy=True all K copies of an instance are the same schedule (K = 1 is `validate_cost_batched`).
+    Ties: the best copy is the lowest c among equal objectives; of exact duplicates only the lowest c is on the front.
+    -> dict:
+      best       (cost_dict_cumsum, Final_4cost [N,4], Objective [N]) of every instance's best copy, in `validate_cost_batched`'s layout
+      best_copy  [N] int64: i*K + c of that copy (an index into the flattened [N,K] arrays)
+      obj        [N,K] every copy's Objective;  final4 [N,K,4] its Final_4cost;  cum [N,K,5] its summed raw rewards
+      front      [N,K] bool: the copy is not dominated in (makespan, energy + idle, transport) by another copy of its instance
+      plans      (task [N,T], mach [N,T]) int32: the decisions of the best copy
+      schedule   {"machine" [N,T] int32, "start" [N,T], "finish" [N,T]}: the best copy's schedule
+    on_event: see `best_of_k_rollout` (tests)."""
+    policy = _SampledPolicy(weights, int(args["n_job"]), int(args["n_machine"]), greedy, seed, device, obs_dtype)
+    return best_of_k_rollout(t, p, tt, edge, args, K, policy, w3=w3, chunk=chunk, device=device, obs_dtype=obs_dtype, left_shift=left_shift,
+                             what="best-of-K", on_event=on_event)

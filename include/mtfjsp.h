@@ -299,6 +299,33 @@ int mtfjsp_beam_select(mtfjsp_handle_t scratch, mtfjsp_handle_t beam, int32_t W,
 int mtfjsp_beam_backtrack(mtfjsp_handle_t h, int32_t W, int32_t S, const int32_t *hist_from_slot, const int32_t *hist_task,
                           const int32_t *hist_mach, const int32_t *start_slot, int32_t *task_plan, int32_t *mach_plan);
 
+/* ------------------------------------------------------------------ groups of copies: final costs, best copy, Pareto front */
+/* Best-of-K evaluation keeps K copies of each of N instances in one handle of N*K (copy c of instance n = element n*K + c, made
+ * with mtfjsp_fork and the index i / K) and lets every copy play its own episode.  These two calls reduce the copies on the
+ * device; nothing per copy has to be read back.  The reference evaluates one schedule per instance (validate.py:60-297).
+ *
+ * mtfjsp_final_costs: cost4_out [batch,4] (device) = {makespan, processing energy / T, transport time, idle time} of every
+ * instance's schedule as it stands, from the previous-step costs (MTFJSP_STATE_PREV_COSTS) — what validate.py:277-287 forms on the
+ * host: one binary64 division, no other arithmetic.  done_out [batch] (device bytes, or NULL) = 1 where all T operations are
+ * scheduled, else 0.  One launch on h's stream.  A handle that was never reset: MTFJSP_ERR_STATE.
+ *
+ * mtfjsp_group_reduce: h gives the device and the stream only.  cost4 [N*K,4] and done [N*K] are device arrays (any source);
+ * w3cfg_host = three HOST doubles (w_mk, w_ec, w_tt), passed by value.  Per copy: mk = cost4[0], ec = cost4[1] + cost4[3],
+ * tt = cost4[2], obj = (w_mk*mk + w_ec*ec) + w_tt*tt in exactly this order, uncontracted (test_all.py:536-538).  A copy is ELIGIBLE
+ * iff done != 0 and none of mk, ec, tt is NaN.  Outputs (device; each may be NULL):
+ *   obj_out [N*K]       obj, NaN for an ineligible copy
+ *   best_out [N]        n*K + c of the eligible copy with the smallest obj, the lowest c among equal ones (comparisons only; an
+ *                       eligible copy whose obj is NaN — possible only with infinite costs — is never chosen); -1 if there is none
+ *   best_obj_out [N]    that copy's obj; NaN if there is none
+ *   front_out [N*K]     1 iff the copy is eligible and no eligible c' of its group dominates it: mk' <= mk && ec' <= ec && tt' <= tt
+ *                       and (one of the three strictly smaller, or all three equal and c' < c) — of exact duplicates the lowest
+ *                       index stays on the front; else 0
+ * 1 <= K <= 4096 (the copies of a group live in one workgroup's LDS, 32 bytes each), N >= 1, N*K < 2^31: otherwise
+ * MTFJSP_ERR_ARG and nothing is written.  One launch, one workgroup per group, on h's stream. */
+int mtfjsp_final_costs(mtfjsp_handle_t h, double *cost4_out, uint8_t *done_out);
+int mtfjsp_group_reduce(mtfjsp_handle_t h, int32_t N, int32_t K, const double *cost4, const uint8_t *done, const double *w3cfg_host,
+                        double *obj_out, int32_t *best_out, double *best_obj_out, uint8_t *front_out);
+
 /* ------------------------------------------------------------------ dispatch-rule baselines */
 /* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
  * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"

@@ -1,0 +1,233 @@
+"""GPU: best-of-K evaluation on the device fork (evaluate.sample_best_of_k, baselines.random_baselines).  Every copy's recorded
+plan is replayed through the C oracle on the K-fold replicated instances: costs, objectives and schedules must equal the replay bit
+for bit, and the best copy, the objectives and the front must equal the host model of tests/group_reduce_ref.py applied to the
+replayed costs.  K = 1 greedy must be `validate_cost_batched`; no tolerance anywhere."""
+import functools
+from importlib import import_module
+
+import numpy as np
+import pytest
+import torch
+
+import device_streams_ref as sref
+import group_reduce_ref as ref
+from env_parity import _same
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = {"J6M6": (6, 6, 2, 4), "J3M4": (3, 4, 2, 3)}
+CONFIG_W = (0.4, 0.4, 0.2)
+KEYS = ("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")
+
+
+def _mods():
+    import mtfjsp_amd  # noqa: F401
+    return (import_module("e2e-mappo-for-mt-fjsp_amd.evaluate"), import_module("e2e-mappo-for-mt-fjsp_amd.baselines"),
+            import_module("e2e-mappo-for-mt-fjsp_amd.encoder"), import_module("e2e-mappo-for-mt-fjsp_amd.instances"))
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, np.float64).view(np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def _setup(shape, B=None):
+    _, _, enc, inst = _mods()
+    J, M, E, N = SHAPES[shape]
+    N = N if B is None else B
+    t, p, tt, edge = inst.generate_instances(N, J, M, E, seed=5100 + J * 100 + M)
+    args = dict(n_job=J, n_machine=M, n_edge=E, weight_mk=CONFIG_W[0], weight_ec=CONFIG_W[1], weight_tt=CONFIG_W[2])
+    return (t, p, tt, edge), args, enc.random_init_weights(seed=17), (J, M, E, N)
+
+
+class Recorder:
+    """on_event hook: every pass's histories ([T, n*K] -> [m*K, T] of the pass's real instances) and what was seen after the reset"""
+
+    def __init__(self, N, K):
+        self.N, self.K, self.task, self.mach, self.w3_seen = N, K, [], [], []
+
+    def __call__(self, event, env, lo, hist_task, hist_mach):
+        m = min(env.B // self.K, self.N - lo)
+        if event == "reset":
+            self.w3_seen.append(env.tasks_fea.cpu().numpy().reshape(env.B, env.T, 12)[:m * self.K, :, 9:12].copy())
+        else:
+            self.task.append(hist_task.t()[:m * self.K].cpu().numpy()); self.mach.append(hist_mach.t()[:m * self.K].cpu().numpy())
+
+    def plans(self):
+        return np.concatenate(self.task), np.concatenate(self.mach)
+
+
+def _replay(data, J, M, K, task, mach, left_shift=True, w3=None):
+    """the C oracle on the K-fold replicated instances driven by the recorded plans task, mach [N*K,T] -> cum [N*K,5], final4, state"""
+    from oracle.env_oracle import OracleBatch
+    t, p, tt, edge = (np.repeat(np.asarray(x), K, axis=0) for x in data)
+    B, T = t.shape[0], J * M
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift, w_cfg=CONFIG_W); orc.scaler_init()
+    orc.reset(np.tile(np.array([CONFIG_W]), (B, 1)) if w3 is None else np.tile(np.asarray(w3, np.float64), (B // K, 1)))
+    cum = np.zeros((B, 5))
+    for s in range(T):
+        cum += orc.step(task[:, s], mach[:, s])[1]
+    st = orc.state()
+    assert st["sched"].all()
+    final4, _ = ref.final_costs(st["prev"], np.full(B, T), T)
+    return cum, final4, st
+
+
+def _check_against_replay(res, rec, data, J, M, N, K, tag, w3=None):
+    T = J * M
+    task, mach = rec.plans()
+    assert task.shape == (N * K, T)
+    cum, final4, st = _replay(data, J, M, K, task, mach, w3=w3)
+    _same(_bits(res["final4"]), _bits(final4.reshape(N, K, 4)), tag + " final4 of every copy (bits)")
+    _same(_bits(res["cum"]), _bits(cum.reshape(N, K, 5)), tag + " summed raw rewards of every copy (bits)")
+    obj, best, best_obj, front = ref.group_reduce(final4, np.ones(N * K, np.uint8), CONFIG_W, N, K)
+    _same(_bits(res["obj"]), _bits(obj.reshape(N, K)), tag + " obj (bits)")
+    _same(res["best_copy"], best.astype(np.int64), tag + " best_copy")
+    _same(res["front"], front.reshape(N, K).astype(bool), tag + " front")
+    cost, f4, ob = res["best"]
+    _same(_bits(ob), _bits(best_obj), tag + " Objective of the best copy (bits)")
+    _same(_bits(f4), _bits(final4[best]), tag + " Final_4cost of the best copy (bits)")
+    for k, key in enumerate(KEYS):
+        _same(_bits(cost[key]), _bits(cum[best, k]), f"{tag} {key} of the best copy (bits)")
+    _same(res["plans"][0], task[best], tag + " plan of the best copy: tasks"); _same(res["plans"][1], mach[best], tag + " plan: machines")
+    _same(res["schedule"]["machine"], st["mach"][best], tag + " schedule: machines")
+    _same(_bits(res["schedule"]["start"]), _bits(st["st"][best]), tag + " schedule: start times (bits)")
+    _same(_bits(res["schedule"]["finish"]), _bits(st["ft"][best]), tag + " schedule: finish times (bits)")
+    return task, mach
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_k1_greedy_is_validate_cost_batched(shape):
+    ev = _mods()[0]
+    data, args, weights, (J, M, E, N) = _setup(shape)
+    T = J * M
+    seen = np.zeros((2, N, T), np.int32)
+
+    def on_action(s, task, mach):
+        seen[0, :, s] = task.cpu().numpy(); seen[1, :, s] = mach.cpu().numpy()
+
+    cost, final4, obj = ev.validate_cost_batched(weights, *data, args, on_action=on_action)
+    res = ev.sample_best_of_k(weights, *data, args, K=1, greedy=True)
+    bc, bf, bo = res["best"]
+    for key in KEYS:
+        _same(_bits(bc[key]), _bits(cost[key]), f"{shape} {key} (bits)")
+    _same(_bits(bf), _bits(final4), shape + " Final_4cost (bits)"); _same(_bits(bo), _bits(obj), shape + " Objective (bits)")
+    _same(res["plans"][0], seen[0], shape + " plan: tasks"); _same(res["plans"][1], seen[1], shape + " plan: machines")
+    _same(res["best_copy"], np.arange(N, dtype=np.int64), shape + " best_copy")
+    assert res["front"].all() and res["obj"].shape == (N, 1) and res["final4"].shape == (N, 1, 4)
+    _same(_bits(res["obj"][:, 0]), _bits(obj), shape + " obj (bits)")
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_k3_greedy_copies_are_one_schedule(shape):
+    ev = _mods()[0]
+    data, args, weights, (J, M, E, N) = _setup(shape)
+    K = 3
+    rec = Recorder(N, K)
+    res = ev.sample_best_of_k(weights, *data, args, K=K, greedy=True, on_event=rec)
+    for c in range(1, K):
+        _same(_bits(res["obj"][:, c]), _bits(res["obj"][:, 0]), f"{shape} obj of copy {c} (bits)")
+    assert (res["best_copy"] % K == 0).all()
+    _same(res["front"], np.tile(np.array([True, False, False]), (N, 1)), shape + " front: copy 0 only")
+    _check_against_replay(res, rec, data, J, M, N, K, shape + " K=3 greedy")
+
+
+@functools.lru_cache(maxsize=None)
+def _sampled(shape, chunk):
+    ev = _mods()[0]
+    data, args, weights, (J, M, E, N) = _setup(shape)
+    rec = Recorder(N, 5)
+    return ev.sample_best_of_k(weights, *data, args, K=5, seed=3, chunk=chunk, on_event=rec), rec
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_k5_sampled_equals_the_replay_and_the_model(shape):
+    data, args, weights, (J, M, E, N) = _setup(shape)
+    res, rec = _sampled(shape, None)
+    task, mach = _check_against_replay(res, rec, data, J, M, N, 5, shape + " K=5 sampled")
+    plans = np.stack([task, mach], -1).reshape(N, 5, -1)
+    assert any((plans[n, c] != plans[n, 0]).any() for n in range(N) for c in range(1, 5)), "the sampled copies of an instance must not all be one plan"
+    assert res["best_copy"].shape == (N,) and res["obj"].shape == (N, 5) and res["final4"].shape == (N, 5, 4) and res["front"].shape == (N, 5)
+    assert res["plans"][0].shape == (N, J * M) and all(res["schedule"][k].shape == (N, J * M) for k in ("machine", "start", "finish"))
+    assert (res["front"].sum(1) >= 1).all()
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_k5_sampled_same_seed_twice(shape):
+    ev = _mods()[0]
+    data, args, weights, _ = _setup(shape)
+    a, _ = _sampled(shape, None)
+    b = ev.sample_best_of_k(weights, *data, args, K=5, seed=3)
+    for key in ("best_copy", "obj", "final4", "front", "cum"):
+        x, y = a[key], b[key]
+        if x.dtype == np.float64:
+            x, y = _bits(x), _bits(y)
+        _same(y, x, f"{shape} second run: {key}")
+    _same(b["plans"][0], a["plans"][0], shape + " second run: plan"); _same(_bits(b["schedule"]["start"]), _bits(a["schedule"]["start"]), shape + " second run: start times")
+    c = ev.sample_best_of_k(weights, *data, args, K=5, seed=4)
+    assert not np.array_equal(c["final4"], a["final4"]), "another seed must give other samples"
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_k5_sampled_in_chunks_of_two(shape):
+    """chunk = 2: N = 4 in two passes, N = 3 with a padded last pass.  The samples are keyed by the copy's index inside the handle,
+    so they need not equal the unchunked ones; every copy must still replay exactly"""
+    data, args, weights, (J, M, E, N) = _setup(shape)
+    res, rec = _sampled(shape, 2)
+    assert len(rec.task) == (N + 1) // 2
+    _check_against_replay(res, rec, data, J, M, N, 5, shape + " K=5 sampled, chunk=2")
+    full, _ = _sampled(shape, None)
+    for key in ("best_copy", "obj", "final4", "front", "cum"):
+        assert res[key].shape == full[key].shape and res[key].dtype == full[key].dtype
+    # the first pass holds copies 0 .. 2*K-1 under the same indices as the unchunked handle: the same samples
+    _same(_bits(res["final4"][:2]), _bits(full["final4"][:2]), shape + " first pass equals the unchunked run")
+
+
+def test_w3_grid_is_what_every_copy_sees():
+    ev = _mods()[0]
+    data, args, weights, (J, M, E, N) = _setup("J6M6")
+    w3 = np.array([[1.0, 0.0, 0.0], [0.25, 0.5, 0.25], [0.0, 0.125, 0.875]])
+    rec = Recorder(N, 3)
+    res = ev.sample_best_of_k(weights, *data, args, K=3, seed=1, w3=w3, on_event=rec)
+    seen = rec.w3_seen[0]                                               # [N*3, T, 3]
+    _same(seen, np.broadcast_to(np.tile(w3.astype(np.float32), (N, 1))[:, None, :], seen.shape), "tasks_fea[:, 9:12] after the reset")
+    # the costs are the oracle's under the same preferences, the objectives are measured with the weights of args
+    _check_against_replay(res, rec, data, J, M, N, 3, "w3 grid", w3=w3)
+    with pytest.raises(ValueError):
+        ev.sample_best_of_k(weights, *data, args, K=3, w3=w3[:2])
+
+
+@pytest.mark.parametrize("left_shift", [False, True], ids=["no_left_shift", "left_shift"])
+def test_random_baselines_equal_the_stream_model_and_the_oracle(left_shift):
+    from oracle.env_oracle import OracleBatch
+    _, baselines, _, _ = _mods()
+    data, args, _, (J, M, E, N) = _setup("J6M6", 5)
+    K, T, seed = 4, J * M, (1 << 33) + 5
+    res = baselines.random_baselines(*data, args, K=K, seed=seed, left_shift=left_shift)
+    assert sorted(res) == sorted([baselines.RANDOM_BEST, baselines.RANDOM_MEAN, baselines.PLANS])
+    t, p, tt, edge = (np.repeat(np.asarray(x), K, axis=0) for x in data)
+    B = N * K
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift, w_cfg=CONFIG_W); orc.scaler_init()
+    orc.reset(np.tile(np.array([CONFIG_W]), (B, 1)))
+    cand, mask = orc.job_mask_state()
+    cum, task, mach = np.zeros((B, 5)), np.zeros((B, T), np.int32), np.zeros((B, T), np.int32)
+    for s in range(T):
+        task[:, s], mach[:, s], job = sref.random_actions(t, cand, mask, seed, s)
+        cum += orc.step(task[:, s], mach[:, s])[1]
+        cand, mask = orc.job_mask_update(job)
+    st = orc.state()
+    assert st["sched"].all()
+    final4, _ = ref.final_costs(st["prev"], np.full(B, T), T)
+    obj, best, best_obj, _ = ref.group_reduce(final4, np.ones(B, np.uint8), CONFIG_W, N, K)
+    cost, f4, ob = res[baselines.RANDOM_BEST]
+    _same(res[baselines.PLANS][baselines.RANDOM_BEST][0], task[best], "the best copy's tasks = the stream model's")
+    _same(res[baselines.PLANS][baselines.RANDOM_BEST][1], mach[best], "the best copy's machines = the stream model's")
+    _same(_bits(ob), _bits(best_obj), "RANDOM_BEST Objective (bits)"); _same(_bits(f4), _bits(final4[best]), "RANDOM_BEST Final_4cost (bits)")
+    for k, key in enumerate(KEYS):
+        _same(_bits(cost[key]), _bits(cum[best, k]), f"RANDOM_BEST {key} (bits)")
+    cost, f4, ob = res[baselines.RANDOM_MEAN]
+    _same(_bits(ob), _bits(obj.reshape(N, K).mean(axis=1)), "RANDOM_MEAN Objective (bits)")
+    _same(_bits(f4), _bits(final4.reshape(N, K, 4).mean(axis=1)), "RANDOM_MEAN Final_4cost (bits)")
+    for k, key in enumerate(KEYS):
+        _same(_bits(cost[key]), _bits(cum.reshape(N, K, 5)[:, :, k].mean(axis=1)), f"RANDOM_MEAN {key} (bits)")
+    assert len({tuple(r) for r in task[:K]}) > 1, "the copies of an instance must be different episodes"
