@@ -14,12 +14,30 @@ import torch
 
 from . import capi
 from .batch_env import DeviceBatchEnv
+from .evaluate import COST_KEYS, best_of_k_rollout, episode_results, parse_args, replay_episode
 
 M_RULE_NAMES = ["SPT", "SEC"]                                                        # pdrs:729
 O_RULE_NAMES = ["FIFO", "MOR", "LWKR_T_o", "LWKR_PT_o", "MWKR_T_o", "MWKR_PT_o"]     # pdrs:730
 # (name, o_rule, m_rule) in test_all.py's order: o_i outer, m_i inner
 RULES = [(f"{O_RULE_NAMES[o]}+{M_RULE_NAMES[m]}", o, m) for o in range(6) for m in range(2)]
 PLANS = "plans"          # key of pdr_baselines' result that holds {name: (task[N,T], mach[N,T])}; no rule is called that
+
+
+def _rule_names(rules, kind=None):
+    """the names of `rules` ((name, ...) each), checked; kind ("look-ahead", "beam"): element 1 is a column of the raw rewards"""
+    names = [r[0] for r in rules]
+    if len(set(names)) != len(rules) or PLANS in names:
+        raise ValueError("rule names must be distinct")
+    if kind and any(int(r[1]) not in range(5) for r in rules):
+        raise ValueError(f"a {kind} rule's column must be 0..4")
+    return names
+
+
+def _results(names, parts, T, w):
+    """{name: (cum, prev, task, mach)} host arrays per rule -> the *_baselines' result dict"""
+    out = {name: episode_results(parts[name][0], parts[name][1], T, w) for name in names}
+    out[PLANS] = {name: parts[name][2:] for name in names}
+    return out
 
 
 def _rule_tensor(x, B, dev):
@@ -52,24 +70,11 @@ def pdr_plan(env, o_rule, m_rule, mor_order=None, seed=0):
 
 def _rollout(env, w3, o_rule, m_rule, mor_order, seed):
     """reset with the config weights, plan, T steps -> (cumulative raw rewards [B,5], final costs [B,4], task, mach)"""
-    T, dev = env.T, env.device
     env.reset(w3)                                                       # pdrs:675 reset(Random_weight_type="eval")
     task, mach = pdr_plan(env, o_rule, m_rule, mor_order, seed)
     ts, ms = task.t().contiguous(), mach.t().contiguous()               # [T,B]: row s = the actions of step s
-    cum = torch.zeros(env.B, 5, dtype=torch.float64, device=dev)
-    bad = torch.zeros(env.B, dtype=torch.int32, device=dev)
-    for s in range(T):
-        env.step(ts[s], ms[s])
-        cum += env.raw                                                  # reward, r_mk, r_idle, r_pt, r_tt (pdrs:776-780), in step order
-        bad |= env.status
-    torch.cuda.synchronize(dev)
-    n_bad = int((bad & (capi.ST_INVALID | capi.ST_INFEASIBLE)).ne(0).sum().item())
-    if n_bad:
-        raise RuntimeError(f"dispatch-rule rollout: {n_bad} instance(s) met an invalid action or an infeasible machine")
-    if not bool(env.info[:, 1].all().item()):
-        raise RuntimeError("dispatch-rule rollout: an episode did not finish after T steps")
-    prev = env.read_state(capi.STATE_PREV_COSTS)                        # mk, e1, transT, idle of the finished schedule (pdrs:808-812)
-    return cum.cpu().numpy(), prev, task.cpu().numpy(), mach.cpu().numpy()
+    cum, prev = replay_episode(env, env.T, lambda s: (ts[s], ms[s]), "dispatch-rule")
+    return cum, prev, task.cpu().numpy(), mach.cpu().numpy()
 
 
 def pdr_baselines(t, p, tt, edge, args, rules=RULES, mor_order=None, seed=0, device=0, env=None, obs_dtype="f32"):
@@ -82,18 +87,12 @@ def pdr_baselines(t, p, tt, edge, args, rules=RULES, mor_order=None, seed=0, dev
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} with the per-instance arrays of `validate_cost_batched` (opr_Gt, opr_mk,
     opr_idleT, opr_pt, opr_transT; [N,4] makespan, e1 / T, transport, idle; pdrs:790-812 and test_all.py:536-538), and under
     PLANS ("plans") {name: (task[N,T], mach[N,T])}: what every rule dispatched."""
-    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
-    T, R = J * M, len(rules)
-    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
-    names = [r[0] for r in rules]
-    if len(set(names)) != R or PLANS in names:
-        raise ValueError("rule names must be distinct")
+    J, M, E, T, w, kw = parse_args(args, left_shift=False, obs_dtype=obs_dtype, device=device)
+    R, names = len(rules), _rule_names(rules)
     if env is None:
         t = np.asarray(t, np.float64)
         N = t.shape[0]
-        scal = args.get("reward_scaling", {}) or {}
-        big = DeviceBatchEnv(J, M, E, R * N, left_shift=False, obs_dtype=obs_dtype, device=device, w_cfg=w,
-                             scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+        big = DeviceBatchEnv(J, M, E, R * N, **kw)
         rep = lambda x: np.tile(np.asarray(x), (R,) + (1,) * (np.asarray(x).ndim - 1))      # noqa: E731
         big.load_instances(rep(t), rep(np.asarray(p, np.float64)), rep(np.asarray(tt, np.float64)), edge=rep(edge))
         big.scaler_init()                                               # the scaled components are produced but not used here
@@ -116,15 +115,7 @@ def pdr_baselines(t, p, tt, edge, args, rules=RULES, mor_order=None, seed=0, dev
         w3 = torch.tensor([w], dtype=torch.float64, device=env.device).repeat(env.B, 1)
         env.scaler_init()
         parts = [_rollout(env, w3, r[1], r[2], mor_order, seed) for r in rules]
-    out, plans = {}, {}
-    for name, (c, prev, task, mach) in zip(names, parts):
-        cost = {"opr_Gt": c[:, 0], "opr_mk": c[:, 1], "opr_idleT": c[:, 2], "opr_pt": c[:, 3], "opr_transT": c[:, 4]}
-        final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
-        obj = w[0] * final4[:, 0] + w[1] * (final4[:, 1] + final4[:, 3]) + w[2] * final4[:, 2]
-        out[name] = (cost, final4, obj)
-        plans[name] = (task, mach)
-    out[PLANS] = plans
-    return out
+    return _results(names, dict(zip(names, parts)), T, w)
 
 
 # ---- one-step look-ahead rules (csrc/mtfjsp_lookahead.hip): the dynamic half of the table.  (name, column of the raw rewards whose
@@ -176,21 +167,13 @@ def lookahead_baselines(t, p, tt, edge, args, rules=LOOKAHEAD_RULES, device=0, o
     step the instance with it.  Unlike the reference's idle-time rule (pdrs:465-540) the tie is not drawn at random (pdrs:520) and
     the machine is not fixed beforehand by a machine rule: job and machine are chosen jointly.
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, and under PLANS {name: (task[N,T], mach[N,T])}."""
-    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
-    T = J * M
-    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
-    names = [r[0] for r in rules]
-    if len(set(names)) != len(rules) or PLANS in names:
-        raise ValueError("rule names must be distinct")
-    if any(int(r[1]) not in range(5) for r in rules):
-        raise ValueError("a look-ahead rule's column must be 0..4")
+    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    names = _rule_names(rules, "look-ahead")
     t = np.asarray(t, np.float64)
     N = t.shape[0]
-    scal = args.get("reward_scaling", {}) or {}
-    env = DeviceBatchEnv(J, M, E, N, left_shift=left_shift, obs_dtype=obs_dtype, device=device, w_cfg=w,
-                         scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+    env = DeviceBatchEnv(J, M, E, N, **kw)
     la = None
-    out, plans = {}, {}
+    parts = {}
     try:
         env.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=edge)
         la = Lookahead(env)
@@ -201,33 +184,18 @@ def lookahead_baselines(t, p, tt, edge, args, rules=LOOKAHEAD_RULES, device=0, o
             env.reset(w3)                                               # pdrs:675 reset(Random_weight_type="eval")
             task = torch.empty(T, N, dtype=torch.int32, device=dev)
             mach = torch.empty(T, N, dtype=torch.int32, device=dev)
-            cum = torch.zeros(N, 5, dtype=torch.float64, device=dev)
-            bad = torch.zeros(N, dtype=torch.int32, device=dev)
-            for s in range(T):
+
+            def decide(s):                                              # the choice of step s, recorded
                 a, m = la.decide(column)
                 task[s].copy_(a); mach[s].copy_(m)
-                env.step(a, m)
-                cum += env.raw                                          # reward, r_mk, r_idle, r_pt, r_tt, in step order
-                bad |= env.status
-            torch.cuda.synchronize(dev)
-            n_bad = int((bad & (capi.ST_INVALID | capi.ST_INFEASIBLE)).ne(0).sum().item())
-            if n_bad:
-                raise RuntimeError(f"look-ahead rollout: {n_bad} instance(s) met an invalid action or an infeasible machine")
-            if not bool(env.info[:, 1].all().item()):
-                raise RuntimeError("look-ahead rollout: an episode did not finish after T steps")
-            prev = env.read_state(capi.STATE_PREV_COSTS)
-            c = cum.cpu().numpy()
-            cost = {"opr_Gt": c[:, 0], "opr_mk": c[:, 1], "opr_idleT": c[:, 2], "opr_pt": c[:, 3], "opr_transT": c[:, 4]}
-            final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
-            obj = w[0] * final4[:, 0] + w[1] * (final4[:, 1] + final4[:, 3]) + w[2] * final4[:, 2]
-            out[name] = (cost, final4, obj)
-            plans[name] = (task.t().contiguous().cpu().numpy(), mach.t().contiguous().cpu().numpy())
+                return a, m
+            cum, prev = replay_episode(env, T, decide, "look-ahead")
+            parts[name] = (cum, prev, task.t().contiguous().cpu().numpy(), mach.t().contiguous().cpu().numpy())
     finally:
         if la is not None:
             la.close()
         env.close()
-    out[PLANS] = plans
-    return out
+    return _results(names, parts, T, w)
 
 
 # ---- beam search (csrc/mtfjsp_beam.hip): the look-ahead's children, the W best of them kept per instance instead of one.  (name,
@@ -340,26 +308,18 @@ def beam_baselines(t, p, tt, edge, args, rules=BEAM_RULES, width=8, dedupe=True,
     step, as `lookahead_baselines` steps its choices.  chunk: source instances per pass (None: the largest with
     chunk * width * T <= BEAM_SCRATCH_BATCH); the results do not depend on it.
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, and under PLANS {name: (task[N,T], mach[N,T])}."""
-    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
-    T, W = J * M, int(width)
-    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
-    names = [r[0] for r in rules]
-    if len(set(names)) != len(rules) or PLANS in names:
-        raise ValueError("rule names must be distinct")
-    if any(int(r[1]) not in range(5) for r in rules):
-        raise ValueError("a beam rule's column must be 0..4")
+    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    W, names = int(width), _rule_names(rules, "beam")
     t, p, tt, edge = np.asarray(t, np.float64), np.asarray(p, np.float64), np.asarray(tt, np.float64), np.asarray(edge)
     N = t.shape[0]
     chunk = max(1, BEAM_SCRATCH_BATCH // (W * T)) if chunk is None else int(chunk)
     if chunk < 1:
         raise ValueError("chunk must be at least 1")
-    scal = args.get("reward_scaling", {}) or {}
     parts = {name: [] for name in names}
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
         n = hi - lo
-        env = DeviceBatchEnv(J, M, E, n, left_shift=left_shift, obs_dtype=obs_dtype, device=device, w_cfg=w,
-                             scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+        env = DeviceBatchEnv(J, M, E, n, **kw)
         bs = None
         try:
             env.load_instances(t[lo:hi], p[lo:hi], tt[lo:hi], edge=edge[lo:hi])
@@ -374,33 +334,13 @@ def beam_baselines(t, p, tt, edge, args, rules=BEAM_RULES, width=8, dedupe=True,
                     bs.restart()
                 task, mach, _ = bs.run(int(column), T)
                 ts, ms = task.t().contiguous(), mach.t().contiguous()   # [T,n]: row s = the actions of step s
-                cum = torch.zeros(n, 5, dtype=torch.float64, device=dev)
-                bad = torch.zeros(n, dtype=torch.int32, device=dev)
-                for s in range(T):
-                    env.step(ts[s], ms[s])
-                    cum += env.raw                                      # reward, r_mk, r_idle, r_pt, r_tt, in step order
-                    bad |= env.status
-                torch.cuda.synchronize(dev)
-                n_bad = int((bad & (capi.ST_INVALID | capi.ST_INFEASIBLE)).ne(0).sum().item())
-                if n_bad:
-                    raise RuntimeError(f"beam-search rollout: {n_bad} instance(s) met an invalid action or an infeasible machine")
-                if not bool(env.info[:, 1].all().item()):
-                    raise RuntimeError("beam-search rollout: an episode did not finish after T steps")
-                parts[name].append((cum.cpu().numpy(), env.read_state(capi.STATE_PREV_COSTS), task.cpu().numpy(), mach.cpu().numpy()))
+                cum, prev = replay_episode(env, T, lambda s: (ts[s], ms[s]), "beam-search")
+                parts[name].append((cum, prev, task.cpu().numpy(), mach.cpu().numpy()))
         finally:
             if bs is not None:
                 bs.close()
             env.close()
-    out, plans = {}, {}
-    for name in names:
-        c, prev, task, mach = (np.concatenate([x[k] for x in parts[name]]) for k in range(4))
-        cost = {"opr_Gt": c[:, 0], "opr_mk": c[:, 1], "opr_idleT": c[:, 2], "opr_pt": c[:, 3], "opr_transT": c[:, 4]}
-        final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
-        obj = w[0] * final4[:, 0] + w[1] * (final4[:, 1] + final4[:, 3]) + w[2] * final4[:, 2]
-        out[name] = (cost, final4, obj)
-        plans[name] = (task, mach)
-    out[PLANS] = plans
-    return out
+    return _results(names, {name: tuple(np.concatenate([x[k] for x in parts[name]]) for k in range(4)) for name in names}, T, w)
 
 
 # ---- the random dispatch rule as best-of-K (csrc/mtfjsp_group.hip): K uniformly random episodes per instance, the best kept
@@ -435,7 +375,6 @@ def random_baselines(t, p, tt, edge, args, K=1, seed=0, device=0, obs_dtype="f32
     -> {"RANDOM_BEST": (cost_dict_cumsum, Final_4cost, Objective) of every instance's best episode (smallest Objective, lowest copy
     on ties), "RANDOM_MEAN": the same three as means over the K episodes (taken on the host)} in `pdr_baselines`' layout, and under
     PLANS {"RANDOM_BEST": (task[N,T], mach[N,T])}."""
-    from .evaluate import COST_KEYS, best_of_k_rollout
     r = best_of_k_rollout(t, p, tt, edge, args, K, _RandomPolicy(seed), chunk=chunk, device=device, obs_dtype=obs_dtype, left_shift=left_shift,
                           what="random-rule")
     mean_cost = {key: r["cum"][:, :, i].mean(axis=1) for i, key in enumerate(COST_KEYS)}

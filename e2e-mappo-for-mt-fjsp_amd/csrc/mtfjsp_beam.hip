@@ -10,11 +10,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/mtfjsp.h"
 
 #include "mtfjsp_env_dev.h"
+#include "mtfjsp_wave_select.h"
 
 #define BEAM_WAVES 4
 #define BEAM_THREADS (BEAM_WAVES * WAVE)
@@ -66,12 +66,11 @@ extern "C" int mtfjsp_state_signature(mtfjsp_handle_t h, uint64_t *sig_out)
     EnvHostView v;
     mtfjsp_env_host_view(h, &v);
     if (!v.was_reset) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_state_signature: the handle has never been reset");
-    if (hipSetDevice(v.device_id) != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_state_signature: hipSetDevice failed");
+    if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_state_signature")) return rc;
     SigArgs A{};
     A.B = v.B; A.T = v.T; A.sd = v.sd; A.pl = v.pl; A.out = (u64 *)sig_out;
     hipLaunchKernelGGL(k_state_signature, dim3((unsigned)(((size_t)v.B + BEAM_WAVES - 1) / BEAM_WAVES)), dim3(BEAM_THREADS), 0, v.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_state_signature: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(h, "mtfjsp_state_signature");
 }
 
 // ---------------------------------------------------------------- selection
@@ -86,26 +85,11 @@ struct BeamArgs {
     double *score_out;                 // [N*W]
 };
 
-// wave-wide maximum on the cross-lane data path, as k_lookahead_select's (row shifts, then row_bcast:15 / :31: lane 63 holds the
-// result).  All 64 lanes must be active.  fmax returns one of its operands: a comparison.
-#define BEAM_DPP(x, ctrl) __builtin_amdgcn_update_dpp((x), (x), (ctrl), 0xF, 0xF, false)
-__device__ __forceinline__ double beam_wave_max(double x)
-{
-#define STEP_(ctrl)                                                                                     \
-    {                                                                                                  \
-        const int lo = BEAM_DPP(__double2loint(x), ctrl), hi = BEAM_DPP(__double2hiint(x), ctrl);      \
-        x = fmax(x, __hiloint2double(hi, lo));                                                         \
-    }
-    STEP_(0x111) STEP_(0x112) STEP_(0x114) STEP_(0x118) STEP_(0x142) STEP_(0x143)
-#undef STEP_
-    return rl_d(x, 63);
-}
-
 // Candidate c = w*T + r of source instance n (slot w, child r = j*M + m) lives in LDS as its value, NaN once it cannot be picked
 // any more (not eligible, picked, or merged into a pick); thread c % 256 owns it — it alone reads and writes val[c] after the
 // first barrier, so a rank needs one barrier: the one between the waves' partial results and their combination.  A wave takes its
 // candidates 64 at a time in ascending c and a later pass wins only with a strictly larger value; the four partial results are
-// combined by (value, then lower c): the lowest index of the maximum, whatever the number of waves.
+// combined by (value, then lower c): the lowest index of the maximum, whatever the number of waves (WaveBest, mtfjsp_wave_select.h).
 __global__ __launch_bounds__(BEAM_THREADS) void k_beam_select(BeamArgs A)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -127,26 +111,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_select(BeamArgs A)
     }
     __syncthreads();
     for (int k = 0; k < W; k++) {
-        double best = 0.0;
-        int bi = -1;
+        WaveBest<true> mine;
         for (int c0 = wave * WAVE; c0 < C; c0 += BEAM_THREADS) {
             const int c = c0 + lane;
             const double v = c < C ? val[c] : (double)NAN;
-            const bool ok = v == v;                                         // a NaN is never selected
-            const double mx = beam_wave_max(ok ? v : -INFINITY);
-            const unsigned long long eq = __ballot(ok && v == mx);
-            if (eq && (bi < 0 || mx > best)) { best = mx; bi = c0 + __ffsll((long long)eq) - 1; }
+            mine.pass(v == v, v, c0);                                       // a NaN is never selected
         }
-        if (lane == 0) { part_v[k & 1][wave] = best; part_i[k & 1][wave] = bi; }
+        if (lane == 0) { part_v[k & 1][wave] = mine.v; part_i[k & 1][wave] = mine.i; }
         __syncthreads();
-        double gb = 0.0;
-        int gi = -1;
-#pragma unroll
-        for (int q = 0; q < BEAM_WAVES; q++) {
-            const double bq = part_v[k & 1][q];
-            const int iq = part_i[k & 1][q];
-            if (iq >= 0 && (gi < 0 || bq > gb || (bq == gb && iq < gi))) { gb = bq; gi = iq; }
-        }
+        const WaveBest<true> all = wave_best_combine<true, BEAM_WAVES>(part_v[k & 1], part_i[k & 1]);
+        const double gb = all.v;
+        const int gi = all.i;
         if (gi < 0) {
             if (k == 0) {                                                   // nothing to pick at all (finished): the beam is kept
                 for (int q = tid; q < W; q += BEAM_THREADS) {
@@ -180,19 +155,6 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_select(BeamArgs A)
     }
 }
 
-// the look-ahead's check of the handle pair (scratch batch = beam batch * T), plus the beam's own
-static int beam_views(const char *who, mtfjsp_handle_t scratch, mtfjsp_handle_t beam, EnvHostView *sc, EnvHostView *bm)
-{
-    mtfjsp_env_host_view(scratch, sc);
-    mtfjsp_env_host_view(beam, bm);
-    if (scratch == beam || sc->J != bm->J || sc->M != bm->M || sc->device_id != bm->device_id || (long)sc->B != (long)bm->B * bm->T) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: the scratch handle must be another handle of the same size on the same device with batch = beam batch * T", who);
-        return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, msg);
-    }
-    return MTFJSP_OK;
-}
-
 extern "C" int mtfjsp_beam_select(mtfjsp_handle_t scratch, mtfjsp_handle_t beam, int32_t W, int32_t column, const double *score_in, const uint64_t *sig,
                                   int32_t *parent_out, int32_t *from_slot_out, int32_t *task_out, int32_t *mach_out, double *score_out)
 {
@@ -202,23 +164,23 @@ extern "C" int mtfjsp_beam_select(mtfjsp_handle_t scratch, mtfjsp_handle_t beam,
     if (column < 0 || column > 4) return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, "mtfjsp_beam_select: column must be 0..4 (reward, makespan, idle, energy, transport)");
     if (score_out == score_in) return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, "mtfjsp_beam_select: score_out must not be score_in (every rank reads all parent scores)");
     EnvHostView sc, bm;
-    int rc = beam_views("mtfjsp_beam_select", scratch, beam, &sc, &bm);
+    int rc = mtfjsp_env_pair_views("mtfjsp_beam_select", "beam", scratch, beam, &sc, &bm);
     if (rc) return rc;
     if (W < 1 || W > BEAM_MAX_W || bm.B % W) return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, "mtfjsp_beam_select: the width must be 1..64 and divide the beam handle's batch");
     if ((long)W * bm.T > BEAM_MAX_CAND) return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, "mtfjsp_beam_select: width * n_job * n_machine must not exceed 8192 candidates");
     if (!sc.was_reset || !bm.was_reset) return mtfjsp_env_fail(scratch, MTFJSP_ERR_STATE, "mtfjsp_beam_select: both handles must hold a state (mtfjsp_lookahead_expand and a step first)");
     if (!sc.obs_bound || !sc.obs.raw) return mtfjsp_env_fail(scratch, MTFJSP_ERR_STATE, "mtfjsp_beam_select: the scratch handle needs bound observations with raw");
-    if (hipSetDevice(bm.device_id) != hipSuccess) return mtfjsp_env_fail(scratch, MTFJSP_ERR_HIP, "mtfjsp_beam_select: hipSetDevice failed");
+    if ((rc = mtfjsp_env_set_device(scratch, bm.device_id, "mtfjsp_beam_select"))) return rc;
     const size_t lds = (size_t)W * bm.T * (sig ? 16 : 8);
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void *)k_beam_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return mtfjsp_env_fail(scratch, MTFJSP_ERR_HIP, "mtfjsp_beam_select: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    if (lds > 48 * 1024 && (rc = mtfjsp_env_hip_check(scratch, hipFuncSetAttribute((const void *)k_beam_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                                                      "mtfjsp_beam_select", "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed")))
+        return rc;
     BeamArgs A{};
     A.W = W; A.T = bm.T; A.M = bm.M; A.MJ = bm.MJ; A.column = column; A.mj = bm.mj; A.status = sc.obs.status; A.raw = sc.obs.raw;
     A.score_in = score_in; A.sig = (const u64 *)sig; A.parent = parent_out; A.from_slot = from_slot_out; A.task = task_out; A.mach = mach_out;
     A.score_out = score_out;
     hipLaunchKernelGGL(k_beam_select, dim3((unsigned)(bm.B / W)), dim3(BEAM_THREADS), lds, bm.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(scratch, MTFJSP_ERR_HIP, "mtfjsp_beam_select: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(scratch, "mtfjsp_beam_select");
 }
 
 // ---------------------------------------------------------------- back-pointers
@@ -252,11 +214,10 @@ extern "C" int mtfjsp_beam_backtrack(mtfjsp_handle_t h, int32_t W, int32_t S, co
     EnvHostView v;
     mtfjsp_env_host_view(h, &v);
     if (W < 1 || W > BEAM_MAX_W || v.B % W || S < 1) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_beam_backtrack: the width must be 1..64 and divide the handle's batch, steps >= 1");
-    if (hipSetDevice(v.device_id) != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_beam_backtrack: hipSetDevice failed");
+    if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_beam_backtrack")) return rc;
     BackArgs A{};
     A.N = v.B / W; A.W = W; A.S = S; A.from_slot = hist_from_slot; A.task = hist_task; A.mach = hist_mach; A.start = start_slot;
     A.task_plan = task_plan; A.mach_plan = mach_plan;
     hipLaunchKernelGGL(k_beam_backtrack, dim3((unsigned)((A.N + 255) / 256)), dim3(256), 0, v.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_beam_backtrack: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(h, "mtfjsp_beam_backtrack");
 }

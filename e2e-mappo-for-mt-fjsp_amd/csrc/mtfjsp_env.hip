@@ -30,6 +30,7 @@
 #include "../../include/mtfjsp.h"
 
 #include "mtfjsp_env_dev.h"
+#include "mtfjsp_wave_select.h"
 
 // ---------------------------------------------------------------------------------------------
 // numpy float64 add.reduce order: 0 + pairwise_sum (8 accumulators, 128-element leaf blocks).
@@ -71,39 +72,7 @@ __device__ __forceinline__ double wave_max(double x)
     for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o));
     return x;
 }
-// the same reductions on the cross-lane data path (DPP: no LDS round trip per step): after four row shifts lane 15 of every row
-// of 16 holds its row's result, row_bcast:15 / :31 carry it on; the wave's result is in LANE 63 only.  Lanes without a source
-// keep their own value (max / min are idempotent).
-#define DPP_I(x, ctrl) __builtin_amdgcn_update_dpp((x), (x), (ctrl), 0xF, 0xF, false)
-__device__ __forceinline__ double wave_max_lane63(double x)
-{
-#define STEP_(ctrl)                                                                                       \
-    {                                                                                                    \
-        const int lo = DPP_I(__double2loint(x), ctrl), hi = DPP_I(__double2hiint(x), ctrl);              \
-        x = fmax(x, __hiloint2double(hi, lo));                                                           \
-    }
-    STEP_(0x111) STEP_(0x112) STEP_(0x114) STEP_(0x118) STEP_(0x142) STEP_(0x143)
-#undef STEP_
-    return x;
-}
-__device__ __forceinline__ int wave_min_lane63(int x)
-{
-#define STEP_(ctrl) { const int y = DPP_I(x, ctrl); x = y < x ? y : x; }
-    STEP_(0x111) STEP_(0x112) STEP_(0x114) STEP_(0x118) STEP_(0x142) STEP_(0x143)
-#undef STEP_
-    return x;
-}
-// inclusive prefix sum over the wave's lanes (zero fill; row_bcast adds the previous rows' totals)
-__device__ __forceinline__ int wave_scan_incl(int x)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);      // rows 1, 3 += lane 15 of the row before
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);      // rows 2, 3 += lane 31
-    return x;
-}
+// (the reductions on the cross-lane data path — wave_ext_lane63, wave_min_lane63, wave_scan_incl: mtfjsp_wave_select.h)
 
 // env.generate_random_weights("01") (env:1253-1259) of instance b: three uniforms in [0,1), normalised by their sum (numpy's sum of three =
 // left-to-right adds).  53-bit uniforms like python's random.random(): (a >> 5, b >> 6) -> (a*2^26 + b) / 2^53.
@@ -1073,7 +1042,7 @@ __device__ __forceinline__ void env_step_wave(const EnvParams &P, const int b, c
                         if (ok) { const int kk = ((int)s_pos[v] << 16) | v; key = kk < key ? kk : key; }
                     }
                 }
-                key = rl_i(wave_min_lane63(key), 63);
+                key = wave_min(key);
                 if (key != 0x7fffffff) {
                     path = MTFJSP_PATH_BETWEEN;
                     Nk = key & 0xffff; ipos = key >> 16; Pk = s_prev[Nk];
@@ -1181,7 +1150,7 @@ __device__ __forceinline__ void env_step_wave(const EnvParams &P, const int b, c
         }
     }
     {   // per-job maxima of the acting job (row maximum of ft_est for the makespan; of real ft for the job mask, ppo:265-275)
-        const double fm = wave_max_lane63(my_fte), rm = wave_max_lane63(lane < M ? my_rft : -INFINITY);
+        const double fm = wave_ext_lane63<true>(my_fte), rm = wave_ext_lane63<true>(lane < M ? my_rft : -INFINITY);
         if (lane == 63) { s_jmax[ja] = fm; s_jrow[ja] = rm; }
     }
     WSYNC();
@@ -1663,6 +1632,20 @@ int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg)
 {
     h->err = msg;
     return code;
+}
+int mtfjsp_env_hip_check(mtfjsp_handle_t h, hipError_t e, const char *who, const char *msg)
+{
+    if (e == hipSuccess) return MTFJSP_OK;
+    h->err = std::string(who) + ": " + msg;
+    return MTFJSP_ERR_HIP;
+}
+int mtfjsp_env_pair_views(const char *who, const char *noun, mtfjsp_handle_t scratch, mtfjsp_handle_t src, EnvHostView *sc, EnvHostView *so)
+{
+    mtfjsp_env_host_view(scratch, sc);
+    mtfjsp_env_host_view(src, so);
+    if (scratch != src && sc->J == so->J && sc->M == so->M && sc->device_id == so->device_id && (long)sc->B == (long)so->B * so->T) return MTFJSP_OK;
+    scratch->err = std::string(who) + ": the scratch handle must be another handle of the same size on the same device with batch = " + noun + " batch * T";
+    return MTFJSP_ERR_ARG;
 }
 
 #define HIPCHK(h, call)                                                                         \

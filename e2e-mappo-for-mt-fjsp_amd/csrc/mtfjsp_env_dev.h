@@ -1,6 +1,8 @@
-// mtfjsp_env_dev.h — device-side definitions of the environment state that more than one translation unit needs: the step
-// kernels of mtfjsp_env.hip, and mtfjsp_encoder.hip, whose machine-actor heads kernel can run the grouped step of its 16 instances
-// as its tail (k_headsx_envstep).  Kernel parameter block, per-task / per-machine records, scalar slots, uniform lane reads.
+// mtfjsp_env_dev.h — definitions of the environment state that more than one translation unit needs.  Device side (the step kernels
+// of mtfjsp_env.hip; mtfjsp_encoder.hip, whose machine-actor heads kernel can run the grouped step of its 16 instances as its tail,
+// k_headsx_envstep; the search baselines mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip): kernel parameter
+// block, per-task / per-machine records, scalar slots, uniform lane reads — the wave-wide selections on top of them are in
+// mtfjsp_wave_select.h.  Host side (the four baseline units): a view of a handle and the checks their entry points share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/mtfjsp.h"
@@ -129,6 +131,14 @@ struct EnvHostView {
 };
 __attribute__((visibility("hidden"))) void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v);
 __attribute__((visibility("hidden"))) int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg);   // sets mtfjsp_last_error, returns code
+// the check behind every HIP call of an entry point `who`: e != hipSuccess sets "<who>: <msg>" and returns MTFJSP_ERR_HIP, else MTFJSP_OK
+__attribute__((visibility("hidden"))) int mtfjsp_env_hip_check(mtfjsp_handle_t h, hipError_t e, const char *who, const char *msg);
+static inline int mtfjsp_env_set_device(mtfjsp_handle_t h, int device_id, const char *who) { return mtfjsp_env_hip_check(h, hipSetDevice(device_id), who, "hipSetDevice failed"); }
+static inline int mtfjsp_env_launched(mtfjsp_handle_t h, const char *who) { return mtfjsp_env_hip_check(h, hipGetLastError(), who, "launch failed"); }
+// both views of a (scratch, source) pair of the look-ahead's shape — another handle of the same size on the same device, scratch batch =
+// source batch * T — or MTFJSP_ERR_ARG on the scratch handle; noun: what the message calls the source ("source", "beam")
+__attribute__((visibility("hidden"))) int mtfjsp_env_pair_views(const char *who, const char *noun, mtfjsp_handle_t scratch, mtfjsp_handle_t src, EnvHostView *sc,
+                                                                EnvHostView *so);
 // mtfjsp_fork's checks and launch.  src_index == nullptr: destination instance i takes source instance i / div (the look-ahead's
 // implicit index: T copies per source instance); the public entry point always passes an index.
 __attribute__((visibility("hidden"))) int mtfjsp_env_fork_launch(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32_t *src_index, int div, int flags,

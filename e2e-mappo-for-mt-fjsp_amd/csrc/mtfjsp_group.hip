@@ -16,6 +16,7 @@
 #include "../../include/mtfjsp.h"
 
 #include "mtfjsp_env_dev.h"
+#include "mtfjsp_wave_select.h"
 
 #define GRP_WAVES 4
 #define GRP_THREADS (GRP_WAVES * WAVE)
@@ -47,12 +48,11 @@ extern "C" int mtfjsp_final_costs(mtfjsp_handle_t h, double *cost4_out, uint8_t 
     EnvHostView v;
     mtfjsp_env_host_view(h, &v);
     if (!v.was_reset) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_final_costs: the handle has never been reset");
-    if (hipSetDevice(v.device_id) != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_final_costs: hipSetDevice failed");
+    if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_final_costs")) return rc;
     FinalArgs A{};
     A.B = v.B; A.T = v.T; A.scal = v.scal; A.cost4 = cost4_out; A.done = done_out;
     hipLaunchKernelGGL(k_final_costs, dim3((unsigned)(((size_t)v.B + 255) / 256)), dim3(256), 0, v.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_final_costs: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(h, "mtfjsp_final_costs");
 }
 
 // ---------------------------------------------------------------- group reduction
@@ -67,26 +67,12 @@ struct GroupArgs {
     uint8_t *front;                    // [N*K] or null
 };
 
-// wave-wide minimum on the cross-lane data path, as k_lookahead_select's maximum (row shifts, then row_bcast:15 / :31: lane 63 holds
-// the result).  All 64 lanes must be active.  fmin returns one of its operands: a comparison.
-#define GRP_DPP(x, ctrl) __builtin_amdgcn_update_dpp((x), (x), (ctrl), 0xF, 0xF, false)
-__device__ __forceinline__ double grp_wave_min(double x)
-{
-#define STEP_(ctrl)                                                                                     \
-    {                                                                                                  \
-        const int lo = GRP_DPP(__double2loint(x), ctrl), hi = GRP_DPP(__double2hiint(x), ctrl);        \
-        x = fmin(x, __hiloint2double(hi, lo));                                                         \
-    }
-    STEP_(0x111) STEP_(0x112) STEP_(0x114) STEP_(0x118) STEP_(0x142) STEP_(0x143)
-#undef STEP_
-    return rl_d(x, 63);
-}
-
 // Copy c of group n lives in LDS as (mk, ec, tt, obj), 32 bytes; an ineligible copy (not done, or a NaN among mk, ec, tt) has NaN for
 // mk and obj there: every comparison with it is false, so it neither dominates nor is picked.  Thread tid owns copies tid, tid + 256,
 // ... (OWN of them at most: 1, 4 or 16 by K) and keeps them in registers: it alone writes their flags, and pass i of wave w over the
 // minimum — copies w*64 + 256*i + lane — is exactly its i-th owned copy, so the minimum reads no LDS.  A wave's later pass wins only
-// with a strictly smaller value and the four partial results are combined by (value, then lower c): the lowest index of the minimum.
+// with a strictly smaller value and the four partial results are combined by (value, then lower c): the lowest index of the minimum
+// (WaveBest, mtfjsp_wave_select.h).
 // The dominance loop reads copy c' at one address for the whole workgroup (a broadcast read: no bank conflict at any pitch).
 template <int OWN>
 __global__ __launch_bounds__(GRP_THREADS) void k_group_reduce(GroupArgs A)
@@ -123,30 +109,16 @@ __global__ __launch_bounds__(GRP_THREADS) void k_group_reduce(GroupArgs A)
     }
     __syncthreads();
     // ---- the smallest objective, lowest copy on ties (an eligible copy whose objective is NaN — infinite costs — is never picked)
-    double best = 0.0;
-    int bi = -1;
+    WaveBest<false> mine;
 #pragma unroll
     for (int i = 0; i < OWN; i++) {
         const int cw = wave * WAVE + i * GRP_THREADS;                       // (wave-uniform)
-        if (cw < K) {
-            const double v = ob[i];
-            const bool ok = v == v;
-            const double mn = grp_wave_min(ok ? v : (double)INFINITY);
-            const unsigned long long eq = __ballot(ok && v == mn);
-            if (eq && (bi < 0 || mn < best)) { best = mn; bi = cw + __ffsll((long long)eq) - 1; }
-        }
+        if (cw < K) mine.pass(ob[i] == ob[i], ob[i], cw);
     }
-    if (lane == 0) { part_v[wave] = best; part_i[wave] = bi; }
+    if (lane == 0) { part_v[wave] = mine.v; part_i[wave] = mine.i; }
     __syncthreads();
     if (tid == 0) {
-        double gb = 0.0;
-        int gi = -1;
-#pragma unroll
-        for (int q = 0; q < GRP_WAVES; q++) {
-            const double bq = part_v[q];
-            const int iq = part_i[q];
-            if (iq >= 0 && (gi < 0 || bq < gb || (bq == gb && iq < gi))) { gb = bq; gi = iq; }
-        }
+        const int gi = wave_best_combine<false, GRP_WAVES>(part_v, part_i).i;
         if (A.best) A.best[blockIdx.x] = gi < 0 ? -1 : (int)(g0 + gi);
         if (A.best_obj) A.best_obj[blockIdx.x] = gi < 0 ? (double)NAN : cp[gi].w;   // the copy's own word (the minimum may be a zero of the other sign)
     }
@@ -176,11 +148,12 @@ template <int OWN>
 static int group_launch(mtfjsp_handle_t h, const EnvHostView &v, int N, const GroupArgs &A)
 {
     const size_t lds = (size_t)A.K * 32;
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void *)k_group_reduce<OWN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_group_reduce: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    if (lds > 48 * 1024)
+        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)k_group_reduce<OWN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                                          "mtfjsp_group_reduce", "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
+            return rc;
     hipLaunchKernelGGL(k_group_reduce<OWN>, dim3((unsigned)N), dim3(GRP_THREADS), lds, v.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_group_reduce: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(h, "mtfjsp_group_reduce");
 }
 
 extern "C" int mtfjsp_group_reduce(mtfjsp_handle_t h, int32_t N, int32_t K, const double *cost4, const uint8_t *done, const double *w3cfg_host,
@@ -192,7 +165,7 @@ extern "C" int mtfjsp_group_reduce(mtfjsp_handle_t h, int32_t N, int32_t K, cons
         return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_group_reduce: 1 <= K <= 4096, N >= 1 and N*K must fit 31 bits");
     EnvHostView v;
     mtfjsp_env_host_view(h, &v);
-    if (hipSetDevice(v.device_id) != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_group_reduce: hipSetDevice failed");
+    if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_group_reduce")) return rc;
     GroupArgs A{};
     A.K = K; A.w_mk = w3cfg_host[0]; A.w_ec = w3cfg_host[1]; A.w_tt = w3cfg_host[2]; A.cost4 = cost4; A.done = done;
     A.obj = obj_out; A.best = best_out; A.best_obj = best_obj_out; A.front = front_out;

@@ -9,11 +9,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/mtfjsp.h"
 
 #include "mtfjsp_env_dev.h"
+#include "mtfjsp_wave_select.h"
 
 struct LaArgs {
     int B, J, M, T, MJ, column;
@@ -38,59 +38,29 @@ __global__ __launch_bounds__(256) void k_lookahead_actions(LaArgs A)
     }
 }
 
-// wave-wide maximum on the cross-lane data path (row shifts, then row_bcast:15 / :31: lane 63 holds the result), read back to every
-// lane.  Lanes without a source keep their own value.  All 64 lanes must be active.  fmax returns one of its operands: a comparison.
-#define LA_DPP(x, ctrl) __builtin_amdgcn_update_dpp((x), (x), (ctrl), 0xF, 0xF, false)
-__device__ __forceinline__ double la_wave_max(double x)
-{
-#define STEP_(ctrl)                                                                                     \
-    {                                                                                                  \
-        const int lo = LA_DPP(__double2loint(x), ctrl), hi = LA_DPP(__double2hiint(x), ctrl);          \
-        x = fmax(x, __hiloint2double(hi, lo));                                                         \
-    }
-    STEP_(0x111) STEP_(0x112) STEP_(0x114) STEP_(0x118) STEP_(0x142) STEP_(0x143)
-#undef STEP_
-    return rl_d(x, 63);
-}
-
 // ONE: T <= 64 — a single pass, straight-line.  Otherwise the copies are taken 64 at a time; a later pass wins only with a strictly
-// larger value, so the lowest index of the maximum is kept.
+// larger value, so the lowest index of the maximum is kept (WaveBest, mtfjsp_wave_select.h).
 template <bool ONE>
 __global__ __launch_bounds__(64) void k_lookahead_select(LaArgs A)
 {
     const int b = blockIdx.x, lane = threadIdx.x, T = A.T, M = A.M;
     const size_t base = (size_t)b * T;
-    double best = 0.0;
-    int bi = -1;
+    WaveBest<true> w;
     for (int c0 = 0; c0 < (ONE ? 1 : T); c0 += WAVE) {
         const int c = c0 + lane, cc = c < T ? c : T - 1;
         const int st = A.status[base + cc];
         const double v = A.raw[(base + cc) * 5 + A.column];
-        const bool ok = c < T && !(st & (MTFJSP_ST_INVALID | MTFJSP_ST_INFEASIBLE));
-        const double mx = la_wave_max(ok ? v : -INFINITY);
-        const unsigned long long eq = __ballot(ok && v == mx);
-        if (eq && (bi < 0 || mx > best)) { best = mx; bi = c0 + __ffsll((long long)eq) - 1; }
+        w.pass(c < T && !(st & (MTFJSP_ST_INVALID | MTFJSP_ST_INFEASIBLE)), v, c0);
     }
+    const int bi = w.i;
     const int j = bi < 0 ? 0 : bi / M;
     const int cnt = A.mj[(size_t)b * A.MJ + j].cnt;
     if (lane == 0) {
         A.task[b] = bi < 0 ? -1 : j * M + (cnt < M ? cnt : M - 1);
         A.mach[b] = bi < 0 ? -1 : bi - j * M;
         if (A.job) A.job[b] = bi < 0 ? -1 : j;
-        if (A.best) A.best[b] = bi < 0 ? (double)NAN : best;
+        if (A.best) A.best[b] = bi < 0 ? (double)NAN : w.v;
     }
-}
-
-static int la_views(const char *who, mtfjsp_handle_t scratch, mtfjsp_handle_t src, EnvHostView *sc, EnvHostView *so)
-{
-    mtfjsp_env_host_view(scratch, sc);
-    mtfjsp_env_host_view(src, so);
-    if (scratch == src || sc->J != so->J || sc->M != so->M || sc->device_id != so->device_id || (long)sc->B != (long)so->B * so->T) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: the scratch handle must be another handle of the same size on the same device with batch = source batch * T", who);
-        return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, msg);
-    }
-    return MTFJSP_OK;
 }
 
 extern "C" int mtfjsp_lookahead_expand(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_t *task_c, int32_t *mach_c)
@@ -98,15 +68,14 @@ extern "C" int mtfjsp_lookahead_expand(mtfjsp_handle_t scratch, mtfjsp_handle_t 
     if (!scratch) return MTFJSP_ERR_ARG;
     if (!src || !task_c || !mach_c) return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, "mtfjsp_lookahead_expand: null argument");
     EnvHostView sc, so;
-    int rc = la_views("mtfjsp_lookahead_expand", scratch, src, &sc, &so);
+    int rc = mtfjsp_env_pair_views("mtfjsp_lookahead_expand", "source", scratch, src, &sc, &so);
     if (rc) return rc;
     rc = mtfjsp_env_fork_launch(scratch, src, nullptr, so.T, MTFJSP_FORK_STATE, "mtfjsp_lookahead_expand");
     if (rc) return rc;
     LaArgs A{};
     A.B = so.B; A.J = so.J; A.M = so.M; A.T = so.T; A.MJ = so.MJ; A.mj = so.mj; A.task = task_c; A.mach = mach_c;
     hipLaunchKernelGGL(k_lookahead_actions, dim3((unsigned)(((size_t)sc.B + 255) / 256)), dim3(256), 0, sc.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(scratch, MTFJSP_ERR_HIP, "mtfjsp_lookahead_expand: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(scratch, "mtfjsp_lookahead_expand");
 }
 
 extern "C" int mtfjsp_lookahead_select(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_t column, int32_t *task_out, int32_t *mach_out,
@@ -116,16 +85,15 @@ extern "C" int mtfjsp_lookahead_select(mtfjsp_handle_t scratch, mtfjsp_handle_t 
     if (!src || !task_out || !mach_out) return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, "mtfjsp_lookahead_select: null argument");
     if (column < 0 || column > 4) return mtfjsp_env_fail(scratch, MTFJSP_ERR_ARG, "mtfjsp_lookahead_select: column must be 0..4 (reward, makespan, idle, energy, transport)");
     EnvHostView sc, so;
-    int rc = la_views("mtfjsp_lookahead_select", scratch, src, &sc, &so);
+    int rc = mtfjsp_env_pair_views("mtfjsp_lookahead_select", "source", scratch, src, &sc, &so);
     if (rc) return rc;
     if (!sc.was_reset || !so.was_reset) return mtfjsp_env_fail(scratch, MTFJSP_ERR_STATE, "mtfjsp_lookahead_select: both handles must hold a state (mtfjsp_lookahead_expand and a step first)");
     if (!sc.obs_bound || !sc.obs.raw) return mtfjsp_env_fail(scratch, MTFJSP_ERR_STATE, "mtfjsp_lookahead_select: the scratch handle needs bound observations with raw");
-    if (hipSetDevice(so.device_id) != hipSuccess) return mtfjsp_env_fail(scratch, MTFJSP_ERR_HIP, "mtfjsp_lookahead_select: hipSetDevice failed");
+    if ((rc = mtfjsp_env_set_device(scratch, so.device_id, "mtfjsp_lookahead_select"))) return rc;
     LaArgs A{};
     A.B = so.B; A.J = so.J; A.M = so.M; A.T = so.T; A.MJ = so.MJ; A.column = column; A.mj = so.mj;
     A.status = sc.obs.status; A.raw = sc.obs.raw; A.task = task_out; A.mach = mach_out; A.job = job_out; A.best = best_out;
     if (so.T <= WAVE) hipLaunchKernelGGL(k_lookahead_select<true>, dim3(so.B), dim3(WAVE), 0, so.stream, A);
     else hipLaunchKernelGGL(k_lookahead_select<false>, dim3(so.B), dim3(WAVE), 0, so.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(scratch, MTFJSP_ERR_HIP, "mtfjsp_lookahead_select: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(scratch, "mtfjsp_lookahead_select");
 }

@@ -22,6 +22,7 @@
 #include "../../include/mtfjsp.h"
 
 #include "mtfjsp_env_dev.h"
+#include "mtfjsp_wave_select.h"
 
 struct PdrArgs {
     int B, J, M, T;
@@ -34,28 +35,6 @@ struct PdrArgs {
 
 // LDS of one instance: v[T] f64 | refer[J] f64 | order[T] i32 | next[J] i32 | machine[T] u8
 static size_t pdr_lds_bytes(int J, int T) { return (size_t)T * 13 + (size_t)J * 12; }
-
-// wave-wide minimum on the cross-lane data path (four row shifts, then row_bcast:15 / :31: lane 63 holds the result), read back
-// to every lane.  Lanes without a source keep their own value.  All 64 lanes must be active.
-#define PDR_DPP(x, ctrl) __builtin_amdgcn_update_dpp((x), (x), (ctrl), 0xF, 0xF, false)
-__device__ __forceinline__ double pdr_wave_min(double x)
-{
-#define STEP_(ctrl)                                                                                       \
-    {                                                                                                    \
-        const int lo = PDR_DPP(__double2loint(x), ctrl), hi = PDR_DPP(__double2hiint(x), ctrl);          \
-        x = fmin(x, __hiloint2double(hi, lo));                                                           \
-    }
-    STEP_(0x111) STEP_(0x112) STEP_(0x114) STEP_(0x118) STEP_(0x142) STEP_(0x143)
-#undef STEP_
-    return rl_d(x, 63);
-}
-__device__ __forceinline__ int pdr_wave_min(int x)
-{
-#define STEP_(ctrl) { const int y = PDR_DPP(x, ctrl); x = y < x ? y : x; }
-    STEP_(0x111) STEP_(0x112) STEP_(0x114) STEP_(0x118) STEP_(0x142) STEP_(0x143)
-#undef STEP_
-    return rl_i(x, 63);
-}
 
 // REG: J <= 64 — lane j keeps refer[j] and the job's next operation in registers, and a selection is one reduction, one ballot
 // and one LDS read by the owner lane.  Otherwise both live in LDS and every lane scans the jobs j = lane, lane + 64, ...
@@ -123,7 +102,7 @@ __global__ __launch_bounds__(64) void k_pdr_plan(PdrArgs A)
         int nx = 0;
         for (int s = 0; s < T; s++) {
             const double key = lane < J ? (most ? -rf : rf) : INFINITY;     // argmax(x) == argmin(-x), ties included
-            const double mn = pdr_wave_min(key);
+            const double mn = wave_ext<false>(key);
             const unsigned long long eq = __ballot(lane < J && key == mn);
             const int jj = eq ? __ffsll((long long)eq) - 1 : 0;             // first index; every value +inf: index 0
             if (lane == jj) {
@@ -145,8 +124,8 @@ __global__ __launch_bounds__(64) void k_pdr_plan(PdrArgs A)
                 const double key = most ? -refer[j] : refer[j];
                 if (bj == INT_MAX || key < best) { best = key; bj = j; }
             }
-            const double mn = pdr_wave_min(best);
-            const int jj = pdr_wave_min(best == mn ? bj : INT_MAX);         // lanes >= J: (inf, INT_MAX)
+            const double mn = wave_ext<false>(best);
+            const int jj = wave_min(best == mn ? bj : INT_MAX);         // lanes >= J: (inf, INT_MAX)
             if (lane == 0) {
                 const int nx = next[jj], k = nx < M ? nx : M - 1;
                 order[s] = jj * M + k;
@@ -177,7 +156,7 @@ extern "C" int mtfjsp_pdr_plan(mtfjsp_handle_t h, const int32_t *o_rule, const i
     if (!e.loaded) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_pdr_plan: no instances loaded or generated");
     const size_t lds = pdr_lds_bytes(e.J, e.T);
     if (lds > 64 * 1024) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_pdr_plan: instance too large (13*T + 12*J bytes of LDS must fit 64 KiB)");
-    if (hipSetDevice(e.device_id) != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_pdr_plan: hipSetDevice failed");
+    if (int rc = mtfjsp_env_set_device(h, e.device_id, "mtfjsp_pdr_plan")) return rc;
     {   // the rule ids are device data, and a bad one must leave the outputs untouched: they are read back and checked before the launch
         std::vector<int32_t> r(2 * (size_t)e.B);
         if (hipMemcpyAsync(r.data(), o_rule, (size_t)e.B * 4, hipMemcpyDeviceToHost, e.stream) != hipSuccess ||
@@ -195,6 +174,5 @@ extern "C" int mtfjsp_pdr_plan(mtfjsp_handle_t h, const int32_t *o_rule, const i
     PdrArgs A{e.B, e.J, e.M, e.T, e.t, e.p, o_rule, m_rule, mor_order, seed, task_out, mach_out};
     if (e.J <= WAVE) hipLaunchKernelGGL(k_pdr_plan<true>, dim3(e.B), dim3(WAVE), lds, e.stream, A);
     else hipLaunchKernelGGL(k_pdr_plan<false>, dim3(e.B), dim3(WAVE), lds, e.stream, A);
-    if (hipGetLastError() != hipSuccess) return mtfjsp_env_fail(h, MTFJSP_ERR_HIP, "mtfjsp_pdr_plan: launch failed");
-    return MTFJSP_OK;
+    return mtfjsp_env_launched(h, "mtfjsp_pdr_plan");
 }

@@ -15,6 +15,49 @@ from . import capi
 from .batch_env import DeviceBatchEnv
 
 
+COST_KEYS = ("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")
+
+
+def parse_args(args, **env_kw):
+    """The reference's config dict `args` (n_job, n_machine, n_edge, weight_mk, weight_ec, weight_tt, reward_scaling) -> (J, M, E, T,
+    w, kw): the sizes, the three weights as floats and `DeviceBatchEnv`'s keywords (w_cfg, scaling_divisor and `env_kw`)."""
+    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
+    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
+    scal = args.get("reward_scaling", {}) or {}
+    return J, M, E, J * M, w, dict(env_kw, w_cfg=w, scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+
+
+def episode_results(cum, prev, T, w):
+    """cum [N,5]: the summed raw step rewards (reward, r_mk, r_idle, r_pt, r_tt); prev [N,4]: mk, e1, transT, idle of the finished
+    schedule (STATE_PREV_COSTS); w: (w_mk, w_ec, w_tt) -> (cost_dict_cumsum, Final_4cost [N,4], Objective [N]) as
+    `validate_cost_batched` documents them (validate.py:277-297, test_all.py:536-538).  Pure numpy: no device, no state."""
+    cost = {key: cum[:, i] for i, key in enumerate(COST_KEYS)}
+    final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
+    obj = w[0] * final4[:, 0] + w[1] * (final4[:, 1] + final4[:, 3]) + w[2] * final4[:, 2]
+    return cost, final4, obj
+
+
+def replay_episode(env, T, actions, what):
+    """T steps of the reset handle `env`, step s with the (task, mach) [B] int32 device tensors `actions(s)` returns, the raw rewards
+    summed on the device; one synchronisation, then RuntimeError("<what> rollout: ...") if an instance met an invalid action or an
+    infeasible machine, or did not finish.  -> (cum [B,5], prev [B,4]) host arrays: `episode_results`' inputs."""
+    dev = env.device
+    cum = torch.zeros(env.B, 5, dtype=torch.float64, device=dev)
+    bad = torch.zeros(env.B, dtype=torch.int32, device=dev)
+    for s in range(T):
+        env.step(*actions(s))
+        cum += env.raw                                                  # reward, r_mk, r_idle, r_pt, r_tt (env:1051-1171), in step order
+        bad |= env.status
+    torch.cuda.synchronize(dev)
+    n_bad = int((bad & (capi.ST_INVALID | capi.ST_INFEASIBLE)).ne(0).sum().item())
+    if n_bad:
+        raise RuntimeError(f"{what} rollout: {n_bad} instance(s) met an invalid action or an infeasible machine")
+    if not bool(env.info[:, 1].all().item()):
+        raise RuntimeError(f"{what} rollout: an episode did not finish after T steps")
+    prev = env.read_state(capi.STATE_PREV_COSTS)                        # mk, e1, transT, idle of the finished schedule (pdrs:808-812)
+    return cum.cpu().numpy(), prev
+
+
 def validate_cost_batched(weights, t, p, tt, edge, args, greedy=True, device=0, obs_dtype="f32", actor=None,
                           forced_actions=None, on_step=None, on_action=None):
     """weights: (job_actor_state_dict, machine_actor_state_dict) with the reference's key names (or an `ActorPair` via
@@ -30,14 +73,10 @@ def validate_cost_batched(weights, t, p, tt, edge, args, greedy=True, device=0, 
       Objective         [B]:   w_mk*mk + w_ec*(pt + idle) + w_tt*transT
     """
     from . import encoder as enc_mod
-    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
-    T = J * M
+    J, M, E, T, w, kw = parse_args(args, obs_dtype=obs_dtype, device=device)
     t = np.asarray(t, np.float64)
     B = t.shape[0]
-    scal = args.get("reward_scaling", {}) or {}
-    env = DeviceBatchEnv(J, M, E, B, obs_dtype=obs_dtype, device=device,
-                         w_cfg=(float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"])),
-                         scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
+    env = DeviceBatchEnv(J, M, E, B, **kw)
     env.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
     env.scaler_init()                                               # the scaled components are produced but not used here
     dev = env.device
@@ -45,7 +84,7 @@ def validate_cost_batched(weights, t, p, tt, edge, args, greedy=True, device=0, 
         actor = enc_mod.ActorPair(J, M, B, device=device, obs_dtype=obs_dtype, weights=weights, greedy=greedy, seed=0)
     actor.enc.set_bn_mode(True)
     try:
-        w3 = torch.tensor([[args["weight_mk"], args["weight_ec"], args["weight_tt"]]], dtype=torch.float64, device=dev).repeat(B, 1)
+        w3 = torch.tensor([w], dtype=torch.float64, device=dev).repeat(B, 1)
         env.reset(w3)                                               # env:1262 Random_weight_type="eval"
         actor.begin_episode()
         task = torch.zeros(B, dtype=torch.int32, device=dev); mach = torch.zeros_like(task); job = torch.zeros_like(task)
@@ -72,14 +111,8 @@ def validate_cost_batched(weights, t, p, tt, edge, args, greedy=True, device=0, 
         prev = env.read_state(capi.STATE_PREV_COSTS)                # mk, e1, transT, idle of the finished schedule (validate.py:277-281)
     finally:
         actor.enc.set_bn_mode(False)
-    c = cum.cpu().numpy()
-    cost = {"opr_Gt": c[:, 0], "opr_mk": c[:, 1], "opr_idleT": c[:, 2], "opr_pt": c[:, 3], "opr_transT": c[:, 4]}
-    final4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
-    obj = args["weight_mk"] * final4[:, 0] + args["weight_ec"] * (final4[:, 1] + final4[:, 3]) + args["weight_tt"] * final4[:, 2]
-    return cost, final4, obj
+    return episode_results(cum.cpu().numpy(), prev, T, w)
 
-
-COST_KEYS = ("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")
 
 
 def best_of_k_rollout(t, p, tt, edge, args, K, policy, w3=None, chunk=None, device=0, obs_dtype="f32", left_shift=True, what="best-of-K",
@@ -92,8 +125,8 @@ def best_of_k_rollout(t, p, tt, edge, args, K, policy, w3=None, chunk=None, devi
     pass's reset, `decide(...)` per step, `close()` at the end.  on_event(event, env, first_instance, hist_task, hist_mach) (tests): called
     with "reset" after every pass's reset and with "end" after its last step, the handle of copies and the [T, n*K] device histories.
     -> the dict `sample_best_of_k` documents, plus `cum` [N,K,5]: every copy's summed raw rewards."""
-    J, M, E = int(args["n_job"]), int(args["n_machine"]), int(args["n_edge"])
-    T, K = J * M, int(K)
+    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    K = int(K)
     if not 1 <= K <= 4096:
         raise ValueError("K must be 1..4096")
     t = np.asarray(t, np.float64)
@@ -102,9 +135,6 @@ def best_of_k_rollout(t, p, tt, edge, args, K, policy, w3=None, chunk=None, devi
     if n < 1:
         raise ValueError("chunk must be at least 1")
     n = min(n, N)
-    w = (float(args["weight_mk"]), float(args["weight_ec"]), float(args["weight_tt"]))
-    scal = args.get("reward_scaling", {}) or {}
-    kw = dict(left_shift=left_shift, obs_dtype=obs_dtype, device=device, w_cfg=w, scaling_divisor=float(scal.get("scaling_divisor", 1.0)))
     src = DeviceBatchEnv(J, M, E, N, **kw)
     env = top = None
     opened = False

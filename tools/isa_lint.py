@@ -23,8 +23,13 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "e2e-mappo-for-mt-fjsp_amd", "csrc")
-SOURCES = ["mtfjsp_env.hip", "mtfjsp_encoder.hip", "mtfjsp_gin_res.hip", "mtfjsp_pdr.hip", "mtfjsp_lookahead.hip"]
+sys.path.insert(0, ROOT)
+import mtfjsp_amd  # noqa: E402,F401  (the package directory's import alias)
+from importlib import import_module  # noqa: E402
+
+_build = import_module("e2e-mappo-for-mt-fjsp_amd._build")
+CSRC = _build.CSRC
+SOURCES = [s for s in _build.SOURCES if s.endswith(".hip")]         # every kernel source the library is built from
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-S", "--cuda-device-only", "-w"]
 PK_F32 = re.compile(r"^\s*(v_pk_(?:mul|add|fma)_f32)\b(.*)$")
 OP_SEL = re.compile(r"op_sel:\[([01]),([01])")
@@ -115,5 +120,5 @@ if __name__ == "__main__":
         print(f"{src}: {kernel}: line {n}: {ins}")
     for kernel, what, n in stream_bad:
         print(f"mtfjsp_encoder.hip: {kernel}: {what} (found {n})")
-    print(f"isa_lint: {len(bad)} unreliable packed-f32 operand swizzle(s), {len(stream_bad)} streaming-load mismatch(es)" + (" with " + " ".join(sys.argv[1:]) if sys.argv[1:] else ""))
+    print(f"isa_lint: {len(SOURCES)} .hip units, {len(bad)} unreliable packed-f32 operand swizzle(s), {len(stream_bad)} streaming-load mismatch(es)" + (" with " + " ".join(sys.argv[1:]) if sys.argv[1:] else ""))
     sys.exit(1 if bad or stream_bad else 0)
