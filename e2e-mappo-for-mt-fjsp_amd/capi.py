@@ -122,6 +122,9 @@ PROTOTYPES = {
     "mtfjsp_gin_res_kernel_name_for": (C.c_char_p, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_gin_res_kernel_name": (C.c_char_p, [_VP]),
     "mtfjsp_encoder_peek_gin_res_host": (_I, [_VP, _VP, C.c_int64, _VP, _VP]),
+    "mtfjsp_fused3_kernel_name_for": (C.c_char_p, [C.c_int32] * 6 + [C.POINTER(C.c_int32)]),
+    "mtfjsp_encoder_fused3_kernel_name": (C.c_char_p, [_VP]),
+    "mtfjsp_encoder_peek_fused3_host": (_I, [_VP, _VP, _VP]),
     "mtfjsp_encoder_range_fallbacks": (_I, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_peek_nodes_host": (_I, [_VP, _VP, C.c_int64]),
     "mtfjsp_encoder_timing_begin": (_I, [_VP]),
@@ -172,3 +175,11 @@ def gin_res_kernel_for(batch, n_job, n_machine, num_cu=256, candidates=None, nod
     name = lib().mtfjsp_gin_res_kernel_name_for(batch, n_job * n_machine, n_job, n_job if candidates is None else candidates, num_cu,
                                                 int(bool(node_output)), C.byref(ipc), C.byref(grid))
     return (name.decode() if name else None), ipc.value, grid.value
+
+
+def fused3_kernel_for(batch, n_job, n_machine, num_cu=256, obs_f64=False, env_tail=False):
+    """(kernel name or None, workgroups): which instantiation of the three-in-one heads launch serves a rollout step of this shape — the library's
+    own rule (csrc/mtfjsp_fused3_select.h), no GPU needed.  MTFJSP_FUSED3_GENERIC=1 in the environment forces the run-time kernel."""
+    grid = C.c_int32(0)
+    name = lib().mtfjsp_fused3_kernel_name_for(batch, n_job, n_machine, num_cu, int(bool(obs_f64)), int(bool(env_tail)), C.byref(grid))
+    return (name.decode() if name else None), grid.value

@@ -1971,12 +1971,19 @@ __global__ __launch_bounds__(512) void k_headsx_gat3x(HeadArgs HA, GatArgs GA)
 #define GAT_PRE_END (GAT_F2_OFF + 16 * 8 * 8 * 4)
 // this workgroup's m_fea2 rows (written by the environment step a rollout step ago: the memory-side cache by now) are requested at the top of
 // the launch — the last of the first phase's requests, by every thread (waves 0-3 drop theirs) — and wait in four registers
-__device__ __forceinline__ void gat_f2_load(const GatArgs &G, int t, int M, float (&x)[4])
+// (fx: every workgroup has 16 full instances of f32 observations — no clamp against the end of the array, no f64 form)
+__device__ __forceinline__ void gat_f2_load(const GatArgs &G, int t, int M, float (&x)[4], const bool fx = false)
 {
     const size_t base = (size_t)blockIdx.x * 16 * M * 8, total = (size_t)G.R * 8;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const size_t idx = base + (size_t)(i * 256 + t), ic = idx < total ? idx : total - 1;
+        const size_t idx = base + (size_t)(i * 256 + t);
+        if (fx) {
+            x[i] = reinterpret_cast<const float *>(G.f2)[i * 256 + t < 16 * M * 8 ? idx : base];
+            if (!(i * 256 + t < 16 * M * 8)) x[i] = 0.f;
+            continue;
+        }
+        const size_t ic = idx < total ? idx : total - 1;
         x[i] = G.feat_f64 ? (float)reinterpret_cast<const double *>(G.f2)[ic] : reinterpret_cast<const float *>(G.f2)[ic];
         if (!(i * 256 + t < 16 * M * 8 && idx < total)) x[i] = 0.f;
     }
@@ -2003,6 +2010,7 @@ __device__ __forceinline__ void gat_prestage(const GatArgs &G, unsigned char *sm
 // (Requesting one word of every line gat_prestage() reads at the top of the launch, so that they wait in this XCD's L2 — they were last
 // read a rollout step ago — shortened it by 2 us and lengthened the first phase of the job heads by 0.5 us: the launch ended 0.7-1.2 us
 // later in alternating runs on one box, because the selection on waves 0-3, not this copy, ends the heads part.  Not kept.)
+#include "mtfjsp_fused3_select.h"
 #if !MTFJSP_BODY_FUNCS
 // ENV (round 6): 0 = the three parts; 1 / 2 = + the environment step of the workgroup's 16 instances as the launch's tail (f32 / f64
 // observations; mtfjsp_env_grp.h's own code with the instances dealt to the 8 waves: bit-identical to k_env_grp16).  Two launches per
@@ -2011,11 +2019,46 @@ __device__ __forceinline__ void gat_prestage(const GatArgs &G, unsigned char *sm
 // heads' part, 13 us ahead of the tail, and waits in this XCD's L2.
 // NLDS (round 6): the GAT part's node rows stay in LDS for the machine part (M <= 6: at most 12 tiles, each wave's tiles in buffers of their
 // own, and the machine part stages its rows by instance) — 12.6 MB per launch less written and 12.6 MB less read back.
-template <int ENV, bool NLDS>
+// SH (round 8): the shape the heads and GAT statements see.  H3ShapeAny: everything from the kernel arguments, as before.  H3ShapeFixed<J, M, 16>: the
+// shape as compile-time constants (mtfjsp_fused3_select.h states when the host may launch it; launch_heads checks the arguments' half) — the statements
+// read it through the HX_FX / GAT_FX macros of the body headers, whose defaults are the run-time expressions, so no other kernel changes.  One item,
+// with a -D switch for A/B builds (0: the run-time code): H3_FX_DROP — the chunk loop and its reload path, the row-valid and group-size selects, the
+// null-pointer alternatives, the non-row-wise selection, the f64 branches, the GAT part's tile bookkeeping and its one-tile-at-a-time loop.
+// (Measured and not kept, profiles/HISTORY.md round 8: the selection's straight-line forms — unrolled scan, total by a DPP row broadcast, the job
+// position by a multiply-high, m_fea1 without its loop.)
+#ifndef H3_FX_DROP
+#define H3_FX_DROP 1
+#endif
+struct H3ShapeAny { static constexpr bool fixed = false; static constexpr int J = 0, M = 0, T = 0, PER = 0; };
+template <int J_, int M_, int IPC_>
+struct H3ShapeFixed {
+    static constexpr bool fixed = true;
+    static constexpr int J = J_, M = M_, T = J_ * M_, PER = 2 * M_ * IPC_ / 16;          // PER: GAT row tiles per workgroup (two nodes per machine)
+    static_assert(IPC_ == HG, "the heads statements take 16 instances per workgroup");
+    static_assert(J_ <= HCH && M_ <= HCH, "one chunk of scorer tiles; the machine part stages its rows by instance");
+    static_assert(PER > 8 && PER <= 12, "the paired GAT tiles: every tile with an LDS buffer of its own");
+};
+typedef H3ShapeFixed<FUSED3_FX_J, FUSED3_FX_M, FUSED3_FX_IPC> H3ShapeHeadline;
+template <int ENV, bool NLDS, class SH = H3ShapeAny>
 __global__ __launch_bounds__(512) void k_headsx_gat3x_headsx(HeadArgs HA, GatArgs GA, HeadArgs HM, XchgArgs XG, EnvParams EP)
 {
+    static_assert(!SH::fixed || (ENV == 0 && NLDS && GAT_PAIRED), "the fixed shape: no environment tail, node rows in LDS, paired GAT tiles");
     extern __shared__ __align__(16) unsigned char smem[];
     const XchgArgs &XA = XG;
+#undef HX_FX
+#undef HX_FX_JOB
+#undef HX_FX_R
+#undef HX_FX_T
+#undef HX_FX_M
+#define HX_FX (SH::fixed && H3_FX_DROP != 0)
+#define HX_FX_JOB true
+#define HX_FX_R (SH::J)
+#define HX_FX_T (SH::T)
+#define HX_FX_M (SH::M)
+#undef GAT_FX
+#undef GAT_FX_PER
+#define GAT_FX (SH::fixed && H3_FX_DROP != 0)
+#define GAT_FX_PER (SH::PER)
     X3_RT(0);
     for (int i = blockIdx.x * 512 + threadIdx.x; i < XW_SET; i += (int)gridDim.x * 512) XA.words_next[i] = 0ull;
 #ifdef MTFJSP_STAMP3
@@ -2030,10 +2073,10 @@ __global__ __launch_bounds__(512) void k_headsx_gat3x_headsx(HeadArgs HA, GatArg
     {
         const HeadArgs &A = HA;
 #ifndef GAT_F2_LATE
-#define HX_TOP_HOOK float gf2[4]; gat_f2_load(GA, tid & 255, A.mf.M, gf2);
+#define HX_TOP_HOOK float gf2[4]; gat_f2_load(GA, tid & 255, HX_FX ? HX_FX_M : A.mf.M, gf2, HX_FX);
 #define HX_IDLE_HOOK gat_prestage(GA, smem, tid - 256, gf2);
 #else                                                              // (diagnostic builds: the rows requested where they are stored, as before)
-#define HX_IDLE_HOOK float gf2[4]; gat_f2_load(GA, tid - 256, A.mf.M, gf2); gat_prestage(GA, smem, tid - 256, gf2);
+#define HX_IDLE_HOOK float gf2[4]; gat_f2_load(GA, tid - 256, HX_FX ? HX_FX_M : A.mf.M, gf2, HX_FX); gat_prestage(GA, smem, tid - 256, gf2);
 #endif
 #define HX_MF1_LDS reinterpret_cast<float *>(smem + GAT_F1_OFF)
 #include "mtfjsp_headsx_body.h"
@@ -2084,6 +2127,10 @@ __global__ __launch_bounds__(512) void k_headsx_gat3x_headsx(HeadArgs HA, GatArg
 #undef H3_BASE
 #define H3_BASE 1024
 #endif
+#undef HX_FX_JOB
+#define HX_FX_JOB false
+#undef HX_FX_R
+#define HX_FX_R (SH::M)
     {
         const HeadArgs &A = HM;
 #undef HX_XCHG
@@ -2106,6 +2153,20 @@ __global__ __launch_bounds__(512) void k_headsx_gat3x_headsx(HeadArgs HA, GatArg
 #endif
 #undef BODY_TID
 #define BODY_TID threadIdx.x
+#undef HX_FX
+#undef HX_FX_JOB
+#undef HX_FX_R
+#undef HX_FX_T
+#undef HX_FX_M
+#define HX_FX false
+#define HX_FX_JOB false
+#define HX_FX_R 0
+#define HX_FX_T 0
+#define HX_FX_M 0
+#undef GAT_FX
+#undef GAT_FX_PER
+#define GAT_FX false
+#define GAT_FX_PER 0
     X3_RT(7);
     if (ENV) {
         asm volatile("" :: "v"(env_warm));
@@ -2929,6 +2990,7 @@ struct mtfjsp_encoder {
     unsigned long long *xw = nullptr;       // [2 sets][XW_SET] count-carrying words of that exchange; forward n uses set n & 1 and zeroes the other
     unsigned long long xw_epoch = 0;
     long long fused3_launches = 0;
+    int fused3_last_kernel = -1;            // Fused3Kernel of the last three-in-one launch (mtfjsp_encoder_fused3_kernel_name)
     double xchg_fine_limit = getenv("MTFJSP_XCHG_FINE_LIMIT") ? atof(getenv("MTFJSP_XCHG_FINE_LIMIT")) : 2147483648.0;   // diagnostic: a lower limit sends ordinary contributions through the wide-range words
     long long fused3_fail_at = getenv("MTFJSP_FUSED3_FAIL_AT") ? atoll(getenv("MTFJSP_FUSED3_FAIL_AT")) : 0;   // diagnostic: this three-in-one launch waits for a workgroup that does not exist
     bool heads_hg8 = !getenv("MTFJSP_NO_HEADS_HG8");
@@ -3171,6 +3233,7 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
     (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
+    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<0, true, H3ShapeHeadline>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
     if (hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)fused3_lds_bytes()) != hipSuccess) e->fuse_mheads = false;
@@ -4087,12 +4150,26 @@ static void launch_heads(mtfjsp_encoder *e, HeadArgs &ha, const std::string &pol
 #endif
             // the node rows stay in LDS where every tile has a buffer of its own (<= 12 tiles per workgroup: M <= 6) and the machine part stages
             // its rows by instance (R <= HCH); MTFJSP_FUSED3_NODES_HBM=1: the round-5 form (rows written to e->node and read back)
+            // Which instantiation: the rule of mtfjsp_fused3_select.h (MTFJSP_FUSED3_GENERIC as it is NOW) on the shape, and — for the fixed one — what its
+            // statements take for granted of the three argument blocks: the headline rollout step's job part (embeddings from the single-launch GIN kernel: no
+            // gather / BatchNorm of X here; an armed selection with gather_from, gathered_out and logp_out; m_fea1 of the pick, f32) and machine part.
             const int gtiles = (2 * ha.B * fused_mheads->R + 15) / 16, gper = (gtiles + grid - 1) / grid;
-            const bool nlds = e->nodes_lds && gper <= 12 && fused_mheads->R <= HCH && (fused3_lds_bytes() >= (size_t)(8 * 2 * 4 * 64 * 16 + gper * 16 * HD * 4));
+            const bool obs_f64 = env_tail ? !env_tail->obs_f32 : (fused_gat->feat_f64 || !ha.mf.obs_f32);
+            const Fused3Plan pl = fused3_plan(ha.B, ha.R, fused_mheads->R, ha.mf.T, e->num_cu, obs_f64, e->nodes_lds ? nullptr : "1", env_tail != nullptr, getenv("MTFJSP_FUSED3_GENERIC"));
+            const bool nlds = pl.nodes_lds && (fused3_lds_bytes() >= (size_t)(8 * 2 * 4 * 64 * 16 + gper * 16 * HD * 4));
+            const HeadArgs &hm = *fused_mheads;
+            const bool fx_args = GAT_PAIRED && nlds && ha.hg == HG && hm.hg == HG && fused_gat->R == ha.B * hm.R && !fused_gat->feat_f64 &&
+                                 !ha.xgather && !ha.xbn_stats && !ha.xrelu && !ha.zero_stats && !ha.zero_stats2 && ha.pooled && ha.sample_mode && ha.gather_from && ha.gathered_out &&
+                                 ha.logp_out && ha.mf_on && ha.mf.obs_f32 && ha.mf.M == hm.R &&
+                                 !hm.xgather && hm.xbn_stats && !hm.xrelu && !hm.zero_stats && !hm.zero_stats2 && hm.sample_mode && hm.logp_out && !hm.gather_from && !hm.mf_on;
+            const Fused3Kernel k3 = (pl.eligible && pl.kernel == FUSED3_K_J6M6X16 && fx_args) ? FUSED3_K_J6M6X16 : FUSED3_K_ANY;
+            e->fused3_last_kernel = (int)k3;
             const EnvParams ep0 = env_tail ? *env_tail : EnvParams{};
             const int envm = !env_tail ? 0 : env_tail->obs_f32 ? 1 : 2;
 #define L3(EV, NL) hipLaunchKernelGGL((k_headsx_gat3x_headsx<EV, NL>), dim3(grid), dim3(512), fused3_lds_bytes(), e->stream, ha, *fused_gat, *fused_mheads, xg, ep0)
-            if (nlds) { if (envm == 0) L3(0, true); else if (envm == 1) L3(1, true); else L3(2, true); }
+            if (k3 == FUSED3_K_J6M6X16)
+                hipLaunchKernelGGL((k_headsx_gat3x_headsx<0, true, H3ShapeHeadline>), dim3(grid), dim3(512), fused3_lds_bytes(), e->stream, ha, *fused_gat, *fused_mheads, xg, ep0);
+            else if (nlds) { if (envm == 0) L3(0, true); else if (envm == 1) L3(1, true); else L3(2, true); }
             else { if (envm == 0) L3(0, false); else if (envm == 1) L3(1, false); else L3(2, false); }
 #undef L3
 #ifdef MTFJSP_STAMP3
@@ -4559,6 +4636,29 @@ extern "C" const char *mtfjsp_gin_res_kernel_name_for(int32_t batch, int32_t row
 extern "C" const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e)
 {
     return e && e->res_last_kernel >= 0 ? GIN_RES_KERNEL_NAME[e->res_last_kernel] : nullptr;
+}
+extern "C" const char *mtfjsp_fused3_kernel_name_for(int32_t batch, int32_t n_job, int32_t n_machine, int32_t num_cu, int32_t obs_f64, int32_t env_tail, int32_t *grid_out)
+{
+    const Fused3Plan pl = fused3_plan(batch, n_job, n_machine, n_job * n_machine, num_cu, obs_f64 != 0, getenv("MTFJSP_FUSED3_NODES_HBM"), env_tail != 0, getenv("MTFJSP_FUSED3_GENERIC"));
+    if (grid_out) *grid_out = pl.grid;
+    return pl.eligible ? FUSED3_KERNEL_NAME[pl.kernel] : nullptr;
+}
+extern "C" const char *mtfjsp_encoder_fused3_kernel_name(mtfjsp_encoder_t e)
+{
+    return e && e->fused3_last_kernel >= 0 ? FUSED3_KERNEL_NAME[e->fused3_last_kernel] : nullptr;
+}
+// diagnostic: the exchange words of the last three-in-one launch ([fine | wide][8 dispatch groups][sum | sumsq of 128 columns] u64, each with its arrival
+// count in the top 6 bits) and the (time-out, range) words
+extern "C" int mtfjsp_encoder_peek_fused3_host(mtfjsp_encoder_t e, uint64_t *words_host, uint32_t *flags_host)
+{
+    if (!e) return MTFJSP_ERR_ARG;
+    if (!e->xw || e->xw_epoch == 0 || e->fused3_last_kernel < 0) { e->err = "no three-in-one heads launch on this handle yet"; return MTFJSP_ERR_STATE; }
+    HIPCHK(e, hipSetDevice(e->cfg.device_id));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (words_host)                                                // the set the last launch added to (it zeroed the other one for the launch after it)
+        HIPCHK(e, hipMemcpy(words_host, e->xw + (size_t)((e->xw_epoch - 1) & 1) * XW_SET, (size_t)XW_SET * 8, hipMemcpyDeviceToHost));
+    if (flags_host) { flags_host[0] = e->res_fail_host ? e->res_fail_host[0] : 0u; flags_host[1] = e->res_fail_host ? e->res_fail_host[1] : 0u; }
+    return MTFJSP_OK;
 }
 extern "C" int mtfjsp_encoder_resident_failures(mtfjsp_encoder_t e, int64_t *count_out)
 {

@@ -9,6 +9,10 @@
 #ifndef GAT_NLDS
 #define GAT_NLDS false                                            // k_headsx_gat3x_headsx<., true>: the node rows stay in LDS for the machine heads of this launch (round 6)
 #endif
+#ifndef GAT_FX
+#define GAT_FX false                                              // k_headsx_gat3x_headsx<0, true, H3ShapeFixed<J, M, 16>>: every workgroup has GAT_FX_PER full row tiles (2 M: its 16
+#define GAT_FX_PER 0                                              // instances' machines), 9..12 of them — the paired form; the one-tile-at-a-time loop is not compiled in
+#endif
     unsigned char *s_wf = smem;                                   // 8*2*4*64*16 B
     float *s_a = reinterpret_cast<float *>(smem + 8 * 2 * 4 * 64 * 16);   // 8 waves * 16 * 128, swizzled
     const int tid = BODY_TID, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -41,9 +45,9 @@
     float *my_f = my_a + 15 * HD;                                 // the tile's feature words live in its last row until that row is written (p = 7)
     const int N = 2 * A.R;
     const int ntiles = (N + 15) / 16;
-    const int per = (ntiles + gridDim.x - 1) / gridDim.x;
+    const int per = GAT_FX ? GAT_FX_PER : (ntiles + gridDim.x - 1) / gridDim.x;
     const int first = blockIdx.x * per;
-    const int last = first + per < ntiles ? first + per : ntiles;
+    const int last = GAT_FX ? first + per : first + per < ntiles ? first + per : ntiles;
     float st_sum[8], st_sq[8];                                    // per lane: <= 2 machines x (tiles per wave) values — f32 partial sums, f64 from the fold on
     for (int c = 0; c < 8; c++) { st_sum[c] = 0.f; st_sq[c] = 0.f; }
     // input projection (+ the first pass' h W, folded on the host) on the f32 matrix instruction (round 5: it was 128 two-wide FMAs per
@@ -150,7 +154,10 @@
 #pragma unroll
             for (int c = 0; c < 8; c++) {
                 const float z1 = acc[c][i + 1];
-                const f32x2 pz = f32x2{acc[c][i], z1} * alv;
+                f32x2 pz = f32x2{acc[c][i], z1} * alv;
+                // (GAT_FX: with the tile bookkeeping constant hipcc hoists the first column block's pz[0] + pz[1] out of both arms of `pass < 2` and
+                // forms it as the swizzled packed add that tools/isa_lint.py refuses — the two products leave the packed multiply as scalars)
+                if (GAT_FX) asm volatile("" : "+v"(pz[0]), "+v"(pz[1]));
                 // ELU after passes 1 and 2 (ac:409-413) of the pair (mixture, node 1's own row): x > 0 ? x : exp(x) - 1 with the two
                 // multiplications by log2(e) and the two "- 1" as two-wide instructions; |err| < 2e-7; the select (not a max) keeps a NaN
                 float n0 = pz[0] + pz[1];
@@ -163,7 +170,7 @@
                 my_a[gx_off(r + 1, c * 16 + m)] = nv[1] > 0.f ? nv[1] : em[1];
             }
         } else {
-            const bool valid = row0 + r < N;
+            const bool valid = GAT_FX || row0 + r < N;
             // GAT_NLDS (round 6): the machine heads that follow in this launch are the ONLY reader of this workgroup's node rows, and
             // workgroup g owns the same 16 instances in both parts — the rows go into the FIRST half of the tile's own buffer (dead once
             // its last products have read it; 8 node rows x 128 f32 = 4 KB) instead of 12.6 MB per launch to memory and back.
@@ -171,7 +178,8 @@
 #pragma unroll
             for (int c = 0; c < 8; c++) {
                 const float z1 = acc[c][i + 1];
-                const f32x2 pz = f32x2{acc[c][i], z1} * alv;
+                f32x2 pz = f32x2{acc[c][i], z1} * alv;
+                if (GAT_FX) asm volatile("" : "+v"(pz[0]), "+v"(pz[1]));
                 float mv = (pz[0] + pz[1] + z1) * 0.5f;              // mean over the 2 nodes (ac:420)
                 nd[c * 16] = mv;
                 if (!valid) mv = 0.f;
@@ -187,7 +195,7 @@
     // instructions of both tiles (the tiles are bound by those reads: profiles/r05_ablate_gat.txt) and no wave is left alone with a second tile
     // while the others idle.  The staged images and feature rows lie where tile buffers 8, 9 are: they are read into registers first, then one
     // barrier releases the buffers.  Per accumulator the products arrive in the same order as in the loop below: the same bits.
-    const bool paired = per > 8 && per <= 12;
+    const bool paired = GAT_FX || (per > 8 && per <= 12);
     if (paired) {
         auto run = [&](auto NTc) __attribute__((always_inline)) {
             constexpr int NT = decltype(NTc)::value;
@@ -198,7 +206,7 @@
                 const int lt = wave + 8 * t;
                 buf[t] = s_a + lt * 16 * HD; row0[t] = (first + lt) * 16;
                 const int r = row0[t] + m, ul = 8 * lt + (m >> 1);
-                const bool node1 = (m & 1) != 0, in = r < N;
+                const bool node1 = (m & 1) != 0, in = GAT_FX || r < N;
                 const float *src = reinterpret_cast<const float *>(smem + (node1 ? GAT_F2_OFF : GAT_F1_OFF)) + ul * (node1 ? 8 : 6);
                 const float fa = in ? src[q] : 0.f, fb = (in && (node1 || q < 2)) ? src[4 + q] : 0.f;
                 xa[t][0] = node1 ? 0.f : fa; xa[t][1] = node1 ? 0.f : fb; xa[t][2] = node1 ? fa : 0.f; xa[t][3] = node1 ? fb : 0.f;

@@ -6,6 +6,23 @@
 #ifndef HX_VALUES_ONLY
 #define HX_VALUES_ONLY 0                   // 1 (k_headsx_values): the critic values only — no scorer rows, no probabilities, no selection (the post-terminal forward pair keeps nothing else: Run.py:455-475)
 #endif
+// The shape through macros ("Fixed shape"): the defaults are the run-time expressions.  k_headsx_gat3x_headsx<0, true, H3ShapeFixed<J, M, 16>>
+// sets HX_FX for its two heads parts: R = HX_FX_R rows per instance, 16 full instances in the workgroup, T = HX_FX_T tasks and M = HX_FX_M machines per
+// instance, f32 observations, an armed selection; HX_FX_JOB: the job part (pooled given, gather_from / gathered_out / logp_out / mf_on, no
+// BatchNorm of X) or the machine part (BatchNorm of X, logp_out, none of the others); neither gathers X, applies a ReLU or zeroes statistics.
+// The host states the rule once: mtfjsp_fused3_select.h.
+#ifndef HX_FX
+#define HX_FX false
+#define HX_FX_JOB false
+#define HX_FX_R 0
+#define HX_FX_T 0
+#define HX_FX_M 0
+#endif
+#define HXA_XBN (HX_FX ? !(HX_FX_JOB) : A.xbn_stats != nullptr)
+#define HXA_XGATHER (HX_FX ? static_cast<const int *>(nullptr) : A.xgather)
+#define HXA_GF (HX_FX ? (HX_FX_JOB) : A.gather_from != nullptr)
+#define HXA_MF (HX_FX ? (HX_FX_JOB) : A.mf_on != 0)
+#define HXA_XRELU (!(HX_FX) && A.xrelu)
     unsigned char *s_xs = smem;                                    // HCH tiles of 2 planes: X rows, then s1
     unsigned char *s_pp = s_xs + HCH * X2_TILE;                    // pooled planes
     unsigned char *s_op = s_pp + X2_TILE;                          // other planes
@@ -26,7 +43,7 @@
     unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_last;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_last)::"memory");
 #endif
-    const int R = A.R;
+    const int R = HX_FX ? HX_FX_R : A.R;
     const unsigned invR = (unsigned)((0x100000000ull + (unsigned)R - 1) / (unsigned)R);
     const int sr = tid >> 5, sc4 = (tid & 31) * 4;                  // staging: thread -> (row sr of 16, 4 columns)
     const int xoff = m * X6_ROWB + 16 * q;                          // operand fragment of (plane p, k-step ks): + p*X6_PLANE + 64*ks
@@ -43,7 +60,7 @@
     float xs0 = 1.f, xs1 = 1.f, xs2 = 1.f, xs3 = 1.f, xh0 = 0.f, xh1 = 0.f, xh2 = 0.f, xh3 = 0.f;   // X scale / shift of this thread's 4 columns
     double bsu[STAT_REP], bsq[STAT_REP];
     float bga = 0.f, bbe = 0.f;
-    if (A.xbn_stats) {
+    if (HXA_XBN) {
 #if !HX_XCHG
 #pragma unroll
         for (int r = 0; r < STAT_REP; r++) { bsu[r] = A.xbn_stats[r * 256 + tc]; bsq[r] = A.xbn_stats[r * 256 + HD + tc]; }
@@ -52,14 +69,14 @@
     }
     {   // one workgroup per group of 16 instances (a persistent loop here makes the compiler hoist ~200 loop-invariant
         // 64-bit weight addresses into registers and spill them)
-        const int g0 = blockIdx.x * A.hg;
-        const int ng = (A.B - g0) < A.hg ? (A.B - g0) : A.hg;
+        const int g0 = blockIdx.x * (HX_FX ? HG : A.hg);
+        const int ng = HX_FX ? HG : (A.B - g0) < A.hg ? (A.B - g0) : A.hg;
         const int nrows = ng * R;
         // scorer row `grow` of the group (instance grow / R, candidate / machine grow % R) -> its source row in X
         auto xrow = [&](int grow) __attribute__((always_inline)) -> const float * {
-            if (!A.xgather) return A.X + ((size_t)g0 * R + grow) * HD + sc4;
+            if (!HXA_XGATHER) return A.X + ((size_t)g0 * R + grow) * HD + sc4;
             const int il = (int)__umulhi((unsigned)grow, invR);
-            return A.X + ((size_t)(g0 + il) * A.xT + A.xgather[(size_t)g0 * R + grow]) * HD + sc4;
+            return A.X + ((size_t)(g0 + il) * A.xT + HXA_XGATHER[(size_t)g0 * R + grow]) * HD + sc4;
         };
 #if HX_XCHG
         // Behind the in-launch exchange nothing may wait for memory that could have been requested before it.  X is this workgroup's
@@ -92,7 +109,7 @@
 #if !HX_XCHG
         // the two embedding rows of this thread's instance (the stage below used to request them where it needed them: a memory round trip
         // on every workgroup's critical path, round 5); without `pooled` (it is formed here from X) some valid row is fetched and ignored
-        const float4 xp_top = *reinterpret_cast<const float4 *>((A.pooled ? A.pooled : A.other) + (size_t)(g0 + (sr < ng ? sr : ng - 1)) * HD + sc4);
+        const float4 xp_top = *reinterpret_cast<const float4 *>((HX_FX || A.pooled ? A.pooled : A.other) + (size_t)(g0 + (sr < ng ? sr : ng - 1)) * HD + sc4);
         const float4 xo_top = *reinterpret_cast<const float4 *>(A.other + (size_t)(g0 + (sr < ng ? sr : ng - 1)) * HD + sc4);
 #endif
         // The selection at the end walks a chain of dependent requests — the picked row's task (gather_from), that task's job predecessor's
@@ -100,7 +117,7 @@
         // are walked for EVERY scorer row instead, up here where requests are free: index now, predecessor's machine behind the first
         // barrier, both parked in LDS (rows beyond 512: the old way).  Pointers are chosen, not branched around (a request behind an `if`
         // makes the later waits drain everything): without gather_from / m_fea1 some valid word of X is fetched and ignored.
-        const int r_gf = (A.gather_from ? A.gather_from + (size_t)g0 * R : reinterpret_cast<const int *>(A.X))[tid < nrows ? tid : nrows - 1];
+        const int r_gf = (HX_FX && !HXA_GF) ? 0 : (HXA_GF ? A.gather_from + (size_t)g0 * R : reinterpret_cast<const int *>(A.X))[tid < nrows ? tid : nrows - 1];
         h16x8 wA[2][4], wB[2][4], wC[2][4];
         const float sW0 = A.sW0, sW1 = A.sW1, sWc0 = A.sWc0, sWc1 = A.sWc1;   // 1 / scale of the weight images
         WCOLX(wA, A.W0x, 1);                                        // Wb
@@ -114,7 +131,7 @@
 #pragma unroll
             for (int t = 0; t < HCH; t++) {
                 const int grow = by_inst ? sr * R + t : t * 16 + sr, gc = (grow < nrows && (!by_inst || t < R)) ? grow : nrows - 1;
-                gi[t] = A.xgather ? A.xgather[(size_t)g0 * R + gc] : gc;
+                gi[t] = HXA_XGATHER ? HXA_XGATHER[(size_t)g0 * R + gc] : gc;
             }
 #pragma unroll
             for (int t = 0; t < HCH; t++) {
@@ -124,7 +141,7 @@
                     xr[t] = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(smem + 8 * 2 * 4 * 64 * 16) + ((gc >> 3) * 16 + (gc & 7)) * HD + sc4);
                     continue;
                 }
-                const float *src = A.xgather ? A.X + ((size_t)(g0 + il) * A.xT + gi[t]) * HD + sc4 : A.X + ((size_t)g0 * R + gc) * HD + sc4;
+                const float *src = HXA_XGATHER ? A.X + ((size_t)(g0 + il) * A.xT + gi[t]) * HD + sc4 : A.X + ((size_t)g0 * R + gc) * HD + sc4;
                 xr[t] = *reinterpret_cast<const float4 *>(src);
             }
         }
@@ -139,9 +156,9 @@
             if (tid < 2 * HD) s_wc2[tid] = r_wc2;
             if (tid < HD) { s_vec[tid] = r_v0; s_vec[HD + tid] = r_v1; s_vec[2 * HD + tid] = r_v2; s_vec[3 * HD + tid] = r_v3; s_vec[4 * HD + tid] = r_v4; }
         }
-        if (A.zero_stats && blockIdx.x == 0) for (int i = tid; i < A.zero_count; i += 512) A.zero_stats[i] = 0.0;
-        if (A.zero_stats2 && blockIdx.x == 0) for (int i = tid; i < A.zero_count2; i += 512) A.zero_stats2[i] = 0.0;
-        if (A.xbn_stats) {
+        if (!HX_FX && A.zero_stats && blockIdx.x == 0) for (int i = tid; i < A.zero_count; i += 512) A.zero_stats[i] = 0.0;
+        if (!HX_FX && A.zero_stats2 && blockIdx.x == 0) for (int i = tid; i < A.zero_count2; i += 512) A.zero_stats2[i] = 0.0;
+        if (HXA_XBN) {
 #if HX_XCHG
             // The statistics of X are this launch's own: every workgroup has added its (sum | sum of squares) per column to the
             // count-carrying words of its dispatch group (the end of mtfjsp_gat3x_body.h) and now collects the eight groups' words —
@@ -235,16 +252,16 @@
                 *reinterpret_cast<float4 *>(A.pooled_out + (size_t)(g0 + sr) * HD + sc4) = xp;
             }
 #else
-            if (A.xbn_stats) {                                      // pooled = mean over the instance's normalised rows (ac:444 / gcn:192)
+            if (HXA_XBN) {                                          // pooled = mean over the instance's normalised rows (ac:444 / gcn:192)
                 if (sr < ng) {
-                    const int nr = A.xgather ? A.xT : R;
+                    const int nr = HXA_XGATHER ? A.xT : R;
                     const float *src = A.X + (size_t)(g0 + sr) * nr * HD + sc4;
                     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
 #pragma unroll 12
                     for (int r = 0; r < nr; r++) {                   // 12 rows in flight per thread
                         const float4 v = *reinterpret_cast<const float4 *>(src + (size_t)r * HD);
                         float y0 = fmaf(v.x, xs0, xh0), y1 = fmaf(v.y, xs1, xh1), y2 = fmaf(v.z, xs2, xh2), y3 = fmaf(v.w, xs3, xh3);
-                        if (A.xrelu) { y0 = fmaxf(y0, 0.f); y1 = fmaxf(y1, 0.f); y2 = fmaxf(y2, 0.f); y3 = fmaxf(y3, 0.f); }
+                        if (HXA_XRELU) { y0 = fmaxf(y0, 0.f); y1 = fmaxf(y1, 0.f); y2 = fmaxf(y2, 0.f); y3 = fmaxf(y3, 0.f); }
                         a0 += y0; a1 += y1; a2 += y2; a3 += y3;
                     }
                     const float ir = 1.0f / (float)nr;
@@ -271,11 +288,11 @@
         if (tid < nrows) s_mask[tid] = r_mask;                      // (requested with the first phase's other loads)
         short r_lk;
         {   // second link of the selection's chain: the machine of the job predecessor of row tid's task
-            const int T_ = A.mf_on ? A.mf.T : 1, il = (int)__umulhi((unsigned)(tid < nrows ? tid : 0), invR);
-            int a = A.gather_from ? r_gf : 0;
+            const int T_ = HX_FX ? (HX_FX_JOB ? HX_FX_T : 1) : A.mf_on ? A.mf.T : 1, il = (int)__umulhi((unsigned)(tid < nrows ? tid : 0), invR);
+            int a = HXA_GF ? r_gf : 0;
             if (a < 0 || a >= T_) a = 0;
             const size_t row = (size_t)(g0 + il) * T_ + a;
-            r_lk = (A.mf_on ? reinterpret_cast<const short *>(A.mf.link) : reinterpret_cast<const short *>(A.X))[(A.mf_on && row > 0 ? row - 1 : 0) * 8 + 4];
+            r_lk = (HX_FX && !HXA_MF) ? (short)0 : (HXA_MF ? reinterpret_cast<const short *>(A.mf.link) : reinterpret_cast<const short *>(A.X))[(HXA_MF && row > 0 ? row - 1 : 0) * 8 + 4];
             s_gf[tid] = r_gf;
         }
         for (int i = tid + 512; i < nrows; i += 512) s_mask[i] = A.mask[(size_t)g0 * R + i];
@@ -284,7 +301,7 @@
         auto xnorm = [&](float4 v, bool valid) __attribute__((always_inline)) {
             if (!valid) return make_float4(0.f, 0.f, 0.f, 0.f);
             float y0 = fmaf(v.x, xs0, xh0), y1 = fmaf(v.y, xs1, xh1), y2 = fmaf(v.z, xs2, xh2), y3 = fmaf(v.w, xs3, xh3);
-            if (A.xrelu) { y0 = fmaxf(y0, 0.f); y1 = fmaxf(y1, 0.f); y2 = fmaxf(y2, 0.f); y3 = fmaxf(y3, 0.f); }
+            if (HXA_XRELU) { y0 = fmaxf(y0, 0.f); y1 = fmaxf(y1, 0.f); y2 = fmaxf(y2, 0.f); y3 = fmaxf(y3, 0.f); }
             return make_float4(y0, y1, y2, y3);
         };
         // one 16-row tile (planes at `tp`) x this wave's column block: 12 products on two chains, fragments of the next k-step in flight
@@ -497,7 +514,7 @@
                     if (A.range_flag && pr_l != pr_l) __hip_atomic_store(A.range_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 H3S_RT(7);
-                if (A.sample_mode) {
+                if (HX_FX || A.sample_mode) {
                     // pick_action_u's scans as a chain along the row: lane k takes lane k-1's running sum (row_shr:1) + its own p
                     float run = pr_l;
 #pragma unroll 1
@@ -534,28 +551,30 @@
                     s_score[r0 * R + r] = pr;                           // lanes of one wave: visible to lane l == 0 below
                 }
               }
-                if (A.sample_mode) {
+                if (HX_FX || A.sample_mode) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     const float p_pick = rowwise ? __shfl(pr_l, (lane & 48) + pick_l) : 0.f;
                     if (l == 0) {
                         const int b = g0 + r0;
                         const int pick = rowwise ? pick_l : pick_action_u(s_score + r0 * R, R, A.sample_mode == 2, u_pre);
                         A.idx_out[b] = pick;
-                        if (A.logp_out) A.logp_out[b] = logf(rowwise ? p_pick : s_score[r0 * R + pick]);
+                        if (HX_FX || A.logp_out) A.logp_out[b] = logf(rowwise ? p_pick : s_score[r0 * R + pick]);
                         const int prow = r0 * R + pick;
-                        const int gsel = !A.gather_from ? pick : prow < 512 ? s_gf[prow] : A.gather_from[(size_t)b * R + pick];
-                        if (A.gather_from && A.gathered_out) A.gathered_out[b] = gsel;
-                        s_part[r0] = __int_as_float(gsel);                     // hand the selected task to the instance's 16 lanes (s_part is free now)
-                        s_part[HG + r0] = __int_as_float(prow);
+                        const int gsel = !HXA_GF ? pick : (HX_FX || prow < 512) ? s_gf[prow] : A.gather_from[(size_t)b * R + pick];
+                        if (HX_FX ? (HX_FX_JOB) : (A.gather_from && A.gathered_out)) A.gathered_out[b] = gsel;
+                        if (!HX_FX) {                                          // (HX_FX is row-wise: every lane of the row knows the pick)
+                            s_part[r0] = __int_as_float(gsel);                 // hand the selected task to the instance's 16 lanes (s_part is free now)
+                            s_part[HG + r0] = __int_as_float(prow);
+                        }
                     }
                     H3T_RT(0);
-                    if (A.mf_on) {
+                    if (HXA_MF) {
                         // = k_mfea1 (pe:152-214) for the task just selected: the 16 lanes of the instance take the machines
-                        const int b = g0 + r0, T_ = A.mf.T, M_ = A.mf.M;
+                        const int b = g0 + r0, T_ = HX_FX ? HX_FX_T : A.mf.T, M_ = HX_FX ? HX_FX_M : A.mf.M;
                         int a, prow_m;
                         if (rowwise) {                                          // every lane of the row knows the pick: no hand-over through LDS
                             prow_m = r0 * R + pick_l;
-                            a = !A.gather_from ? pick_l : prow_m < 512 ? s_gf[prow_m] : A.gather_from[(size_t)b * R + pick_l];
+                            a = !HXA_GF ? pick_l : (HX_FX || prow_m < 512) ? s_gf[prow_m] : A.gather_from[(size_t)b * R + pick_l];
                         } else {
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                             a = __float_as_int(s_part[r0]); prow_m = __float_as_int(s_part[HG + r0]);
@@ -564,7 +583,7 @@
                         const size_t row = (size_t)b * T_ + a;
                         int pm = 0;
                         if (a % M_ != 0) {
-                            pm = prow_m < 512 ? s_pm[prow_m] : (int)reinterpret_cast<const short *>(A.mf.link)[(row - 1) * 8 + 4];   // machine of the job predecessor
+                            pm = (HX_FX || prow_m < 512) ? s_pm[prow_m] : (int)reinterpret_cast<const short *>(A.mf.link)[(row - 1) * 8 + 4];   // machine of the job predecessor
                             if (pm < 0) pm += M_;                                             // python negative index (pe:206)
                         }
                         H3T_RT(1);
@@ -584,7 +603,7 @@
                             H3T_RT(4);
                             const size_t o = ((size_t)b * M_ + mm) * 6;
                             const double f3 = (double)(1 - (int)mk), f5 = (double)(shop_m + 1);
-                            if (A.mf.obs_f32) {
+                            if (HX_FX || A.mf.obs_f32) {
                                 float *of = reinterpret_cast<float *>(A.mf.m_fea1_out) + o;
                                 of[0] = (float)f0; of[1] = (float)f1; of[2] = (float)x; of[3] = (float)f3; of[4] = (float)f4; of[5] = (float)f5;
                             } else {

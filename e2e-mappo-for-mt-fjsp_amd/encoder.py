@@ -223,6 +223,18 @@ class Encoder:
         capi.check(self.L.mtfjsp_encoder_peek_gin_res_host(self.h, cand.ctypes.data, cand.size, stats.ctypes.data, flags.ctypes.data), self.h, enc=True)
         return cand, stats, flags
 
+    def fused3_kernel_name(self):
+        """the instantiation of the three-in-one heads launch this handle's last such launch ran (None: none yet)"""
+        name = self.L.mtfjsp_encoder_fused3_kernel_name(self.h)
+        return name.decode() if name else None
+
+    def peek_fused3(self):
+        """diagnostic: (exchange words [2 fine | wide, 8, 256] u64, (time-out, range) words) of the last three-in-one heads launch"""
+        words = np.empty((2, 8, 256), dtype=np.uint64)
+        flags = np.zeros(2, dtype=np.uint32)
+        capi.check(self.L.mtfjsp_encoder_peek_fused3_host(self.h, words.ctypes.data, flags.ctypes.data), self.h, enc=True)
+        return words, flags
+
     def range_fallbacks(self):
         """-> (times the handle left the f16 split products because an activation exceeded their range, product mode in force)"""
         n, m = C.c_int64(0), C.c_int32(0)

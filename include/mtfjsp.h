@@ -580,6 +580,22 @@ const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e);
  * floats of the candidate rows [B*J,128]; the 6 x 8 x 128 x 2 count-carrying statistics words of its six boundaries (csrc/mtfjsp_gin_resident.h,
  * gr_fix_encode); the (time-out, range) words.  Any of the three pointers may be NULL. */
 int mtfjsp_encoder_peek_gin_res_host(mtfjsp_encoder_t e, float *cand_feat_host, int64_t count, uint64_t *stats_host, uint32_t *flags_host);
+/* Which instantiation of the three-in-one heads launch (job heads + the machine path's GAT passes + machine heads: k_headsx_gat3x_headsx) serves a job
+ * forward of the rollout — the library's one statement of the rule (csrc/mtfjsp_fused3_select.h; launch_heads goes through it).  No GPU involved.
+ * batch instances of n_job candidates and n_machine machines (n_job * n_machine task rows) on num_cu compute units; obs_f64 != 0: f64 observations;
+ * env_tail != 0: an armed environment step rides in the launch.  "k_headsx_gat3x_headsx<0, true, H3ShapeFixed<6, 6, 16>>" — the kernel text compiled for
+ * J = 6, M = 6, 16 full instances per workgroup, f32 observations, node rows in LDS, no environment tail — serves exactly batch = 4096 of that shape;
+ * "k_headsx_gat3x_headsx", the same text with the shape read at run time, everything else the launch is eligible for; NULL where it is not (the
+ * separate launches run).  MTFJSP_FUSED3_GENERIC=1 (read per call, by the launches too) forces the run-time kernel; MTFJSP_FUSED3_NODES_HBM is
+ * honoured as the handle honours it.  The handle's half of the eligibility (its switches, the census of co-resident workgroups) is not part of
+ * the answer, and a forward whose arguments are not the rollout step's (no armed selection, no m_fea1 context ...) runs the run-time kernel.
+ * *grid_out (may be NULL): workgroups.  mtfjsp_encoder_fused3_kernel_name: what the handle's last three-in-one launch ran (NULL: none yet). */
+const char *mtfjsp_fused3_kernel_name_for(int32_t batch, int32_t n_job, int32_t n_machine, int32_t num_cu, int32_t obs_f64, int32_t env_tail, int32_t *grid_out);
+const char *mtfjsp_encoder_fused3_kernel_name(mtfjsp_encoder_t e);
+/* diagnostic (tests): the exchange words of the handle's last three-in-one launch, copied to host memory after synchronising the stream —
+ * [2 sets: fine | wide][8 dispatch groups][256: sum | sum of squares of 128 columns] u64, arrival count in the top 6 bits — and the (time-out, range)
+ * words.  Either pointer may be NULL. */
+int mtfjsp_encoder_peek_fused3_host(mtfjsp_encoder_t e, uint64_t *words_host, uint32_t *flags_host);
 /* number of statistics-exchange time-outs of the single-launch kernels reported on this handle so far */
 int mtfjsp_encoder_resident_failures(mtfjsp_encoder_t e, int64_t *count_out);
 int mtfjsp_encoder_timing_begin(mtfjsp_encoder_t e);
