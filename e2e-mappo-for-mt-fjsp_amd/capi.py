@@ -124,6 +124,8 @@ PROTOTYPES = {
     "mtfjsp_encoder_peek_gin_res_host": (_I, [_VP, _VP, C.c_int64, _VP, _VP]),
     "mtfjsp_fused3_kernel_name_for": (C.c_char_p, [C.c_int32] * 6 + [C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_fused3_kernel_name": (C.c_char_p, [_VP]),
+    "mtfjsp_heads_kernel_name_for": (C.c_char_p, [C.c_int32] * 5 + [C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mtfjsp_encoder_heads_kernel_name": (C.c_char_p, [_VP, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_peek_fused3_host": (_I, [_VP, _VP, _VP]),
     "mtfjsp_encoder_range_fallbacks": (_I, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_peek_nodes_host": (_I, [_VP, _VP, C.c_int64]),
@@ -183,3 +185,20 @@ def fused3_kernel_for(batch, n_job, n_machine, num_cu=256, obs_f64=False, env_ta
     grid = C.c_int32(0)
     name = lib().mtfjsp_fused3_kernel_name_for(batch, n_job, n_machine, num_cu, int(bool(obs_f64)), int(bool(env_tail)), C.byref(grid))
     return (name.decode() if name else None), grid.value
+
+
+# flag bits of mtfjsp_heads_kernel_name_for (include/mtfjsp.h)
+HEADS_GAT, HEADS_MHEADS, HEADS_ENV_TAIL, HEADS_VALUES_ONLY, HEADS_F32, HEADS_NO_GAT, HEADS_NO_MHEADS, HEADS_OBS_F64 = 1, 2, 4, 8, 16, 32, 64, 128
+
+
+def heads_kernel_for(batch, n_job, n_machine, which=0, num_cu=256, gat=False, mheads=False, env_tail=False, values_only=False, f32=False,
+                     gat_ok=True, mheads_ok=True, obs_f64=False):
+    """(kernel name, instances per workgroup, workgroups): which heads kernel serves the job (which = 0) / machine (which = 1) actor's forward — the
+    library's own rule (csrc/mtfjsp_heads_select.h), no GPU needed.  gat / mheads / env_tail / values_only: what the caller asks to ride in the launch;
+    f32, gat_ok, mheads_ok: the handle's answers (product mode bit 4; its half of the two fusion conditions).  MTFJSP_NO_HEADS_HG8, MTFJSP_NO_HEADS10,
+    MTFJSP_FUSED3_NODES_HBM and MTFJSP_FUSED3_GENERIC are read from the environment per call."""
+    flags = (HEADS_GAT * bool(gat) | HEADS_MHEADS * bool(mheads) | HEADS_ENV_TAIL * bool(env_tail) | HEADS_VALUES_ONLY * bool(values_only) |
+             HEADS_F32 * bool(f32) | HEADS_NO_GAT * (not gat_ok) | HEADS_NO_MHEADS * (not mheads_ok) | HEADS_OBS_F64 * bool(obs_f64))
+    group, grid = C.c_int32(0), C.c_int32(0)
+    name = lib().mtfjsp_heads_kernel_name_for(batch, n_machine if which else n_job, n_machine, n_job * n_machine, num_cu, flags, C.byref(group), C.byref(grid))
+    return (name.decode() if name else None), group.value, grid.value

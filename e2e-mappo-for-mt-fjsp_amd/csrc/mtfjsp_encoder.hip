@@ -2010,7 +2010,7 @@ __device__ __forceinline__ void gat_prestage(const GatArgs &G, unsigned char *sm
 // (Requesting one word of every line gat_prestage() reads at the top of the launch, so that they wait in this XCD's L2 — they were last
 // read a rollout step ago — shortened it by 2 us and lengthened the first phase of the job heads by 0.5 us: the launch ended 0.7-1.2 us
 // later in alternating runs on one box, because the selection on waves 0-3, not this copy, ends the heads part.  Not kept.)
-#include "mtfjsp_fused3_select.h"
+#include "mtfjsp_heads_select.h"
 #if !MTFJSP_BODY_FUNCS
 // ENV (round 6): 0 = the three parts; 1 / 2 = + the environment step of the workgroup's 16 instances as the launch's tail (f32 / f64
 // observations; mtfjsp_env_grp.h's own code with the instances dealt to the 8 waves: bit-identical to k_env_grp16).  Two launches per
@@ -2020,7 +2020,7 @@ __device__ __forceinline__ void gat_prestage(const GatArgs &G, unsigned char *sm
 // NLDS (round 6): the GAT part's node rows stay in LDS for the machine part (M <= 6: at most 12 tiles, each wave's tiles in buffers of their
 // own, and the machine part stages its rows by instance) — 12.6 MB per launch less written and 12.6 MB less read back.
 // SH (round 8): the shape the heads and GAT statements see.  H3ShapeAny: everything from the kernel arguments, as before.  H3ShapeFixed<J, M, 16>: the
-// shape as compile-time constants (mtfjsp_fused3_select.h states when the host may launch it; launch_heads checks the arguments' half) — the statements
+// shape as compile-time constants (mtfjsp_fused3_select.h states when the host may launch it; fused3_instantiation checks the arguments' half) — the statements
 // read it through the HX_FX / GAT_FX macros of the body headers, whose defaults are the run-time expressions, so no other kernel changes.  One item,
 // with a -D switch for A/B builds (0: the run-time code): H3_FX_DROP — the chunk loop and its reload path, the row-valid and group-size selects, the
 // null-pointer alternatives, the non-row-wise selection, the f64 branches, the GAT part's tile bookkeeping and its one-tile-at-a-time loop.
@@ -2220,6 +2220,49 @@ __global__ __launch_bounds__(512) void k_headsx_values(HeadArgs A)
 }
 #undef HX_VALUES_ONLY
 #define HX_VALUES_ONLY 0
+// Every heads kernel the host launches with the dynamic LDS it needs, ONCE: mtfjsp_encoder_create walks these rows for the LDS attributes and
+// launch_heads looks up the row of its plan (mtfjsp_heads_select.h).  env: 0 no environment tail, 1 / 2 the step behind the last selection (f32 / f64
+// observations); nlds, fixed: the three-in-one launch's node rows in LDS, its fixed-shape instantiation.  A new instantiation is one row here and one
+// condition in the rule.
+static size_t headsx_gat3x_lds_bytes() { return headsx_lds_bytes() > gat3x_lds_bytes() ? headsx_lds_bytes() : gat3x_lds_bytes(); }
+static size_t headsx_envstep_lds_bytes() { return headsx_lds_bytes() > EnvGrpDynLds<1>::bytes ? headsx_lds_bytes() : EnvGrpDynLds<1>::bytes; }
+struct HeadsRow {
+    HeadsKernel kernel; int env; bool nlds, fixed;
+    const void *fn; size_t lds;
+    int nargs;                                                      // the kernel's arguments: 1 (heads) | 2 (heads, GAT) | 3 (heads, step) | 5 (heads, GAT, machine heads, exchange, step)
+    HeadsRow(HeadsKernel k, int ev, bool nl, bool fx, void (*f)(HeadArgs), size_t l) : kernel(k), env(ev), nlds(nl), fixed(fx), fn((const void *)f), lds(l), nargs(1) {}
+    HeadsRow(HeadsKernel k, int ev, bool nl, bool fx, void (*f)(HeadArgs, GatArgs), size_t l) : kernel(k), env(ev), nlds(nl), fixed(fx), fn((const void *)f), lds(l), nargs(2) {}
+    HeadsRow(HeadsKernel k, int ev, bool nl, bool fx, void (*f)(HeadArgs, EnvParams), size_t l) : kernel(k), env(ev), nlds(nl), fixed(fx), fn((const void *)f), lds(l), nargs(3) {}
+    HeadsRow(HeadsKernel k, int ev, bool nl, bool fx, void (*f)(HeadArgs, GatArgs, HeadArgs, XchgArgs, EnvParams), size_t l) : kernel(k), env(ev), nlds(nl), fixed(fx), fn((const void *)f), lds(l), nargs(5) {}
+};
+static const std::vector<HeadsRow> &heads_table()
+{
+    static const std::vector<HeadsRow> rows = {
+        {HEADS_K_F32, 0, false, false, k_heads, heads_lds_bytes()},
+        {HEADS_K_X, 0, false, false, k_headsx, headsx_lds_bytes()},
+        {HEADS_K_X10, 0, false, false, k_headsx10, headsx10_lds_bytes()},
+        {HEADS_K_VALUES, 0, false, false, k_headsx_values, headsx_lds_bytes()},
+        {HEADS_K_GAT3X, 0, false, false, k_headsx_gat3x, headsx_gat3x_lds_bytes()},
+        {HEADS_K_ENVSTEP, 1, false, false, k_headsx_envstep<float>, headsx_envstep_lds_bytes()},
+        {HEADS_K_ENVSTEP, 2, false, false, k_headsx_envstep<double>, headsx_envstep_lds_bytes()},
+#if !MTFJSP_BODY_FUNCS
+        {HEADS_K_FUSED3, 0, false, false, k_headsx_gat3x_headsx<0, false>, fused3_lds_bytes()},
+        {HEADS_K_FUSED3, 1, false, false, k_headsx_gat3x_headsx<1, false>, fused3_lds_bytes()},
+        {HEADS_K_FUSED3, 2, false, false, k_headsx_gat3x_headsx<2, false>, fused3_lds_bytes()},
+        {HEADS_K_FUSED3, 0, true, false, k_headsx_gat3x_headsx<0, true>, fused3_lds_bytes()},
+        {HEADS_K_FUSED3, 1, true, false, k_headsx_gat3x_headsx<1, true>, fused3_lds_bytes()},
+        {HEADS_K_FUSED3, 2, true, false, k_headsx_gat3x_headsx<2, true>, fused3_lds_bytes()},
+        {HEADS_K_FUSED3, 0, true, true, k_headsx_gat3x_headsx<0, true, H3ShapeHeadline>, fused3_lds_bytes()},
+#endif
+    };
+    return rows;
+}
+static const HeadsRow *heads_row(HeadsKernel k, int env, bool nlds, bool fixed)
+{
+    for (const HeadsRow &r : heads_table())
+        if (r.kernel == k && r.env == env && r.nlds == nlds && r.fixed == fixed) return &r;
+    return nullptr;
+}
 
 // ---------------------------------------------------------------------------------------------
 // GIN layer 0, first Linear (12 -> 128) fused with the neighbour aggregation of the raw task features
@@ -2991,6 +3034,7 @@ struct mtfjsp_encoder {
     unsigned long long xw_epoch = 0;
     long long fused3_launches = 0;
     int fused3_last_kernel = -1;            // Fused3Kernel of the last three-in-one launch (mtfjsp_encoder_fused3_kernel_name)
+    struct { int kernel = -1, three = 0, hg = 0, grid = 0; } heads_last[2];   // HeadsKernel (Fused3Kernel), instances per workgroup and workgroups of the launch that computed the last job [0] / machine [1] forward (mtfjsp_encoder_heads_kernel_name)
     double xchg_fine_limit = getenv("MTFJSP_XCHG_FINE_LIMIT") ? atof(getenv("MTFJSP_XCHG_FINE_LIMIT")) : 2147483648.0;   // diagnostic: a lower limit sends ordinary contributions through the wide-range words
     long long fused3_fail_at = getenv("MTFJSP_FUSED3_FAIL_AT") ? atoll(getenv("MTFJSP_FUSED3_FAIL_AT")) : 0;   // diagnostic: this three-in-one launch waits for a workgroup that does not exist
     bool heads_hg8 = !getenv("MTFJSP_NO_HEADS_HG8");
@@ -3025,7 +3069,6 @@ struct mtfjsp_encoder {
     struct FusedSample { bool armed = false; int greedy = 0; uint64_t seed = 0, counter = 0; int32_t *idx = nullptr; float *logp = nullptr;
                          const int32_t *gather_from = nullptr; int32_t *gathered = nullptr; } fs[2];   // [0] job actor, [1] machine actor
     int values_only = 0;                    // mtfjsp_encoder_arm_values_only: the next (job, machine) forward pair produces the critic values only
-    bool vo_now = false;                    // (the forward in progress is such a forward)
     FusedSample fs1_consumed;               // the machine selection the last three-in-one launch consumed (restored when the machine forward that follows is NOT the one it ran)
     // timing
     bool timing = false;
@@ -3220,24 +3263,15 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
     (void)hipFuncSetAttribute((const void *)k_gin_inst<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_gin_inst<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_gat_inst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_heads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)heads_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_headsx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)headsx_lds_bytes());
-    if (hipFuncSetAttribute((const void *)k_headsx10, hipFuncAttributeMaxDynamicSharedMemorySize, (int)headsx10_lds_bytes()) != hipSuccess) e->heads10 = false;
-    (void)hipFuncSetAttribute((const void *)k_headsx_envstep<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(headsx_lds_bytes() > EnvGrpDynLds<1>::bytes ? headsx_lds_bytes() : EnvGrpDynLds<1>::bytes));
-    (void)hipFuncSetAttribute((const void *)k_headsx_envstep<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(headsx_lds_bytes() > EnvGrpDynLds<1>::bytes ? headsx_lds_bytes() : EnvGrpDynLds<1>::bytes));
-    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(headsx_lds_bytes() > gat3x_lds_bytes() ? headsx_lds_bytes() : gat3x_lds_bytes()));
-#if !MTFJSP_BODY_FUNCS
-    (void)hipFuncSetAttribute((const void *)k_headsx_values, hipFuncAttributeMaxDynamicSharedMemorySize, (int)headsx_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<0, true, H3ShapeHeadline>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
-    (void)hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused3_lds_bytes());
-    if (hipFuncSetAttribute((const void *)k_headsx_gat3x_headsx<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)fused3_lds_bytes()) != hipSuccess) e->fuse_mheads = false;
-#else
+    for (const HeadsRow &r : heads_table()) {
+#if MTFJSP_BODY_FUNCS
+        if (r.kernel == HEADS_K_VALUES) continue;                    // (this diagnostic build never asked for it)
+#endif
+        if (hipFuncSetAttribute(r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds) == hipSuccess) continue;
+        if (r.kernel == HEADS_K_X10) e->heads10 = false;
+        if (r.kernel == HEADS_K_FUSED3 && r.env == 0 && !r.nlds) e->fuse_mheads = false;
+    }
+#if MTFJSP_BODY_FUNCS
     e->fuse_mheads = false;
 #endif
     {   // resident GIN kernel: whole instances per workgroup, at most 576 rows, one workgroup per CU
@@ -3951,21 +3985,15 @@ static int gat3x_args(mtfjsp_encoder *e, const std::string &pre, const void *m_f
 // parts (16), m_fea1 produced by that launch itself, whole-batch statistics without a cross-shard reduction, split products.
 static bool gat_fusable(const mtfjsp_encoder *e)
 {
-    // Worth it when the heads' grid (B / 16 workgroups) is exactly as wide as the GAT launch would make its own — min(row tiles / 8,
-    // CUs) — and fits the chip in one round: J6M6 x 4096: 47.7 us against 24.6 + 26.8.  Fewer workgroups than the GAT's own grid leave
-    // CUs idle during the GAT part (J20M20 x 2048, 128 workgroups: 110 against 53 + 38), two rounds of workgroups gain nothing
-    // (J10M10 x 8192: 130 against 128).
-    const int hgrid = e->cfg.batch / HG, gtiles = (2 * e->cfg.batch * e->cfg.n_machine + 15) / 16, ggrid = (gtiles + 7) / 8 < e->num_cu ? (gtiles + 7) / 8 : e->num_cu;
-    return e->fuse_gat && !e->bn_mode && !e->reduce_fn && !(e->f32_products & (2 | 4)) && e->cfg.batch % HG == 0 && hgrid <= e->num_cu && hgrid >= ggrid &&
+    return e->fuse_gat && !e->bn_mode && !e->reduce_fn && !(e->f32_products & (2 | 4)) && heads_gat_ride_shape(e->cfg.batch, e->cfg.n_machine, e->num_cu) &&
            e->w.count("machine_actor.gat_layer.W") && e->wx6.count("machine_actor.gat_layer.W");
 }
 // ... and the machine actor's heads as well (k_headsx_gat3x_headsx)?  The in-launch exchange needs every workgroup resident at once:
-// one per CU, on a device where the census of the single-launch GIN kernel found all of them available; a count field of the exchange
-// words holds the arrivals of one dispatch group in 6 bits.
+// one per CU, on a device where the census of the single-launch GIN kernel found all of them available (the shape's half: fused3_plan).
 static bool mheads_fusable(const mtfjsp_encoder *e)
 {
-    const int hgrid = e->cfg.batch / HG;
-    return e->fuse_mheads && e->res_ok && gat_fusable(e) && hgrid <= e->num_cu && (hgrid + 7) / 8 <= 63 && e->xw && e->cfg.n_machine <= 8 &&   // (<= 8: the pool rows are requested ahead of the exchange, mtfjsp_headsx_body.h)
+    return e->fuse_mheads && e->res_ok && gat_fusable(e) && e->xw &&
+           fused3_plan(e->cfg.batch, e->cfg.n_job, e->cfg.n_machine, e->T, e->num_cu, false, nullptr, false, nullptr).eligible &&
            e->wx6.count("machine_actor.m_policy.linears.0.weight") && e->wx6.count("machine_actor.machine_critic.linears.0.weight");
 }
 static int run_gat(mtfjsp_encoder *e, const std::string &pre, const void *m_fea1, const void *m_fea2, float *h_pooled, int *slot_out = nullptr)
@@ -4126,145 +4154,146 @@ static void set_head_images(mtfjsp_encoder *e, HeadArgs &ha, const std::string &
     ha.sW0 = e->wx6_sinv.at(policy + ".linears.0.weight"); ha.sW1 = e->wx6_sinv.at(policy + ".linears.1.weight");
     ha.sWc0 = e->wx6_sinv.at(critic + ".linears.0.weight"); ha.sWc1 = e->wx6_sinv.at(critic + ".linears.1.weight");
 }
-static void launch_heads(mtfjsp_encoder *e, HeadArgs &ha, const std::string &policy, const std::string &critic, const GatArgs *fused_gat = nullptr,
-                         const EnvParams *env_tail = nullptr, const HeadArgs *fused_mheads = nullptr)
+#ifdef MTFJSP_STAMP3
+static unsigned long long *g_st3 = nullptr;                         // [2048 workgroups][8 waves][8] stamps of the last three-in-one launch
+// mean (and *mx: maximum) over the waves lo <= (w & 7) < hi of `grid` workgroups of stamp i, in us since t0; waves that left no stamp do not count
+static double stamp_mean(const std::vector<unsigned long long> &h, int grid, int i, int lo, int hi, unsigned long long t0, double *mx = nullptr)
 {
-    if (e->f32_products & 4) { hipLaunchKernelGGL(k_heads, dim3((ha.B + HG - 1) / HG), dim3(512), heads_lds_bytes(), e->stream, ha); return; }
-    ha.hg = (!fused_gat && !env_tail && e->heads_hg8 && 2 * ((ha.B + HG - 1) / HG) <= e->num_cu) ? HG / 2 : HG;
-    const int grid = (ha.B + ha.hg - 1) / ha.hg;
-    set_head_images(e, ha, policy, critic);
-    if (fused_gat) {                                                // + the machine path's GAT passes of the same 16 instances
-        const size_t lds = headsx_lds_bytes() > gat3x_lds_bytes() ? headsx_lds_bytes() : gat3x_lds_bytes();
-#if !MTFJSP_BODY_FUNCS
-        if (fused_mheads) {                                         // + the machine actor's heads behind the in-launch exchange of the node statistics
-            XchgArgs xg{};
-            const int set = (int)(e->xw_epoch++ & 1);
-            xg.words = e->xw + (size_t)set * XW_SET; xg.words_next = e->xw + (size_t)(set ^ 1) * XW_SET;
-            xg.nblk = (unsigned)grid; xg.fail = e->res_fail; xg.range_flag = e->range_flag;
-            xg.fine_limit = e->xchg_fine_limit > 0 && e->xchg_fine_limit <= 2147483648.0 ? e->xchg_fine_limit : 2147483648.0;
-            if (++e->fused3_launches == e->fused3_fail_at) xg.nblk += 8;      // (diagnostic) every group's count stays one short: the time-out path
-#ifdef MTFJSP_STAMP3
-            static unsigned long long *d_st3 = nullptr;
-            if (!d_st3) { (void)hipMalloc((void **)&d_st3, (size_t)2048 * 64 * 8); (void)hipMemset(d_st3, 0, (size_t)2048 * 64 * 8); }
-            xg.stamps = d_st3;
-#endif
-            // the node rows stay in LDS where every tile has a buffer of its own (<= 12 tiles per workgroup: M <= 6) and the machine part stages
-            // its rows by instance (R <= HCH); MTFJSP_FUSED3_NODES_HBM=1: the round-5 form (rows written to e->node and read back)
-            // Which instantiation: the rule of mtfjsp_fused3_select.h (MTFJSP_FUSED3_GENERIC as it is NOW) on the shape, and — for the fixed one — what its
-            // statements take for granted of the three argument blocks: the headline rollout step's job part (embeddings from the single-launch GIN kernel: no
-            // gather / BatchNorm of X here; an armed selection with gather_from, gathered_out and logp_out; m_fea1 of the pick, f32) and machine part.
-            const int gtiles = (2 * ha.B * fused_mheads->R + 15) / 16, gper = (gtiles + grid - 1) / grid;
-            const bool obs_f64 = env_tail ? !env_tail->obs_f32 : (fused_gat->feat_f64 || !ha.mf.obs_f32);
-            const Fused3Plan pl = fused3_plan(ha.B, ha.R, fused_mheads->R, ha.mf.T, e->num_cu, obs_f64, e->nodes_lds ? nullptr : "1", env_tail != nullptr, getenv("MTFJSP_FUSED3_GENERIC"));
-            const bool nlds = pl.nodes_lds && (fused3_lds_bytes() >= (size_t)(8 * 2 * 4 * 64 * 16 + gper * 16 * HD * 4));
-            const HeadArgs &hm = *fused_mheads;
-            const bool fx_args = GAT_PAIRED && nlds && ha.hg == HG && hm.hg == HG && fused_gat->R == ha.B * hm.R && !fused_gat->feat_f64 &&
-                                 !ha.xgather && !ha.xbn_stats && !ha.xrelu && !ha.zero_stats && !ha.zero_stats2 && ha.pooled && ha.sample_mode && ha.gather_from && ha.gathered_out &&
-                                 ha.logp_out && ha.mf_on && ha.mf.obs_f32 && ha.mf.M == hm.R &&
-                                 !hm.xgather && hm.xbn_stats && !hm.xrelu && !hm.zero_stats && !hm.zero_stats2 && hm.sample_mode && hm.logp_out && !hm.gather_from && !hm.mf_on;
-            const Fused3Kernel k3 = (pl.eligible && pl.kernel == FUSED3_K_J6M6X16 && fx_args) ? FUSED3_K_J6M6X16 : FUSED3_K_ANY;
-            e->fused3_last_kernel = (int)k3;
-            const EnvParams ep0 = env_tail ? *env_tail : EnvParams{};
-            const int envm = !env_tail ? 0 : env_tail->obs_f32 ? 1 : 2;
-#define L3(EV, NL) hipLaunchKernelGGL((k_headsx_gat3x_headsx<EV, NL>), dim3(grid), dim3(512), fused3_lds_bytes(), e->stream, ha, *fused_gat, *fused_mheads, xg, ep0)
-            if (k3 == FUSED3_K_J6M6X16)
-                hipLaunchKernelGGL((k_headsx_gat3x_headsx<0, true, H3ShapeHeadline>), dim3(grid), dim3(512), fused3_lds_bytes(), e->stream, ha, *fused_gat, *fused_mheads, xg, ep0);
-            else if (nlds) { if (envm == 0) L3(0, true); else if (envm == 1) L3(1, true); else L3(2, true); }
-            else { if (envm == 0) L3(0, false); else if (envm == 1) L3(1, false); else L3(2, false); }
-#undef L3
-#ifdef MTFJSP_STAMP3
-            if (e->fused3_launches % 50 == 20 && getenv("MTFJSP_STAMP_PRINT")) {
-                (void)hipStreamSynchronize(e->stream);
-                std::vector<unsigned long long> h((size_t)grid * 64);
-                (void)hipMemcpy(h.data(), d_st3, h.size() * 8, hipMemcpyDeviceToHost);
-                std::vector<unsigned long long> h2((size_t)grid * 64);
-                (void)hipMemcpy(h2.data(), d_st3 + (size_t)256 * 64, h2.size() * 8, hipMemcpyDeviceToHost);
-                unsigned long long t0 = ~0ull;
-                for (int w = 0; w < grid * 8; w++) t0 = h[(size_t)w * 8] < t0 ? h[(size_t)w * 8] : t0;
-                printf("STAMP3 (us since the first wave's start; mean / max over %d waves): ", grid * 8);
-                const char *nm[8] = {"start", "job heads done", "gat tiles done", "gat stats out", "poll done", "bn staged", "mheads products done", "end"};
-                for (int i = 0; i < 8; i++) {
-                    double m = 0, mx = 0; int n = 0;
-                    for (int w = 0; w < grid * 8; w++) { if (!h[(size_t)w * 8 + i]) continue; const double v = (double)(h[(size_t)w * 8 + i] - t0) / 100.0; m += v; mx = v > mx ? v : mx; n++; }
-                    printf(" [%s] %.2f/%.2f", nm[i], n ? m / n : 0.0, mx);
-                }
-                printf("\n");
-                for (int i = 1; i <= 3; i++) {                          // per wave index: who finishes when
-                    printf("STAMP3 [%s] by wave:", nm[i]);
-                    for (int wv = 0; wv < 8; wv++) {
-                        double m = 0; int n = 0;
-                        for (int b = 0; b < grid; b++) { const unsigned long long x = h[((size_t)b * 8 + wv) * 8 + i]; if (x) { m += (double)(x - t0) / 100.0; n++; } }
-                        printf(" %.2f", n ? m / n : 0.0);
-                    }
-                    printf("\n");
-                }
-                for (int part = 0; part < 2; part++) {                  // the heads statements' phase boundaries (H3_RT): job part, machine part
-                    std::vector<unsigned long long> h3((size_t)grid * 64);
-                    (void)hipMemcpy(h3.data(), d_st3 + (size_t)(part ? 1024 : 512) * 64, h3.size() * 8, hipMemcpyDeviceToHost);
-                    const char *hn[8] = {"requests waited for (6)", "weights + pool (7)", "stage done (0)", "phase A (1)", "X planes (2)", "phase B + s1 (3)", "phase C + scores (4)", "softmax + selection (5)"};
-                    const int order[8] = {6, 7, 0, 1, 2, 3, 4, 5};
-                    printf("STAMP3 %s heads, mean over waves 0-3 / 4-7:", part ? "machine" : "job");
-                    for (int oi = 0; oi < 8; oi++) {
-                        double m[2] = {0, 0}; int n[2] = {0, 0};
-                        for (int w = 0; w < grid * 8; w++) { const unsigned long long x = h3[(size_t)w * 8 + order[oi]]; if (x) { m[(w & 7) >> 2] += (double)(x - t0) / 100.0; n[(w & 7) >> 2]++; } }
-                        printf(" [%s] %.2f/%.2f", hn[oi], n[0] ? m[0] / n[0] : 0.0, n[1] ? m[1] / n[1] : 0.0);
-                    }
-                    printf("\n");
-                }
-                for (int part = 0; part < 2; part++) {                  // ... and inside phases B, C and the selection (H3S_RT)
-                    std::vector<unsigned long long> h3((size_t)grid * 64);
-                    (void)hipMemcpy(h3.data(), d_st3 + (size_t)((part ? 1024 : 512) + 256) * 64, h3.size() * 8, hipMemcpyDeviceToHost);
-                    const char *hn[8] = {"B products", "c2", "barrier", "s1 planes", "C products + partial scores", "value head", "barrier + scores", "probabilities"};
-                    printf("STAMP3 %s heads detail, mean over waves 0-3 / 4-7:", part ? "machine" : "job");
-                    for (int oi = 0; oi < 8; oi++) {
-                        double m[2] = {0, 0}; int n[2] = {0, 0};
-                        for (int w = 0; w < grid * 8; w++) { const unsigned long long x = h3[(size_t)w * 8 + oi]; if (x) { m[(w & 7) >> 2] += (double)(x - t0) / 100.0; n[(w & 7) >> 2]++; } }
-                        printf(" [%s] %.2f/%.2f", hn[oi], n[0] ? m[0] / n[0] : 0.0, n[1] ? m[1] / n[1] : 0.0);
-                    }
-                    printf("\n");
-                }
-                for (int part = 0; part < 2; part++) {                  // ... and inside the selection (H3T_RT; waves 0-3)
-                    std::vector<unsigned long long> h3((size_t)grid * 64);
-                    (void)hipMemcpy(h3.data(), d_st3 + (size_t)(part ? 1792 : 1536) * 64, h3.size() * 8, hipMemcpyDeviceToHost);
-                    const char *hj[5] = {"picked, index handed over", "predecessor's machine", "t / p / transport requested", "t / p arrived", "means arrived"};
-                    const char *hm[5] = {"picked", "poll loop entered", "first poll back", "second poll back", "third poll back"};
-                    const char **hn = part ? hm : hj;
-                    printf("STAMP3 %s, mean over waves 0-3:", part ? "machine exchange / selection" : "job selection");
-                    for (int oi = 0; oi < 5; oi++) {
-                        double m = 0; int n = 0;
-                        for (int w = 0; w < grid * 8; w++) { const unsigned long long x = h3[(size_t)w * 8 + oi]; if (x) { m += (double)(x - t0) / 100.0; n++; } }
-                        printf(" [%s] %.2f", hn[oi], n ? m / n : 0.0);
-                    }
-                    printf("\n");
-                }
-                const char *gn[8] = {"gat entry", "staged", "projection", "pass 1", "pass 2", "pass 3 = first tile", "second tile", "all tiles done (barrier)"};
-                for (int i = 0; i < 8; i++) {                           // inside the GAT statements (mtfjsp_gat3x_body.h: G3_RT)
-                    printf("STAMP3 gat [%s] by wave:", gn[i]);
-                    for (int wv = 0; wv < 8; wv++) {
-                        double m = 0; int n = 0;
-                        for (int b = 0; b < grid; b++) { const unsigned long long x = h2[((size_t)b * 8 + wv) * 8 + i]; if (x) { m += (double)(x - t0) / 100.0; n++; } }
-                        printf(" %.2f", n ? m / n : 0.0);
-                    }
-                    printf("\n");
-                }
-            }
-#endif
-            return;
-        }
-#endif
-        hipLaunchKernelGGL(k_headsx_gat3x, dim3(grid), dim3(512), lds, e->stream, ha, *fused_gat);
-        return;
+    double m = 0; int n = 0;
+    for (int w = 0; w < grid * 8; w++) {
+        const unsigned long long x = h[(size_t)w * 8 + i];
+        if ((w & 7) < lo || (w & 7) >= hi || !x) continue;
+        const double v = (double)(x - t0) / 100.0;
+        m += v; n++;
+        if (mx) *mx = v > *mx ? v : *mx;
     }
-    if (env_tail) {                                                 // + the environment step of the same 16 instances (k_env_grp16's partition)
-        const size_t lds = headsx_lds_bytes() > EnvGrpDynLds<1>::bytes ? headsx_lds_bytes() : EnvGrpDynLds<1>::bytes;
-        if (env_tail->obs_f32) hipLaunchKernelGGL(k_headsx_envstep<float>, dim3(grid), dim3(512), lds, e->stream, ha, *env_tail);
-        else hipLaunchKernelGGL(k_headsx_envstep<double>, dim3(grid), dim3(512), lds, e->stream, ha, *env_tail);
-        return;
+    return n ? m / n : 0.0;
+}
+static void fused3_stamp_report(mtfjsp_encoder *e, int grid)
+{
+    if (!(e->fused3_launches % 50 == 20 && getenv("MTFJSP_STAMP_PRINT"))) return;
+    (void)hipStreamSynchronize(e->stream);
+    const auto fetch = [grid](size_t first_group) {
+        std::vector<unsigned long long> v((size_t)grid * 64);
+        (void)hipMemcpy(v.data(), g_st3 + first_group * 64, v.size() * 8, hipMemcpyDeviceToHost);
+        return v;
+    };
+    const std::vector<unsigned long long> h = fetch(0), h2 = fetch(256);
+    unsigned long long t0 = ~0ull;
+    for (int w = 0; w < grid * 8; w++) t0 = h[(size_t)w * 8] < t0 ? h[(size_t)w * 8] : t0;
+    printf("STAMP3 (us since the first wave's start; mean / max over %d waves): ", grid * 8);
+    const char *nm[8] = {"start", "job heads done", "gat tiles done", "gat stats out", "poll done", "bn staged", "mheads products done", "end"};
+    for (int i = 0; i < 8; i++) {
+        double mx = 0;
+        const double m = stamp_mean(h, grid, i, 0, 8, t0, &mx);
+        printf(" [%s] %.2f/%.2f", nm[i], m, mx);
     }
-    if (e->vo_now) { hipLaunchKernelGGL(k_headsx_values, dim3(grid), dim3(512), headsx_lds_bytes(), e->stream, ha); return; }
-    const int ntl = (ha.hg * ha.R + 15) / 16;                       // tiles of a full group
-    if (e->heads10 && ntl > 6 && ntl <= 10) { hipLaunchKernelGGL(k_headsx10, dim3(grid), dim3(512), headsx10_lds_bytes(), e->stream, ha); return; }
-    hipLaunchKernelGGL(k_headsx, dim3(grid), dim3(512), headsx_lds_bytes(), e->stream, ha);
+    printf("\n");
+    for (int i = 1; i <= 3; i++) {                                  // per wave index: who finishes when
+        printf("STAMP3 [%s] by wave:", nm[i]);
+        for (int wv = 0; wv < 8; wv++) printf(" %.2f", stamp_mean(h, grid, i, wv, wv + 1, t0));
+        printf("\n");
+    }
+    for (int part = 0; part < 2; part++) {                          // the heads statements' phase boundaries (H3_RT): job part, machine part
+        const std::vector<unsigned long long> h3 = fetch(part ? 1024 : 512);
+        const char *hn[8] = {"requests waited for (6)", "weights + pool (7)", "stage done (0)", "phase A (1)", "X planes (2)", "phase B + s1 (3)", "phase C + scores (4)", "softmax + selection (5)"};
+        const int order[8] = {6, 7, 0, 1, 2, 3, 4, 5};
+        printf("STAMP3 %s heads, mean over waves 0-3 / 4-7:", part ? "machine" : "job");
+        for (int oi = 0; oi < 8; oi++) printf(" [%s] %.2f/%.2f", hn[oi], stamp_mean(h3, grid, order[oi], 0, 4, t0), stamp_mean(h3, grid, order[oi], 4, 8, t0));
+        printf("\n");
+    }
+    for (int part = 0; part < 2; part++) {                          // ... and inside phases B, C and the selection (H3S_RT)
+        const std::vector<unsigned long long> h3 = fetch((part ? 1024 : 512) + 256);
+        const char *hn[8] = {"B products", "c2", "barrier", "s1 planes", "C products + partial scores", "value head", "barrier + scores", "probabilities"};
+        printf("STAMP3 %s heads detail, mean over waves 0-3 / 4-7:", part ? "machine" : "job");
+        for (int oi = 0; oi < 8; oi++) printf(" [%s] %.2f/%.2f", hn[oi], stamp_mean(h3, grid, oi, 0, 4, t0), stamp_mean(h3, grid, oi, 4, 8, t0));
+        printf("\n");
+    }
+    for (int part = 0; part < 2; part++) {                          // ... and inside the selection (H3T_RT; waves 0-3)
+        const std::vector<unsigned long long> h3 = fetch(part ? 1792 : 1536);
+        const char *hj[5] = {"picked, index handed over", "predecessor's machine", "t / p / transport requested", "t / p arrived", "means arrived"};
+        const char *hm[5] = {"picked", "poll loop entered", "first poll back", "second poll back", "third poll back"};
+        const char **hn = part ? hm : hj;
+        printf("STAMP3 %s, mean over waves 0-3:", part ? "machine exchange / selection" : "job selection");
+        for (int oi = 0; oi < 5; oi++) printf(" [%s] %.2f", hn[oi], stamp_mean(h3, grid, oi, 0, 8, t0));
+        printf("\n");
+    }
+    const char *gn[8] = {"gat entry", "staged", "projection", "pass 1", "pass 2", "pass 3 = first tile", "second tile", "all tiles done (barrier)"};
+    for (int i = 0; i < 8; i++) {                                   // inside the GAT statements (mtfjsp_gat3x_body.h: G3_RT)
+        printf("STAMP3 gat [%s] by wave:", gn[i]);
+        for (int wv = 0; wv < 8; wv++) printf(" %.2f", stamp_mean(h2, grid, i, wv, wv + 1, t0));
+        printf("\n");
+    }
+}
+#endif
+// the exchange words of the next three-in-one launch of `grid` workgroups: forward n adds to set n & 1 and zeroes the other one
+static XchgArgs fused3_exchange(mtfjsp_encoder *e, int grid)
+{
+    XchgArgs xg{};
+    const int set = (int)(e->xw_epoch++ & 1);
+    xg.words = e->xw + (size_t)set * XW_SET; xg.words_next = e->xw + (size_t)(set ^ 1) * XW_SET;
+    xg.nblk = (unsigned)grid; xg.fail = e->res_fail; xg.range_flag = e->range_flag;
+    xg.fine_limit = e->xchg_fine_limit > 0 && e->xchg_fine_limit <= 2147483648.0 ? e->xchg_fine_limit : 2147483648.0;
+    if (++e->fused3_launches == e->fused3_fail_at) xg.nblk += 8;      // (diagnostic) every group's count stays one short: the time-out path
+#ifdef MTFJSP_STAMP3
+    if (!g_st3) { (void)hipMalloc((void **)&g_st3, (size_t)2048 * 64 * 8); (void)hipMemset(g_st3, 0, (size_t)2048 * 64 * 8); }
+    xg.stamps = g_st3;
+#endif
+    return xg;
+}
+// Which instantiation of the three-in-one launch: the plan (mtfjsp_fused3_select.h's rule on the shape, MTFJSP_FUSED3_GENERIC as it is NOW) and what
+// only the handle and the three argument blocks can tell.  *nlds: the node rows stay in LDS where the plan allows it — every tile with a buffer of its
+// own (<= 12 tiles per workgroup: M <= 6), the machine part staging its rows by instance — and the launch's LDS holds them (otherwise the round-5 form:
+// rows written to e->node and read back).  The fixed instantiation also needs what its statements take for granted of the arguments: the headline
+// rollout step's job part (embeddings from the single-launch GIN kernel: no gather / BatchNorm of X here; an armed selection with gather_from,
+// gathered_out and logp_out; m_fea1 of the pick, f32) and machine part.
+static Fused3Kernel fused3_instantiation(const HeadsPlan &pl, const HeadArgs &ha, const GatArgs &ga, const HeadArgs &hm, bool *nlds)
+{
+    const int gtiles = (2 * ha.B * hm.R + 15) / 16, gper = (gtiles + pl.grid - 1) / pl.grid;
+    *nlds = pl.three.nodes_lds && (fused3_lds_bytes() >= (size_t)(8 * 2 * 4 * 64 * 16 + gper * 16 * HD * 4));
+    const bool fx_args = GAT_PAIRED && *nlds && ha.hg == HG && hm.hg == HG && ga.R == ha.B * hm.R && !ga.feat_f64 &&
+                         !ha.xgather && !ha.xbn_stats && !ha.xrelu && !ha.zero_stats && !ha.zero_stats2 && ha.pooled && ha.sample_mode && ha.gather_from && ha.gathered_out &&
+                         ha.logp_out && ha.mf_on && ha.mf.obs_f32 && ha.mf.M == hm.R &&
+                         !hm.xgather && hm.xbn_stats && !hm.xrelu && !hm.zero_stats && !hm.zero_stats2 && hm.sample_mode && hm.logp_out && !hm.gather_from && !hm.mf_on;
+    return (pl.three.eligible && pl.three.kernel == FUSED3_K_J6M6X16 && fx_args) ? FUSED3_K_J6M6X16 : FUSED3_K_ANY;
+}
+// the heads launch of forward `which` (0 job, 1 machine) as its plan says; the riding parts' argument blocks where the plan's kernel takes them
+static int launch_heads(mtfjsp_encoder *e, const HeadsPlan &pl, int which, HeadArgs &ha, const std::string &policy, const std::string &critic,
+                        const GatArgs *fused_gat = nullptr, const EnvParams *env_tail = nullptr, const HeadArgs *fused_mheads = nullptr)
+{
+    ha.hg = pl.hg;
+    if (pl.kernel != HEADS_K_F32) set_head_images(e, ha, policy, critic);
+    bool nlds = false;
+    Fused3Kernel k3 = FUSED3_K_ANY;
+    XchgArgs xg{};
+    EnvParams ep = env_tail ? *env_tail : EnvParams{};
+    if (pl.kernel == HEADS_K_FUSED3) {
+        xg = fused3_exchange(e, pl.grid);
+        k3 = fused3_instantiation(pl, ha, *fused_gat, *fused_mheads, &nlds);
+        e->fused3_last_kernel = (int)k3;
+    }
+    const HeadsRow *k = heads_row(pl.kernel, pl.env, nlds, k3 == FUSED3_K_J6M6X16);
+    void *a1[] = {&ha}, *a2[] = {&ha, (void *)fused_gat}, *a3[] = {&ha, &ep}, *a5[] = {&ha, (void *)fused_gat, (void *)fused_mheads, &xg, &ep};
+    void **args = !k ? nullptr : k->nargs == 1 ? a1 : k->nargs == 2 ? a2 : k->nargs == 3 ? a3 : a5;
+    if (!k || (k->nargs == 2 && !fused_gat) || (k->nargs == 3 && !env_tail) || (k->nargs == 5 && !(fused_gat && fused_mheads))) {
+        e->err = std::string("no heads kernel in this build for the launch planned: ") + heads_kernel_name(pl);
+        return MTFJSP_ERR_STATE;
+    }
+    (void)hipLaunchKernel(k->fn, dim3(pl.grid), dim3(512), args, k->lds, e->stream);
+    e->heads_last[which] = {(int)pl.kernel, (int)k3, pl.hg, pl.grid};
+#ifdef MTFJSP_STAMP3
+    if (pl.kernel == HEADS_K_FUSED3) fused3_stamp_report(e, pl.grid);
+#endif
+    return MTFJSP_OK;
+}
+// the shape and the handle's answers of a heads launch's request (mtfjsp_heads_select.h); the forward adds what it asks to ride along
+static HeadsRequest heads_request(const mtfjsp_encoder *e, int R)
+{
+    HeadsRequest q{};
+    q.B = e->cfg.batch; q.R = R; q.M = e->cfg.n_machine; q.T = e->T; q.num_cu = e->num_cu;
+    q.f32 = (e->f32_products & 4) != 0; q.hg8 = e->heads_hg8; q.heads10 = e->heads10; q.nodes_hbm = !e->nodes_lds;
+    q.obs_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64;
+    return q;
 }
 static void arm_sampling(mtfjsp_encoder *e, int which, HeadArgs &ha)
 {
@@ -4355,8 +4384,28 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
         }
         hm = e->hm_b;
     }
+    // The heads launch of this forward, planned ONCE from what is armed on the handle now — before the timed interval opens, which covers the stream
+    // work of assembling the riding parts' arguments too (the statistics memset and the first-use projection launches of gat3x_args).  Nothing is
+    // consumed here: the arms are taken below, where they always were.
+    const EnvParams &EP = e->env_step.P;
+    HeadsRequest rq = heads_request(e, J);
+    // values only (armed pair): nothing rides in this launch, no selection, no m_fea1
+    rq.values_only = e->values_only > 0 && !e->fs[0].armed && !e->mf_armed && !rq.f32 && !e->bn_mode;
+    rq.gat = e->mf_armed && e->mf_ctx.m_fea2;
+    rq.gat_ok = rq.gat && gat_fusable(e);
+    // the whole machine forward in this launch: armed outputs (mtfjsp_encoder_arm_machine_heads) and an armed machine selection
+    rq.mheads = e->mh.armed && e->fs[1].armed;
+    rq.mheads_ok = rq.gat_ok && rq.mheads && mheads_fusable(e);
+    // an environment step armed BEFORE this forward (mtfjsp_encoder_arm_env_step) rides in the three-in-one launch when the machine
+    // selection made there is the one it reads and the shapes agree (round 6: two launches per rollout step)
+    rq.env_tail = rq.mheads_ok && e->env_step.armed && e->fuse_env3 && !e->timing && e->fs[0].armed &&
+                  (const void *)e->fs[1].idx == (const void *)EP.mach_idx && (const void *)e->fs[0].gathered == (const void *)EP.task_idx &&
+                  EP.B == B && EP.M == e->cfg.n_machine && env_one_slot(EP.J, EP.M, EP.T) && fused3_lds_bytes() >= EnvGrpDynLds<1>::bytes;
+    if (rq.mheads_ok) { rq.obs_f64 = rq.env_tail ? !EP.obs_f32 : (rq.obs_f64 || !e->mf_ctx.obs_f32); rq.force_generic = getenv("MTFJSP_FUSED3_GENERIC"); }
+    const HeadsPlan hp = heads_plan(rq);
+    const bool with_gat = hp.kernel == HEADS_K_GAT3X || hp.kernel == HEADS_K_FUSED3, with_mheads = hp.kernel == HEADS_K_FUSED3, env_tail = with_mheads && hp.env != 0;
     {
-        Timed t(e, (e->mf_armed && e->mf_ctx.m_fea2 && gat_fusable(e)) ? ((e->mh.armed && e->fs[1].armed && mheads_fusable(e)) ? "heads_gat3_heads" : "heads_gat3") : "heads");
+        Timed t(e, HEADS_KERNEL_FAMILY[hp.kernel]);
         HeadArgs ha{};
         ha.B = B; ha.R = J; ha.X = e->cand_feat; ha.pooled = h_pooled; ha.other = hm;
         ha.W0i = WI("job_actor.o_policy.linears.0.weight"); ha.b0 = W("job_actor.o_policy.linears.0.bias");
@@ -4391,12 +4440,7 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
         e->prefused.valid = false; e->prefused.heads = false;
         GatArgs ga{};
         HeadArgs hm_args{};
-        // values only (armed pair): nothing rides in this launch, no selection, no m_fea1
-        e->vo_now = e->values_only > 0 && !ha.sample_mode && !ha.mf_on && !(e->f32_products & 4) && !e->bn_mode;
         if (e->values_only > 0) e->values_only--;
-        const bool with_gat = !e->vo_now && ha.mf_on && ha.mf.m_fea2 && gat_fusable(e);
-        // the whole machine forward in this launch: armed outputs (mtfjsp_encoder_arm_machine_heads) and an armed machine selection
-        const bool with_mheads = with_gat && e->mh.armed && e->fs[1].armed && mheads_fusable(e);
         e->mh.armed = false;
         if (with_gat && !with_mheads) {                                  // the machine forward that follows finds its GAT passes done
             const int slot = e->gat_slot;
@@ -4420,15 +4464,9 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
             e->prefused.heads = true; e->prefused.f1 = ha.mf.m_fea1_out; e->prefused.f2 = ha.mf.m_fea2; e->prefused.h_pooled_o = h_pooled;
             e->prefused.mmask = ha.mf.mmask_out; e->prefused.prob = e->mh.prob; e->prefused.h_pooled = e->mh.h_pooled; e->prefused.machine_v = e->mh.machine_v;
         }
-        // an environment step armed BEFORE this forward (mtfjsp_encoder_arm_env_step) rides in the three-in-one launch when the machine
-        // selection made there is the one it reads and the shapes agree (round 6: two launches per rollout step)
-        const EnvParams &EP = e->env_step.P;
-        const bool env_tail = with_mheads && e->env_step.armed && e->fuse_env3 && !e->timing && hm_args.sample_mode && ha.sample_mode &&
-                              (const void *)hm_args.idx_out == (const void *)EP.mach_idx && (const void *)ha.gathered_out == (const void *)EP.task_idx &&
-                              EP.B == B && EP.M == e->cfg.n_machine && env_one_slot(EP.J, EP.M, EP.T) && fused3_lds_bytes() >= EnvGrpDynLds<1>::bytes;
         if (e->env_step.armed && with_mheads) { e->env_step.armed = false; e->env_step.done = env_tail; }
-        launch_heads(e, ha, "job_actor.o_policy", "job_actor.job_critic", with_gat ? &ga : nullptr, env_tail ? &EP : nullptr, with_mheads ? &hm_args : nullptr);
-        e->vo_now = false;
+        rc = launch_heads(e, hp, 0, ha, "job_actor.o_policy", "job_actor.job_critic", with_gat ? &ga : nullptr, env_tail ? &EP : nullptr, with_mheads ? &hm_args : nullptr);
+        if (rc) return rc;
 #ifdef MTFJSP_STAMP
         static int printed = 0;
         if (printed++ < 3 && getenv("MTFJSP_STAMP_PRINT")) {
@@ -4484,6 +4522,7 @@ static int machine_actor_forward_impl(mtfjsp_encoder_t e, const void *m_fea1, co
         e->fs1_consumed = mtfjsp_encoder::FusedSample{};
         e->env_step.armed = false;                                    // (env_step.done: set by the job forward whose launch ran this forward — and the armed step, if it could)
         e->fs[1].armed = false;                                       // (a selection armed again for this call has been made already)
+        e->heads_last[1] = e->heads_last[0];                          // (that launch computed this forward)
         return MTFJSP_OK;
     }
     if (e->prefused.heads && e->fs1_consumed.idx && !e->fs[1].armed) e->fs[1] = e->fs1_consumed;   // other pointers: this forward is computed here and selects again with the selection the fused launch consumed
@@ -4493,8 +4532,18 @@ static int machine_actor_forward_impl(mtfjsp_encoder_t e, const void *m_fea1, co
     else rc = e->bn_mode ? run_gat_inst(e, "machine_actor.", m_fea1, m_fea2, h_pooled) : run_gat(e, "machine_actor.", m_fea1, m_fea2, nullptr, &slot);
     e->prefused.valid = false;
     if (rc) return rc;
+    // the heads launch, planned once from what is armed on the handle now (as in the job forward; nothing is consumed here).  An armed environment
+    // step (mtfjsp_encoder_arm_env_step) rides in this launch when the selection made here is the one it reads, the shapes agree and the launch is
+    // the split-product heads kernel; otherwise the caller steps the environment itself
+    const EnvParams &EP = e->env_step.P;
+    HeadsRequest rq = heads_request(e, M);
+    rq.values_only = e->values_only > 0 && !e->fs[1].armed && !rq.f32 && !e->bn_mode;
+    rq.env_tail = e->env_step.armed && e->fuse_env && !e->timing && !e->bn_mode && !rq.f32 && e->fs[1].armed &&
+                  (const void *)e->fs[1].idx == (const void *)EP.mach_idx && EP.B == B && EP.M == M && env_one_slot(EP.J, EP.M, EP.T);
+    if (rq.env_tail) rq.obs_f64 = !EP.obs_f32;
+    const HeadsPlan hp = heads_plan(rq);
     {
-        Timed t(e, "heads");
+        Timed t(e, HEADS_KERNEL_FAMILY[hp.kernel]);
         HeadArgs ha = machine_head_args(e, h_pooled_o, mmask, prob, machine_v);
         if (e->bn_mode) ha.pooled = h_pooled;                     // k_gat_inst already normalised and pooled the nodes per instance
         else {
@@ -4509,16 +4558,10 @@ static int machine_actor_forward_impl(mtfjsp_encoder_t e, const void *m_fea1, co
             }
         }
         arm_sampling(e, 1, ha);
-        e->vo_now = e->values_only > 0 && !ha.sample_mode && !(e->f32_products & 4) && !e->bn_mode;
         if (e->values_only > 0) e->values_only--;
-        // an armed environment step (mtfjsp_encoder_arm_env_step) rides in this launch when the selection made here is the one it
-        // reads, the shapes agree and the launch is the split-product heads kernel; otherwise the caller steps the environment itself
-        const EnvParams &EP = e->env_step.P;
-        const bool env_tail = e->env_step.armed && e->fuse_env && !e->timing && !e->bn_mode && !(e->f32_products & 4) && ha.sample_mode &&
-                              (const void *)ha.idx_out == (const void *)EP.mach_idx && EP.B == B && EP.M == M && env_one_slot(EP.J, EP.M, EP.T);
-        e->env_step.armed = false; e->env_step.done = env_tail;
-        launch_heads(e, ha, "machine_actor.m_policy", "machine_actor.machine_critic", nullptr, (env_tail && !e->vo_now) ? &EP : nullptr);
-        e->vo_now = false;
+        e->env_step.armed = false; e->env_step.done = rq.env_tail;
+        rc = launch_heads(e, hp, 1, ha, "machine_actor.m_policy", "machine_actor.machine_critic", nullptr, hp.kernel == HEADS_K_ENVSTEP ? &EP : nullptr);
+        if (rc) return rc;
     }
     HIPCHK(e, hipGetLastError());
     return MTFJSP_OK;
@@ -4642,6 +4685,29 @@ extern "C" const char *mtfjsp_fused3_kernel_name_for(int32_t batch, int32_t n_jo
     const Fused3Plan pl = fused3_plan(batch, n_job, n_machine, n_job * n_machine, num_cu, obs_f64 != 0, getenv("MTFJSP_FUSED3_NODES_HBM"), env_tail != 0, getenv("MTFJSP_FUSED3_GENERIC"));
     if (grid_out) *grid_out = pl.grid;
     return pl.eligible ? FUSED3_KERNEL_NAME[pl.kernel] : nullptr;
+}
+extern "C" const char *mtfjsp_heads_kernel_name_for(int32_t batch, int32_t rows_per_instance, int32_t n_machine, int32_t task_rows, int32_t num_cu, uint32_t flags,
+                                                    int32_t *group_out, int32_t *grid_out)
+{
+    if (batch < 1 || rows_per_instance < 1 || n_machine < 1 || task_rows < 1 || num_cu < 1) return nullptr;
+    HeadsRequest q{};
+    q.B = batch; q.R = rows_per_instance; q.M = n_machine; q.T = task_rows; q.num_cu = num_cu;
+    q.gat = flags & MTFJSP_HEADS_GAT; q.mheads = flags & MTFJSP_HEADS_MHEADS; q.env_tail = flags & MTFJSP_HEADS_ENV_TAIL; q.values_only = flags & MTFJSP_HEADS_VALUES_ONLY;
+    q.f32 = flags & MTFJSP_HEADS_F32; q.gat_ok = !(flags & MTFJSP_HEADS_NO_GAT); q.mheads_ok = !(flags & MTFJSP_HEADS_NO_MHEADS); q.obs_f64 = flags & MTFJSP_HEADS_OBS_F64;
+    q.hg8 = !getenv("MTFJSP_NO_HEADS_HG8"); q.heads10 = !getenv("MTFJSP_NO_HEADS10"); q.nodes_hbm = getenv("MTFJSP_FUSED3_NODES_HBM") != nullptr;
+    q.force_generic = getenv("MTFJSP_FUSED3_GENERIC");
+    const HeadsPlan pl = heads_plan(q);
+    if (group_out) *group_out = pl.hg;
+    if (grid_out) *grid_out = pl.grid;
+    return heads_kernel_name(pl);
+}
+extern "C" const char *mtfjsp_encoder_heads_kernel_name(mtfjsp_encoder_t e, int32_t which, int32_t *group_out, int32_t *grid_out)
+{
+    if (!e || which < 0 || which > 1 || e->heads_last[which].kernel < 0) return nullptr;
+    const auto &l = e->heads_last[which];
+    if (group_out) *group_out = l.hg;
+    if (grid_out) *grid_out = l.grid;
+    return l.kernel == HEADS_K_FUSED3 ? FUSED3_KERNEL_NAME[l.three] : HEADS_KERNEL_NAME[l.kernel];
 }
 extern "C" const char *mtfjsp_encoder_fused3_kernel_name(mtfjsp_encoder_t e)
 {

@@ -228,6 +228,12 @@ class Encoder:
         name = self.L.mtfjsp_encoder_fused3_kernel_name(self.h)
         return name.decode() if name else None
 
+    def heads_kernel(self, which):
+        """(kernel name, instances per workgroup, workgroups) of the launch that computed the last job (0) / machine (1) forward (name None: none yet)"""
+        group, grid = C.c_int32(0), C.c_int32(0)
+        name = self.L.mtfjsp_encoder_heads_kernel_name(self.h, which, C.byref(group), C.byref(grid))
+        return (name.decode() if name else None), group.value, grid.value
+
     def peek_fused3(self):
         """diagnostic: (exchange words [2 fine | wide, 8, 256] u64, (time-out, range) words) of the last three-in-one heads launch"""
         words = np.empty((2, 8, 256), dtype=np.uint64)

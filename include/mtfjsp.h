@@ -581,7 +581,7 @@ const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e);
  * gr_fix_encode); the (time-out, range) words.  Any of the three pointers may be NULL. */
 int mtfjsp_encoder_peek_gin_res_host(mtfjsp_encoder_t e, float *cand_feat_host, int64_t count, uint64_t *stats_host, uint32_t *flags_host);
 /* Which instantiation of the three-in-one heads launch (job heads + the machine path's GAT passes + machine heads: k_headsx_gat3x_headsx) serves a job
- * forward of the rollout — the library's one statement of the rule (csrc/mtfjsp_fused3_select.h; launch_heads goes through it).  No GPU involved.
+ * forward of the rollout — the library's one statement of the rule (csrc/mtfjsp_fused3_select.h; the heads launch's plan, csrc/mtfjsp_heads_select.h, goes through it).  No GPU involved.
  * batch instances of n_job candidates and n_machine machines (n_job * n_machine task rows) on num_cu compute units; obs_f64 != 0: f64 observations;
  * env_tail != 0: an armed environment step rides in the launch.  "k_headsx_gat3x_headsx<0, true, H3ShapeFixed<6, 6, 16>>" — the kernel text compiled for
  * J = 6, M = 6, 16 full instances per workgroup, f32 observations, node rows in LDS, no environment tail — serves exactly batch = 4096 of that shape;
@@ -592,6 +592,38 @@ int mtfjsp_encoder_peek_gin_res_host(mtfjsp_encoder_t e, float *cand_feat_host, 
  * *grid_out (may be NULL): workgroups.  mtfjsp_encoder_fused3_kernel_name: what the handle's last three-in-one launch ran (NULL: none yet). */
 const char *mtfjsp_fused3_kernel_name_for(int32_t batch, int32_t n_job, int32_t n_machine, int32_t num_cu, int32_t obs_f64, int32_t env_tail, int32_t *grid_out);
 const char *mtfjsp_encoder_fused3_kernel_name(mtfjsp_encoder_t e);
+/* Which heads kernel serves an actor forward, with how many instances per workgroup and how many workgroups — the library's one statement of the rule
+ * (csrc/mtfjsp_heads_select.h; both forwards launch from it).  No handle, no GPU.  batch instances of rows_per_instance scorer rows (n_job for the job
+ * actor, n_machine for the machine actor), n_machine machines and task_rows task rows each on num_cu compute units.  flags: what the caller asks to ride
+ * in the launch, and the handle's answers that are not the shape's —
+ *   MTFJSP_HEADS_GAT          the machine path's GAT passes (a job forward with an armed m_fea1 context that has m_fea2)
+ *   MTFJSP_HEADS_MHEADS       ... and the machine actor's heads (mtfjsp_encoder_arm_machine_heads with an armed machine selection)
+ *   MTFJSP_HEADS_ENV_TAIL     an armed environment step that reads the last selection made in the launch
+ *   MTFJSP_HEADS_VALUES_ONLY  the critic values alone (mtfjsp_encoder_arm_values_only)
+ *   MTFJSP_HEADS_F32          product mode bit 4: the f32 matrix instruction
+ *   MTFJSP_HEADS_NO_GAT       the handle cannot let the GAT passes ride (MTFJSP_NO_FUSED_GAT, per-instance BatchNorm, a statistics reduction, product
+ *                             mode bits 2 | 4, no split weight images)
+ *   MTFJSP_HEADS_NO_MHEADS    ... nor the machine heads (MTFJSP_NO_FUSED_MHEADS, no census of co-resident workgroups, no exchange words)
+ *   MTFJSP_HEADS_OBS_F64      f64 observations
+ * Precedence: "k_heads" with the f32 instruction (groups of 16, nothing rides); the three-in-one launch (the name mtfjsp_fused3_kernel_name_for gives:
+ * GAT and machine heads asked for and allowed, shape eligible); "k_headsx_gat3x" (GAT asked for and allowed; whole groups of 16 in one round of
+ * workgroups, a grid as wide as the GAT launch's own); "k_headsx_envstep"; "k_headsx_values"; "k_headsx10" (a full group has 7 to 10 tiles of 16 rows);
+ * "k_headsx".  Groups of 8 instances only where nothing rides and 2 * ceil(batch / 16) <= num_cu.  MTFJSP_NO_HEADS_HG8, MTFJSP_NO_HEADS10,
+ * MTFJSP_FUSED3_NODES_HBM and MTFJSP_FUSED3_GENERIC are read per call (a handle reads the first three when it is created).  *group_out / *grid_out
+ * (may be NULL): instances per workgroup, workgroups.  NULL: a size below 1.
+ * mtfjsp_encoder_heads_kernel_name: the kernel that computed the handle's last job (which = 0) / machine (which = 1) forward, with its group size and
+ * grid — for a machine forward that the job forward's launch had already run, the three-in-one launch.  NULL: no such forward yet. */
+#define MTFJSP_HEADS_GAT 1u
+#define MTFJSP_HEADS_MHEADS 2u
+#define MTFJSP_HEADS_ENV_TAIL 4u
+#define MTFJSP_HEADS_VALUES_ONLY 8u
+#define MTFJSP_HEADS_F32 16u
+#define MTFJSP_HEADS_NO_GAT 32u
+#define MTFJSP_HEADS_NO_MHEADS 64u
+#define MTFJSP_HEADS_OBS_F64 128u
+const char *mtfjsp_heads_kernel_name_for(int32_t batch, int32_t rows_per_instance, int32_t n_machine, int32_t task_rows, int32_t num_cu, uint32_t flags,
+                                         int32_t *group_out, int32_t *grid_out);
+const char *mtfjsp_encoder_heads_kernel_name(mtfjsp_encoder_t e, int32_t which, int32_t *group_out, int32_t *grid_out);
 /* diagnostic (tests): the exchange words of the handle's last three-in-one launch, copied to host memory after synchronising the stream —
  * [2 sets: fine | wide][8 dispatch groups][256: sum | sum of squares of 128 columns] u64, arrival count in the top 6 bits — and the (time-out, range)
  * words.  Either pointer may be NULL. */

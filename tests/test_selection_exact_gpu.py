@@ -100,28 +100,27 @@ def test_standalone_sampler_on_hand_built_rows(n, B):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# fused selection: which kernel a decision's two heads launches are (restates launch_heads / gat_fusable / mheads_fusable of
-# csrc/mtfjsp_encoder.hip for the switches these tests use)
-# What the library itself reports: three-in-one or not (fused_launches()), the environment step inside the launch (act's return
-# value), the heads family of each launch (timing families heads / heads_gat3 / heads_gat3_heads) and the product mode.  Whether a
-# "heads" launch is k_headsx or k_headsx10, and whether its groups hold 8 or 16 instances, is NOT reported by the library: those two
-# distinctions rest on this restatement of launch_heads' conditions, and a change of the routing there must be repeated here.
-def _plain(R, B, num_cu, env):
-    hg = 8 if (not env.get("MTFJSP_NO_HEADS_HG8") and 2 * ((B + 15) // 16) <= num_cu) else 16
-    ntl = (hg * R + 15) // 16
-    return "k_headsx10" if (not env.get("MTFJSP_NO_HEADS10") and 6 < ntl <= 10) else "k_headsx"
+# fused selection: which kernel a decision's two heads launches are.  The library reports it — the kernel, its group size and its grid per forward
+# (Encoder.heads_kernel), three-in-one or not (fused_launches()), the environment step inside the launch (act's return value), the heads family
+# of each launch (timing families heads / heads_gat3 / heads_gat3_heads) and the product mode — and states its rule without a handle
+# (capi.heads_kernel_for, csrc/mtfjsp_heads_select.h).  _asks is what ActorPair.act arms under a case's switches and modes: the rule's input.
+def _asks(env, mode, stepping):
+    """-> (job, machine): keyword arguments of capi.heads_kernel_for for the two forwards of one decision"""
+    handle = dict(f32=mode.get("product") == 15, gat_ok=not mode.get("bn") and not mode.get("product"), mheads_ok=not env.get("MTFJSP_NO_FUSED_MHEADS"))
+    mheads = not (env.get("MTFJSP_FUSED_ENV") and stepping)
+    job = dict(handle, gat=True, mheads=mheads, env_tail=bool(mheads and env.get("MTFJSP_FUSED_ENV3") and stepping))
+    return job, dict(handle, which=1, env_tail=bool(env.get("MTFJSP_FUSED_ENV") and stepping))
 
 
-def _route(J, M, B, num_cu, env, mode):
-    if mode.get("product") == 15:
-        return "k_heads", "k_heads"
-    hgrid, gtiles = B // 16, (2 * B * M + 15) // 16
-    gat = not mode.get("bn") and B % 16 == 0 and hgrid <= num_cu and hgrid >= min((gtiles + 7) // 8, num_cu)
-    if gat and env.get("MTFJSP_FUSED_ENV"):
-        return "k_headsx_gat3x", "k_headsx_envstep"
-    if gat and not env.get("MTFJSP_NO_FUSED_MHEADS") and M <= 8:
-        return ("three_in_one_env",) * 2 if env.get("MTFJSP_FUSED_ENV3") else ("three_in_one",) * 2
-    return ("k_headsx_gat3x" if gat else _plain(J, B, num_cu, env)), _plain(M, B, num_cu, env)
+def _kernel_of(form):
+    return "k_headsx_gat3x_headsx" if form.startswith("three_in_one") else form
+
+
+def _rule(capi, J, M, B, num_cu, env, mode, stepping):
+    """-> ((job kernel, group, grid), (machine ...)) by the handle-free rule; a machine forward the job launch ran is that launch"""
+    job, mach = _asks(env, mode, stepping)
+    kj = capi.heads_kernel_for(B, J, M, num_cu=num_cu, **job)
+    return kj, (kj if kj[0].startswith("k_headsx_gat3x_headsx") else capi.heads_kernel_for(B, J, M, num_cu=num_cu, **mach))
 
 
 HG16, NO10, BOTH = {"MTFJSP_NO_HEADS_HG8": "1"}, {"MTFJSP_NO_HEADS10": "1"}, {"MTFJSP_NO_HEADS_HG8": "1", "MTFJSP_NO_HEADS10": "1"}
@@ -157,7 +156,7 @@ def _case_id(c):
     return f"J{J}M{M}E{E}x{B}-{sw}" + ("-f32" if mode.get("product") else "") + ("-bn" if mode.get("bn") else "")
 
 
-def _check_decision(ro, forms, greedy, stepping, last, capi):
+def _check_decision(ro, forms, greedy, stepping, last, capi, rule):
     """one ActorPair.act at the rollout's current state (with the environment step only where the form carries it) and everything it
     wrote checked; -> True when the environment took the step inside the launch"""
     env, act, e = ro.env, ro.actor, ro.actor.enc
@@ -173,6 +172,11 @@ def _check_decision(ro, forms, greedy, stepping, last, capi):
     act.greedy = was_greedy
     three = forms[0].startswith("three_in_one")
     assert e.fused_launches() - n3 == (1 if three else 0), "three-in-one launch " + ("did not run" if three else "ran")
+    for which in (0, 1):
+        name, group, grid = e.heads_kernel(which)
+        want = _kernel_of(forms[which])
+        assert name is not None and (name.startswith(want) if three else name == want), f"forward {which} ran {name}, expected {want}"
+        assert (group, grid) == rule[which][1:], f"forward {which}: groups of {group} in {grid} workgroups, the rule says {rule[which][1:]}"
     assert bool(stepped) == stepping, "the environment step did not ride in the heads launch"
     if not stepping:
         want = {}
@@ -207,7 +211,11 @@ def test_fused_selection_of_every_launch_form(case, monkeypatch):
         monkeypatch.setenv(k, v)
     enc_mod, rollout, capi = _mods()
     num_cu = torch.cuda.get_device_properties(0).multi_processor_count
-    assert _route(J, M, B, num_cu, env_sw, mode) == forms, f"on {num_cu} CUs this shape is routed to {_route(J, M, B, num_cu, env_sw, mode)}: choose another shape"
+    stepping = forms[1] in ("k_headsx_envstep", "three_in_one_env")
+    rule = _rule(capi, J, M, B, num_cu, env_sw, mode, stepping)
+    routed = tuple(r[0] for r in rule)
+    assert all(r.startswith(_kernel_of(f)) if f.startswith("three_in_one") else r == f for r, f in zip(routed, forms)), \
+        f"on {num_cu} CUs this shape is routed to {routed}: choose another shape"
     T = J * M
     only_greedy = bool(mode.get("bn"))
     ro = rollout.Rollout(J, M, E, B, policy="actor", obs_dtype="f32", weights=enc_mod.random_init_weights(seed=J * 100 + M), collect=False,
@@ -217,7 +225,6 @@ def test_fused_selection_of_every_launch_form(case, monkeypatch):
         e.set_product_mode(mode["product"])
     if mode.get("bn"):
         e.set_bn_mode(True)
-    stepping = forms[1] in ("k_headsx_envstep", "three_in_one_env")
     if forms[0].startswith("three_in_one"):
         assert e.check(), "the three-in-one launch needs the single-launch GIN kernel's census"
     if mode.get("product"):
@@ -239,7 +246,7 @@ def test_fused_selection_of_every_launch_form(case, monkeypatch):
     for t, greedy in plan:
         advance_to(t)
         assert ro.t_in_ep == t and ro.nsteps == t
-        _check_decision(ro, forms, greedy, stepping, t == T - 1, capi)
+        _check_decision(ro, forms, greedy, stepping, t == T - 1, capi, rule)
         flags.bitwise_or_(ro.env.status)
     assert int((flags & capi.ST_INVALID).ne(0).sum().item()) == 0
     e.check()
