@@ -380,3 +380,105 @@ def random_baselines(t, p, tt, edge, args, K=1, seed=0, device=0, obs_dtype="f32
     mean_cost = {key: r["cum"][:, :, i].mean(axis=1) for i, key in enumerate(COST_KEYS)}
     return {RANDOM_BEST: r["best"], RANDOM_MEAN: (mean_cost, r["final4"].mean(axis=1), r["obj"].mean(axis=1)),
             PLANS: {RANDOM_BEST: r["plans"]}}
+
+
+# ---- local search on plans (csrc/mtfjsp_plan.hip): K neighbours of every instance's incumbent per round, replayed side by side
+MOVE_SWAP, MOVE_INSERT, MOVE_REASSIGN = 1, 2, 4          # bits of `moves`; what "accepted" holds
+ALL_MOVES = MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN
+
+
+def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL_MOVES, left_shift=False, chunk=None, device=0,
+                 obs_dtype="f32", name="LS"):
+    """Hill climbing from the plans `start` = (task [N,T], mach [N,T]) — any plan the library returns: PLANS of `pdr_baselines`,
+    `lookahead_baselines`, `beam_baselines`, `random_baselines`, or `plans` of `evaluate.sample_best_of_k` — on the N instances t, p
+    [N,T,M], tt [N,M,M], edge [N,E,M/E] (args as for `pdr_baselines`).  Per round every instance's incumbent becomes K neighbours
+    (`DeviceBatchEnv.plan_neighbours`: copy 0 the incumbent itself, every other copy one SWAP / INSERT of the job string or one
+    REASSIGN of a task's machine, drawn from `moves` by the Philox stream of (seed, instance, copy, round)); the K-copy handle
+    replays them, and `group_reduce` keeps the best as the next incumbent: plan_neighbours, reset, T steps, final_costs,
+    group_reduce — T + 4 launches a round, no torch kernel, nothing read back before the last round.  The incumbent is copy 0 and
+    the reduction keeps the lowest copy among equal objectives: it survives ties, and the best Objective never rises.  The draws
+    are keyed by the instance's number in the whole set: the results do not depend on `chunk` (instances per pass; None: all N).
+    After the last round the best plans are replayed on an n-instance handle step by step, as `beam_baselines` replays its plans;
+    a start plan that is no valid plan ends there (RuntimeError).  rounds = 0 is a plain replay of `start`; K = 1 never moves.
+    -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS {name: (task[N,T], mach[N,T])}, and
+       "start_obj" [N]: the Objective of `start`;  "history" [rounds, N]: the best Objective after every round;
+       "accepted" [rounds, N] int8: the move that gave the round's best copy (MOVE_*), -1 where the incumbent stayed."""
+    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    K, R, moves = int(K), int(rounds), int(moves)
+    if not 1 <= K <= 4096:
+        raise ValueError("K must be 1..4096")
+    if R < 0 or not 1 <= moves <= ALL_MOVES:
+        raise ValueError("rounds must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN")
+    _rule_names([(name,), ("start_obj",), ("history",), ("accepted",)])
+    t = np.asarray(t, np.float64)
+    N = t.shape[0]
+    st_task, st_mach = np.ascontiguousarray(start[0], np.int32), np.ascontiguousarray(start[1], np.int32)
+    if st_task.shape != (N, T) or st_mach.shape != (N, T):
+        raise ValueError("start must be (task [N,T], mach [N,T])")
+    n = N if chunk is None else int(chunk)
+    if n < 1:
+        raise ValueError("chunk must be at least 1")
+    n = min(n, N)
+    src = DeviceBatchEnv(J, M, E, N, **kw)
+    env = top = None
+    parts = []
+    try:
+        src.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
+        dev = src.device
+        top = DeviceBatchEnv(J, M, E, n, **kw)                         # the final replay
+        w3_top = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n, 1)
+        inst_of = torch.arange(n, dtype=torch.int32, device=dev)
+        if R:
+            env = DeviceBatchEnv(J, M, E, n * K, **kw)                 # the copies
+            w3_all = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n * K, 1)
+            copy_of = torch.arange(n * K, dtype=torch.int32, device=dev) // K
+            own = torch.arange(n, dtype=torch.int32, device=dev) * K    # every group's copy 0
+            bufs = [tuple(torch.empty(T, n * K, dtype=torch.int32, device=dev) for _ in range(2)) for _ in range(2)]
+            cost4 = torch.empty(n * K, 4, dtype=torch.float64, device=dev)
+            done = torch.empty(n * K, dtype=torch.uint8, device=dev)
+            obj0 = torch.empty(n * K, dtype=torch.float64, device=dev)
+            best = torch.empty(R, n, dtype=torch.int32, device=dev)
+            hist = torch.empty(R, n, dtype=torch.float64, device=dev)
+            kind = torch.empty(R, n * K, dtype=torch.int8, device=dev)
+        for lo in range(0, N, n):
+            m = min(n, N - lo)                                          # a last, smaller pass is padded with copies of its last instance
+            sel = np.minimum(np.arange(n) + lo, N - 1)
+            cur_t = torch.as_tensor(np.ascontiguousarray(st_task[sel].T), device=dev)       # [T,n]: row s = the actions of step s
+            cur_m = torch.as_tensor(np.ascontiguousarray(st_mach[sel].T), device=dev)
+            top.fork_from(src, torch.clamp(inst_of + lo, max=N - 1), instance=True, state=False, obs=False)
+            if R:
+                env.fork_from(src, torch.clamp(copy_of + lo, max=N - 1), instance=True, state=False, obs=False)
+                env.scaler_init()                                       # the scaled components are produced but not used here
+            col = None
+            for r in range(R):
+                out_t, out_m = bufs[r & 1]
+                env.plan_neighbours(K, cur_t, cur_m, col, seed, r, lo, moves, out_t, out_m, kind[r])
+                env.reset(w3_all)
+                for s in range(T):
+                    env.step(out_t[s], out_m[s])
+                env.final_costs(cost4, done)                            # a rejected action leaves done = 0: the copy is not eligible
+                env.group_reduce(n, K, cost4, done, w, obj=obj0 if r == 0 else False, best=best[r], best_obj=hist[r], front=False)
+                cur_t, cur_m, col = out_t, out_m, best[r]
+            if R:
+                pick = torch.where(col < 0, own, col).long()            # a group without an eligible copy: its copy 0, which the replay rejects
+                cur_t, cur_m = cur_t.index_select(1, pick).contiguous(), cur_m.index_select(1, pick).contiguous()
+                acc = torch.where(best < 0, torch.full_like(best, -1), kind.gather(1, best.clamp(min=0).long()).to(torch.int32)).to(torch.int8)
+            top.scaler_init()
+            top.reset(w3_top)                                           # pdrs:675 reset(Random_weight_type="eval")
+            cum, prev = replay_episode(top, T, lambda s: (cur_t[s], cur_m[s]), f"{name} local-search")
+            host = lambda x, k=m: x[..., :k].cpu().numpy()              # noqa: E731
+            part = dict(cum=cum[:m], prev=prev[:m], task=host(cur_t).T.copy(), mach=host(cur_m).T.copy())
+            if R:
+                part.update(start_obj=host(obj0.view(n, K)[:, 0]), history=host(hist), accepted=host(acc))
+            parts.append(part)
+    finally:
+        for e in (top, env, src):
+            if e is not None:
+                e.close()
+    r = {k: np.concatenate([x[k] for x in parts], axis=-1 if k in ("history", "accepted") else 0) for k in parts[0]}
+    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, w)
+    if R:
+        out.update(start_obj=r["start_obj"], history=r["history"], accepted=r["accepted"])
+    else:
+        out.update(start_obj=out[name][2].copy(), history=np.zeros((0, N)), accepted=np.zeros((0, N), np.int8))
+    return out

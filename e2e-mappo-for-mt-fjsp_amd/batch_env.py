@@ -185,6 +185,40 @@ class DeviceBatchEnv:
                                               ptr(front)), self.h)
         return obj, best, best_obj, front
 
+    # ---- neighbourhood moves on plans (csrc/mtfjsp_plan.hip): local search over the groups of copies
+    def plan_neighbours(self, K, src_task, src_mach, src_col=None, seed=0, round=0, first_instance=0, moves=7, task_out=None, mach_out=None,
+                        kind_out=True):
+        """This handle holds N groups of K copies (batch = N*K, copy c of group n = element n*K + c).  src_task, src_mach: int32
+        device tensors [T, stride] in history layout (row s = the action of step s); the incumbent plan of group n is column
+        src_col[n] (int32 device tensor [N], e.g. `best` of `group_reduce`) or column n without src_col.
+        -> (task [T, N*K], mach [T, N*K], kind [N*K] int8) device tensors: copy 0 of every group is its incumbent (kind -1), every
+        other copy the incumbent after one move drawn from `moves` (a mask of 1 SWAP, 2 INSERT, 4 REASSIGN; kind = the move drawn) by
+        the Philox stream of (seed, first_instance + n, c, round) — include/mtfjsp.h has the rule.  Row s is ready for `step`.  A
+        source column or an incumbent entry out of range gives a group of -1.  task_out / mach_out: tensors to write into (they must
+        not overlap the sources); kind_out: True, a tensor, or None / False for no kinds.  One launch, nothing read back."""
+        K, T, dev = int(K), self.T, self.device
+        for x in (src_task, src_mach):
+            assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and x.dim() == 2 and x.shape[0] == T
+        assert src_mach.shape == src_task.shape
+        if src_col is not None:
+            assert src_col.is_cuda and src_col.dtype == torch.int32 and src_col.is_contiguous() and src_col.numel() * max(K, 1) == self.B
+        task_out = torch.empty(T, self.B, dtype=torch.int32, device=dev) if task_out is None else task_out
+        mach_out = torch.empty(T, self.B, dtype=torch.int32, device=dev) if mach_out is None else mach_out
+        for x in (task_out, mach_out):
+            assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and tuple(x.shape) == (T, self.B)
+        if kind_out is True:
+            kind_out = torch.empty(self.B, dtype=torch.int8, device=dev)
+        elif kind_out is False:
+            kind_out = None
+        if kind_out is not None:
+            assert kind_out.is_cuda and kind_out.dtype == torch.int8 and kind_out.is_contiguous() and kind_out.numel() == self.B
+        self._plan_keep = (src_task, src_mach, src_col)                 # alive until the launch has run
+        capi.check(self.L.mtfjsp_plan_neighbours(self.h, K, src_task.data_ptr(), src_mach.data_ptr(), src_task.shape[1],
+                                                 C.c_void_p(src_col.data_ptr() if src_col is not None else None), int(seed), int(round),
+                                                 int(first_instance), int(moves), task_out.data_ptr(), mach_out.data_ptr(),
+                                                 C.c_void_p(kind_out.data_ptr() if kind_out is not None else None)), self.h)
+        return task_out, mach_out, kind_out
+
     def scaler_init(self):
         capi.check(self.L.mtfjsp_scaler_init(self.h), self.h)
 

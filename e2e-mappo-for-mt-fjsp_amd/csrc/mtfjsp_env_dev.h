@@ -1,8 +1,8 @@
 // mtfjsp_env_dev.h — definitions of the environment state that more than one translation unit needs.  Device side (the step kernels
 // of mtfjsp_env.hip; mtfjsp_encoder.hip, whose machine-actor heads kernel can run the grouped step of its 16 instances as its tail,
-// k_headsx_envstep; the search baselines mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip): kernel parameter
+// k_headsx_envstep; the search baselines mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip, mtfjsp_plan.hip): kernel parameter
 // block, per-task / per-machine records, scalar slots, uniform lane reads — the wave-wide selections on top of them are in
-// mtfjsp_wave_select.h.  Host side (the four baseline units): a view of a handle and the checks their entry points share.
+// mtfjsp_wave_select.h.  Host side (the five baseline units): a view of a handle and the checks their entry points share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/mtfjsp.h"
@@ -115,7 +115,7 @@ __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t 
     }
 }
 
-// host side: what the library's other translation units (mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip) see of a handle; defined in mtfjsp_env.hip
+// host side: what the library's other translation units (mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip, mtfjsp_plan.hip) see of a handle; defined in mtfjsp_env.hip
 struct EnvHostView {
     int B, J, M, T, device_id;
     bool loaded;

@@ -326,6 +326,49 @@ int mtfjsp_final_costs(mtfjsp_handle_t h, double *cost4_out, uint8_t *done_out);
 int mtfjsp_group_reduce(mtfjsp_handle_t h, int32_t N, int32_t K, const double *cost4, const uint8_t *done, const double *w3cfg_host,
                         double *obj_out, int32_t *best_out, double *best_obj_out, uint8_t *front_out);
 
+/* ------------------------------------------------------------------ local search on plans: neighbourhood moves */
+/* Improvement of a schedule the library already has, over the best-of-K machinery above: every group's incumbent plan becomes K
+ * neighbouring plans in one launch, the K copies replay them (mtfjsp_reset, T x mtfjsp_step), mtfjsp_final_costs and
+ * mtfjsp_group_reduce keep the best, and its best_out is the next round's src_col: T + 4 launches a round, nothing read back.
+ * Copy 0 is the incumbent itself and the reduction keeps the lowest copy among equal objectives, so the incumbent survives ties and
+ * the best objective never rises: hill climbing by construction.  The reference has no improvement step.
+ *
+ * A plan is the flexible-job-shop encoding: step s dispatches the next operation of job q[s] = task[s] / n_machine, and every task
+ * a = j*n_machine + o has a machine mu[a] (= mach[s] where task[s] == a).  Any permutation of q is a plan: a move needs no repair.
+ *
+ * mtfjsp_plan_neighbours: h = the handle of the copies (batch = N*K, copy c of group n = element g = n*K + c); it gives t (the
+ * feasible machines), the device and the stream, and must hold instances (MTFJSP_ERR_STATE otherwise).  src_task, src_mach: device
+ * int32 [T, src_stride] in history layout, row s = the action of step s; the incumbent of group n is column src_col[n] (device
+ * int32 [N]) or, with src_col == NULL, column n.  task_out, mach_out: device int32 [T, N*K], row s ready for mtfjsp_step.
+ * kind_out: device int8 [N*K] or NULL: -1 for copy 0, else the move drawn (1 SWAP, 2 INSERT, 4 REASSIGN), whether or not it
+ * changed the plan.
+ *   copy 0      the incumbent, unchanged; no draw
+ *   copy c >= 1 w0..w3 = Philox4x32-10 of counter ((uint32)(first_instance + n), c, (uint32)round, 0x6d6f7665 "move") under the key
+ *               ((uint32)seed, (uint32)(seed >> 32)).  ONLY THE LOW 32 BITS of the instance number and of the round enter the
+ *               counter: first_instance and first_instance + 2^32 give one stream.  The instance number is global (first_instance
+ *               = the group's offset in the caller's set), so results do not depend on how the set is cut into passes.  Every
+ *               uniform integer below n is (w * n) >> 32.  moves = the allowed kinds as a bit mask; the kind drawn is the
+ *               ((w0 * popcount(moves)) >> 32)-th set bit of it; x = (w1 * T) >> 32.
+ *     SWAP      y = (w2 * (T-1)) >> 32, y += (y >= x): q[x] and q[y] change places (equal jobs: the plan stays as it is)
+ *     INSERT    the same x, y: the element at x is taken out and put in at position y, those between move by one
+ *     REASSIGN  a = task[x]; F = the machines m != mu[a] with t[a][m] >= 0 in ascending order; mu[a] = F[(w2 * |F|) >> 32], and
+ *               nothing where F is empty
+ *   decode      task'[s] = q'[s]*n_machine + (number of s' < s with q'[s'] == q'[s]), mach'[s] = mu'[task'[s]]: the machine
+ *               travels with the operation, not with the position
+ * Every input is device data that is never read back: a src_col[n] outside [0, src_stride), or an incumbent with a task outside
+ * [0, T) or a machine outside [0, n_machine), writes -1 to all rows of all K copies of that group — mtfjsp_step rejects them and
+ * done stays 0, which makes them ineligible for mtfjsp_group_reduce.  An incumbent that is in range but no plan (wrong operation
+ * counts) gives in-range or -1 entries.  No access leaves the arrays either way.
+ * MTFJSP_ERR_ARG, nothing written: K < 1, batch % K != 0, moves == 0 or > 7, a null src_task / src_mach / task_out / mach_out,
+ * src_stride < 1, an output array that overlaps a source array or another output; n_job*n_machine too large for 16 plans in a
+ * workgroup's LDS (beyond about 1900).
+ * One launch (k_plan_neighbours) on h's stream, no read-back, no synchronisation: a workgroup builds 64 (32, 16 for larger T)
+ * consecutive copies in LDS and stores every row as one contiguous run. */
+enum { MTFJSP_MOVE_SWAP = 1, MTFJSP_MOVE_INSERT = 2, MTFJSP_MOVE_REASSIGN = 4 };
+int mtfjsp_plan_neighbours(mtfjsp_handle_t h, int32_t K, const int32_t *src_task, const int32_t *src_mach, int64_t src_stride,
+                           const int32_t *src_col, uint64_t seed, uint64_t round, uint64_t first_instance, uint32_t moves,
+                           int32_t *task_out, int32_t *mach_out, int8_t *kind_out);
+
 /* ------------------------------------------------------------------ dispatch-rule baselines */
 /* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
  * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"
