@@ -385,6 +385,8 @@ def random_baselines(t, p, tt, edge, args, K=1, seed=0, device=0, obs_dtype="f32
 # ---- local search on plans (csrc/mtfjsp_plan.hip): K neighbours of every instance's incumbent per round, replayed side by side
 MOVE_SWAP, MOVE_INSERT, MOVE_REASSIGN = 1, 2, 4          # bits of `moves`; what "accepted" holds
 ALL_MOVES = MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN
+MOVE_CRIT_SWAP, MOVE_CRIT_REASSIGN = 8, 16               # moves a critical path of the incumbent's schedule directs
+CRIT_MOVES = MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN
 
 
 def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL_MOVES, left_shift=False, chunk=None, device=0,
@@ -400,15 +402,20 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
     are keyed by the instance's number in the whole set: the results do not depend on `chunk` (instances per pass; None: all N).
     After the last round the best plans are replayed on an n-instance handle step by step, as `beam_baselines` replays its plans;
     a start plan that is no valid plan ends there (RuntimeError).  rounds = 0 is a plain replay of `start`; K = 1 never moves.
+    `moves` may also hold MOVE_CRIT_SWAP and MOVE_CRIT_REASSIGN (CRIT_MOVES: both; ALL_MOVES | CRIT_MOVES: all five kinds): a move
+    changes the makespan only if it breaks an arc of a critical path, so these take one machine arc of the incumbent's critical
+    path between two jobs and turn it round, or put one task of the path on another machine.  The path is read off the device
+    state (`DeviceBatchEnv.critical_path`): of `start` after one replay on the n-instance handle before round 0, of every group's
+    best copy after its `group_reduce`, while that state is still there — T + 5 launches a round, still nothing read back.
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS {name: (task[N,T], mach[N,T])}, and
        "start_obj" [N]: the Objective of `start`;  "history" [rounds, N]: the best Objective after every round;
-       "accepted" [rounds, N] int8: the move that gave the round's best copy (MOVE_*), -1 where the incumbent stayed."""
+       "accepted" [rounds, N] int8: the move that gave the round's best copy (MOVE_*, 8 and 16 included), -1 where the incumbent stayed."""
     J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
     K, R, moves = int(K), int(rounds), int(moves)
     if not 1 <= K <= 4096:
         raise ValueError("K must be 1..4096")
-    if R < 0 or not 1 <= moves <= ALL_MOVES:
-        raise ValueError("rounds must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN")
+    if R < 0 or not 1 <= moves <= (ALL_MOVES | CRIT_MOVES):
+        raise ValueError("rounds must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN | MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN")
     _rule_names([(name,), ("start_obj",), ("history",), ("accepted",)])
     t = np.asarray(t, np.float64)
     N = t.shape[0]
@@ -440,6 +447,10 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
             best = torch.empty(R, n, dtype=torch.int32, device=dev)
             hist = torch.empty(R, n, dtype=torch.float64, device=dev)
             kind = torch.empty(R, n * K, dtype=torch.int8, device=dev)
+            path = None
+            if moves & CRIT_MOVES:                                      # every group's critical path: tasks, arcs, length
+                path = (torch.empty(n, T, dtype=torch.int32, device=dev), torch.empty(n, T, dtype=torch.int8, device=dev),
+                        torch.empty(n, dtype=torch.int32, device=dev))
         for lo in range(0, N, n):
             m = min(n, N - lo)                                          # a last, smaller pass is padded with copies of its last instance
             sel = np.minimum(np.arange(n) + lo, N - 1)
@@ -450,14 +461,22 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
                 env.fork_from(src, torch.clamp(copy_of + lo, max=N - 1), instance=True, state=False, obs=False)
                 env.scaler_init()                                       # the scaled components are produced but not used here
             col = None
+            if R and path is not None:                                  # the start plans' schedules, for round 0's directed moves
+                top.scaler_init()
+                top.reset(w3_top)
+                for s in range(T):
+                    top.step(cur_t[s], cur_m[s])
+                top.critical_path(None, None, *path)
             for r in range(R):
                 out_t, out_m = bufs[r & 1]
-                env.plan_neighbours(K, cur_t, cur_m, col, seed, r, lo, moves, out_t, out_m, kind[r])
+                env.plan_neighbours(K, cur_t, cur_m, col, seed, r, lo, moves, out_t, out_m, kind[r], critical=path)
                 env.reset(w3_all)
                 for s in range(T):
                     env.step(out_t[s], out_m[s])
                 env.final_costs(cost4, done)                            # a rejected action leaves done = 0: the copy is not eligible
                 env.group_reduce(n, K, cost4, done, w, obj=obj0 if r == 0 else False, best=best[r], best_obj=hist[r], front=False)
+                if path is not None:                                    # of the best copies, while their state is still there (-1: an empty path)
+                    env.critical_path(best[r], None, *path)
                 cur_t, cur_m, col = out_t, out_m, best[r]
             if R:
                 pick = torch.where(col < 0, own, col).long()            # a group without an eligible copy: its copy 0, which the replay rejects

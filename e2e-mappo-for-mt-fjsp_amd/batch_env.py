@@ -187,7 +187,7 @@ class DeviceBatchEnv:
 
     # ---- neighbourhood moves on plans (csrc/mtfjsp_plan.hip): local search over the groups of copies
     def plan_neighbours(self, K, src_task, src_mach, src_col=None, seed=0, round=0, first_instance=0, moves=7, task_out=None, mach_out=None,
-                        kind_out=True):
+                        kind_out=True, critical=None):
         """This handle holds N groups of K copies (batch = N*K, copy c of group n = element n*K + c).  src_task, src_mach: int32
         device tensors [T, stride] in history layout (row s = the action of step s); the incumbent plan of group n is column
         src_col[n] (int32 device tensor [N], e.g. `best` of `group_reduce`) or column n without src_col.
@@ -195,7 +195,11 @@ class DeviceBatchEnv:
         other copy the incumbent after one move drawn from `moves` (a mask of 1 SWAP, 2 INSERT, 4 REASSIGN; kind = the move drawn) by
         the Philox stream of (seed, first_instance + n, c, round) — include/mtfjsp.h has the rule.  Row s is ready for `step`.  A
         source column or an incumbent entry out of range gives a group of -1.  task_out / mach_out: tensors to write into (they must
-        not overlap the sources); kind_out: True, a tensor, or None / False for no kinds.  One launch, nothing read back."""
+        not overlap the sources); kind_out: True, a tensor, or None / False for no kinds.  One launch, nothing read back.
+        critical = (path_task [N,T] int32, path_arc [N,T] int8, path_len [N] int32) as `critical_path` returns them for the incumbents'
+        schedules: `moves` may then also hold 8 CRIT_SWAP (a machine arc of the path between two jobs is turned round) and 16
+        CRIT_REASSIGN (a task of the path changes machine).  With `critical` or moves > 7 the call is
+        mtfjsp_plan_neighbours_critical; with moves <= 7 both entries give the same words."""
         K, T, dev = int(K), self.T, self.device
         for x in (src_task, src_mach):
             assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and x.dim() == 2 and x.shape[0] == T
@@ -212,12 +216,44 @@ class DeviceBatchEnv:
             kind_out = None
         if kind_out is not None:
             assert kind_out.is_cuda and kind_out.dtype == torch.int8 and kind_out.is_contiguous() and kind_out.numel() == self.B
-        self._plan_keep = (src_task, src_mach, src_col)                 # alive until the launch has run
-        capi.check(self.L.mtfjsp_plan_neighbours(self.h, K, src_task.data_ptr(), src_mach.data_ptr(), src_task.shape[1],
-                                                 C.c_void_p(src_col.data_ptr() if src_col is not None else None), int(seed), int(round),
-                                                 int(first_instance), int(moves), task_out.data_ptr(), mach_out.data_ptr(),
-                                                 C.c_void_p(kind_out.data_ptr() if kind_out is not None else None)), self.h)
+        self._plan_keep = (src_task, src_mach, src_col, critical)       # alive until the launch has run
+        args = (self.h, K, src_task.data_ptr(), src_mach.data_ptr(), src_task.shape[1],
+                C.c_void_p(src_col.data_ptr() if src_col is not None else None), int(seed), int(round), int(first_instance), int(moves),
+                task_out.data_ptr(), mach_out.data_ptr(), C.c_void_p(kind_out.data_ptr() if kind_out is not None else None))
+        if critical is None and int(moves) <= 7:
+            capi.check(self.L.mtfjsp_plan_neighbours(*args), self.h)
+        else:
+            path = (None, None, None) if critical is None else tuple(critical)
+            if critical is not None:
+                N = self.B // max(K, 1)
+                for x, dt, shape in zip(path, (torch.int32, torch.int8, torch.int32), ((N, T), (N, T), (N,))):
+                    assert x.is_cuda and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape
+            capi.check(self.L.mtfjsp_plan_neighbours_critical(*args, *(C.c_void_p(None if x is None else x.data_ptr()) for x in path)), self.h)
         return task_out, mach_out, kind_out
+
+    def critical_path(self, col=None, n=None, task_out=None, arc_out=None, len_out=None):
+        """One critical path per row out of this handle's schedules as they stand (mtfjsp_critical_path: one launch, nothing read
+        back).  col: int32 device tensor [n] — row i describes instance col[i]; an entry outside [0, B) gives an empty row — or None:
+        row i = instance i, n = B.
+        -> (path_task [n,T] int32, path_arc [n,T] int8, path_len [n] int32) device tensors: from the task that ends last backwards
+        along tight arcs, the route predecessor first (arc 1), else the job predecessor (arc 0); -1 for the last element's arc and
+        at and after path_len.  include/mtfjsp.h has the rule.  task_out / arc_out / len_out: tensors to write into."""
+        dev, T = self.device, self.T
+        if col is not None:
+            assert col.is_cuda and col.dtype == torch.int32 and col.is_contiguous() and col.dim() == 1
+            n = col.numel() if n is None else int(n)
+            assert n <= col.numel()
+        else:
+            n = self.B if n is None else int(n)
+        task_out = torch.empty(max(n, 0), T, dtype=torch.int32, device=dev) if task_out is None else task_out
+        arc_out = torch.empty(max(n, 0), T, dtype=torch.int8, device=dev) if arc_out is None else arc_out
+        len_out = torch.empty(max(n, 0), dtype=torch.int32, device=dev) if len_out is None else len_out
+        for x, dt, shape in ((task_out, torch.int32, (n, T)), (arc_out, torch.int8, (n, T)), (len_out, torch.int32, (n,))):
+            assert x.is_cuda and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape
+        self._crit_keep = col                                           # alive until the launch has run
+        capi.check(self.L.mtfjsp_critical_path(self.h, n, C.c_void_p(col.data_ptr() if col is not None else None), task_out.data_ptr(),
+                                               arc_out.data_ptr(), len_out.data_ptr()), self.h)
+        return task_out, arc_out, len_out
 
     def scaler_init(self):
         capi.check(self.L.mtfjsp_scaler_init(self.h), self.h)

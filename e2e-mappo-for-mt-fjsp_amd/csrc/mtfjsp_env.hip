@@ -1626,7 +1626,7 @@ void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v)
     v->B = h->cfg.batch; v->J = h->cfg.n_job; v->M = h->cfg.n_machine; v->T = h->T; v->device_id = h->cfg.device_id;
     v->loaded = h->loaded; v->t = h->t; v->p = h->p; v->stream = h->stream;
     v->was_reset = h->was_reset; v->obs_bound = h->obs_bound; v->mj = h->mj; v->MJ = h->MJ; v->sd = h->sd; v->pl = h->pl; v->obs = h->obs;
-    v->scal = h->scal;
+    v->scal = h->scal; v->tt = h->tt;
 }
 int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg)
 {

@@ -128,6 +128,7 @@ struct EnvHostView {
     const TaskPL *pl;                  // [B,T] per-task records: energy, route links
     mtfjsp_obs_t obs;                  // the bound observation (valid with obs_bound)
     const double *scal;                // [B,SCAL_N] per-instance scalar state (slots above)
+    const double *tt;                  // [B,M,M] device transport times (mtfjsp_critical_path: the tightness of a job arc)
 };
 __attribute__((visibility("hidden"))) void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v);
 __attribute__((visibility("hidden"))) int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg);   // sets mtfjsp_last_error, returns code

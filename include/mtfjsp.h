@@ -369,6 +369,49 @@ int mtfjsp_plan_neighbours(mtfjsp_handle_t h, int32_t K, const int32_t *src_task
                            const int32_t *src_col, uint64_t seed, uint64_t round, uint64_t first_instance, uint32_t moves,
                            int32_t *task_out, int32_t *mach_out, int8_t *kind_out);
 
+/* mtfjsp_critical_path: one critical path per row out of the scheduling state of h as it stands — which operations and which
+ * machine hand-overs make the schedule as long as it is.  h: any handle that has been reset (MTFJSP_ERR_STATE otherwise).  col:
+ * device int32 [n], row i describes instance col[i] of h (any order, repeats allowed); NULL = the identity, and n must then be the
+ * batch.  Outputs (device): path_task int32 [n,T], path_arc int8 [n,T], path_len int32 [n].  The rule uses only what
+ * mtfjsp_read_state_host exports (machine, start, finish = start + duration: the addition the step performs, routes) and tt:
+ *   tasks     only the scheduled tasks (machine >= 0) of instance col[i].  col[i] outside [0, batch), or nothing scheduled:
+ *             path_len = 0 and the row is all -1
+ *   first     path_task[0] = the scheduled task with the largest finish time, the lowest task index among equal ones
+ *   arcs      of a task a on machine m: mp = its route predecessor (none for the first of a route), jp = a - 1 (none for
+ *             operation 0 of a job).  a is MACHINE-TIGHT iff st[a] == ft[mp] + xm, xm = tt[m][m] if mp is of a's job, else 0.0
+ *             (the step's own rule for a route neighbour); JOB-TIGHT iff st[a] == ft[jp] + tt[machine of jp][m].  Both are binary64 equalities of the very sums
+ *             the step formed when it placed a (appending, in front of the route, in a gap): exact, not approximate
+ *   walk      from a to mp if machine-tight (arc kind 1), else to jp if job-tight (arc kind 0), else the path ends at a
+ *   encoding  path_arc[k] = the kind of the arc from path_task[k] to path_task[k+1]; -1 for the last element; path_task and
+ *             path_arc are -1 at and after path_len; path_len <= T
+ * Without left shift every task of a complete schedule is tight on one side until a start at 0.0 is reached; with left shift a task
+ * put in front of a route or into a gap can leave its successor tight on neither side, and the path ends there.
+ * MTFJSP_ERR_ARG, nothing written: a null output, n < 1, col == NULL with n != batch.
+ * One launch (k_critical_path) on h's stream, nothing read back: one wave per row, lanes over tasks; the walk is pointer doubling
+ * in LDS (position k applies the table of 2^b steps where bit b of k is set), comparisons and the two sums above only.
+ *
+ * mtfjsp_plan_neighbours_critical: mtfjsp_plan_neighbours with two more kinds of move, directed by a critical path per group:
+ * path_task, path_arc [N,T] and path_len [N] (device; row n belongs to group n) as mtfjsp_critical_path writes them for the
+ * incumbents' schedules.  moves is a mask in 1..31; Philox draw, tag, w0..w3 and the choice of the kind — the
+ * ((w0 * popcount(moves)) >> 32)-th set bit in ascending order 1, 2, 4, 8, 16 — are mtfjsp_plan_neighbours'.  With moves <= 7 the
+ * path arrays are not read (they may be NULL) and the output is mtfjsp_plan_neighbours' word for word.  pos[a] = the position of
+ * task a in the incumbent, L = path_len[n]:
+ *     CRIT_SWAP      A = the ascending k in [0, L-1) with path_arc[k] == 1 and path_task[k], path_task[k+1] of different jobs.  A
+ *                    empty: the identity.  Else k = A[(w1 * |A|) >> 32], v = path_task[k], u = path_task[k+1], and INSERT with
+ *                    x = pos[v], y = pos[u] (the element at x taken out and put in at y, whichever is larger); decode as always
+ *     CRIT_REASSIGN  L == 0: the identity.  Else a = path_task[(w1 * L) >> 32], then as REASSIGN with this a: F = the other
+ *                    feasible machines in ascending order, mu[a] = F[(w2 * |F|) >> 32], nothing where F is empty
+ * kind_out names the kind drawn (8, 16) whether or not it changed the plan.  With a crit bit in moves, a path_len[n] outside [0, T]
+ * or a path_task[n][k], k < path_len[n], outside [0, T) writes -1 to all K copies of group n, as a bad incumbent does.
+ * MTFJSP_ERR_ARG, nothing written: as mtfjsp_plan_neighbours with moves > 31; a crit bit with a null path array; an output that
+ * overlaps one of the three path arrays.  mtfjsp_plan_neighbours itself keeps refusing moves > 7. */
+enum { MTFJSP_MOVE_CRIT_SWAP = 8, MTFJSP_MOVE_CRIT_REASSIGN = 16 };
+int mtfjsp_critical_path(mtfjsp_handle_t h, int32_t n, const int32_t *col, int32_t *path_task, int8_t *path_arc, int32_t *path_len);
+int mtfjsp_plan_neighbours_critical(mtfjsp_handle_t h, int32_t K, const int32_t *src_task, const int32_t *src_mach, int64_t src_stride,
+                                    const int32_t *src_col, uint64_t seed, uint64_t round, uint64_t first_instance, uint32_t moves,
+                                    int32_t *task_out, int32_t *mach_out, int8_t *kind_out, const int32_t *path_task, const int8_t *path_arc,
+                                    const int32_t *path_len);
+
 /* ------------------------------------------------------------------ dispatch-rule baselines */
 /* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
  * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"
