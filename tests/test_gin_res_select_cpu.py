@@ -28,6 +28,8 @@ TABLE = [
     ((4096, 7, 5, False), (GENERIC, 16, 256)),          # T = 35 (J = 7)
     ((2048, 6, 6, False), (GENERIC, 8, 256)),           # 8 instances per workgroup
     ((16, 6, 6, False), (GENERIC, 1, 16)),
+    ((9216, 4, 4, False), (GENERIC, 36, 256)),          # T = 16, the fewest rows per instance: 36 instances = 576 rows per workgroup
+    ((2048, 5, 13, False), (GENERIC, 8, 256)),          # T = 65, the most (tests/gin_res_edges.py has the shapes in between)
 ]
 
 
