@@ -124,6 +124,8 @@ PROTOTYPES = {
     "mtfjsp_encoder_resident_failures": (_I, [_VP, C.POINTER(C.c_int64)]),
     "mtfjsp_gin_res_kernel_name_for": (C.c_char_p, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_gin_res_kernel_name": (C.c_char_p, [_VP]),
+    "mtfjsp_gin_launches_for": (C.c_int32, [C.c_int32] * 6 + [C.c_uint32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mtfjsp_encoder_gin_launches": (C.c_int32, [_VP, C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_peek_gin_res_host": (_I, [_VP, _VP, C.c_int64, _VP, _VP]),
     "mtfjsp_fused3_kernel_name_for": (C.c_char_p, [C.c_int32] * 6 + [C.POINTER(C.c_int32)]),
     "mtfjsp_encoder_fused3_kernel_name": (C.c_char_p, [_VP]),
@@ -180,6 +182,41 @@ def gin_res_kernel_for(batch, n_job, n_machine, num_cu=256, candidates=None, nod
     name = lib().mtfjsp_gin_res_kernel_name_for(batch, n_job * n_machine, n_job, n_job if candidates is None else candidates, num_cu,
                                                 int(bool(node_output)), C.byref(ipc), C.byref(grid))
     return (name.decode() if name else None), ipc.value, grid.value
+
+
+# flag bits of mtfjsp_gin_launches_for (include/mtfjsp.h)
+GIN_CRITIC, GIN_NODE_OUTPUT, GIN_PER_INSTANCE, GIN_OBS_F64, GIN_NO_SINGLE, GIN_REDUCE = 1, 2, 4, 8, 16, 32
+
+
+def _gin_launches(call):
+    """{path, pool, steps: [(family, kernel, rev, nt, reduce)], rpr, pool_grid} from one of the two report entries"""
+    buf, order, pool = C.create_string_buffer(1024), (C.c_int32 * 12)(), (C.c_int32 * 2)()
+    n = call(buf, len(buf), order, pool)
+    if n < 0:
+        return None
+    path, form, seq = buf.value.decode().split(";")
+    steps = [tuple(s.split(":")) + (order[i] & 1, order[i] >> 1 & 1, order[i] >> 2) for i, s in enumerate(seq.split(","))]
+    assert len(steps) == n
+    return {"path": path, "pool": form, "steps": steps, "rpr": pool[0], "pool_grid": pool[1]}
+
+
+def gin_launches_for(batch, n_job, n_machine, num_cu=256, critic=False, candidates=None, node_output=False, per_instance=False, obs_f64=False,
+                     single_ok=True, reduce=False, product_mode=0, rows=None):
+    """Which path a GIN forward takes, who pools and every launch it makes — the library's own rule (csrc/mtfjsp_gin_select.h), no GPU needed.
+    critic: the global critic asks (no candidates) instead of the job actor; candidates: per instance (default n_job, 0 for the critic);
+    single_ok, reduce, product_mode: the handle's answers (its census passed; a statistics reduction is installed; its product mode); rows: rows per
+    instance where they are not n_job * n_machine.  The streaming switches (MTFJSP_FUSE_GIN0, MTFJSP_FUSE_POOL, MTFJSP_FUSE_PAIR, MTFJSP_NO_STREAM_ORDER,
+    MTFJSP_STREAM_NT, MTFJSP_POOL_S, MTFJSP_FUSE_POOL_MAXT), MTFJSP_NO_RESIDENT_GIN and MTFJSP_GIN_RES_GENERIC are read from the environment per call."""
+    flags = (GIN_CRITIC * bool(critic) | GIN_NODE_OUTPUT * bool(node_output) | GIN_PER_INSTANCE * bool(per_instance) | GIN_OBS_F64 * bool(obs_f64) |
+             GIN_NO_SINGLE * (not single_ok) | GIN_REDUCE * bool(reduce))
+    J = (0 if critic else n_job) if candidates is None else candidates
+    T = n_job * n_machine if rows is None else rows
+    return _gin_launches(lambda *out: lib().mtfjsp_gin_launches_for(batch, T, n_job, J, num_cu, product_mode, flags, *out))
+
+
+def encoder_gin_launches(handle):
+    """the same report for the handle's last GIN forward (None: none yet)"""
+    return _gin_launches(lambda *out: lib().mtfjsp_encoder_gin_launches(handle, *out))
 
 
 def fused3_kernel_for(batch, n_job, n_machine, num_cu=256, obs_f64=False, env_tail=False):

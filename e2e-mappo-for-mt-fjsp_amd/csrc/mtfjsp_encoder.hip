@@ -2011,6 +2011,7 @@ __device__ __forceinline__ void gat_prestage(const GatArgs &G, unsigned char *sm
 // read a rollout step ago — shortened it by 2 us and lengthened the first phase of the job heads by 0.5 us: the launch ended 0.7-1.2 us
 // later in alternating runs on one box, because the selection on waves 0-3, not this copy, ends the heads part.  Not kept.)
 #include "mtfjsp_heads_select.h"
+#include "mtfjsp_gin_select.h"
 #if !MTFJSP_BODY_FUNCS
 // ENV (round 6): 0 = the three parts; 1 / 2 = + the environment step of the workgroup's 16 instances as the launch's tail (f32 / f64
 // observations; mtfjsp_env_grp.h's own code with the instances dealt to the 8 waves: bit-identical to k_env_grp16).  Two launches per
@@ -3011,6 +3012,7 @@ struct mtfjsp_encoder {
     // resident GIN kernel (mtfjsp_gin_resident.h): eligibility decided at create time, then verified by a census launch
     bool res_ok = false; int res_ipc = 0, res_grid = 0;
     int res_last_kernel = -1;               // GinResKernel of the last single-launch forward (mtfjsp_encoder_gin_res_kernel_name)
+    GinPlan gin_last{}; bool gin_last_valid = false;   // the plan of the last GIN forward (mtfjsp_gin_select.h; mtfjsp_encoder_gin_launches)
     double *res_stats = nullptr;            // [2 sets][GR_STATS_SET] 64-bit count-carrying fixed-point words (mtfjsp_gin_resident.h); forward n uses set n & 1 and zeroes the other one
     unsigned long long *res_bar = nullptr;  // [17 * 16] barrier words
     unsigned *res_fail = nullptr;           // device address of *res_fail_host
@@ -3061,8 +3063,9 @@ struct mtfjsp_encoder {
     // issue (~100 us per launch even with no output at all), not by memory
     int fuse_pair = getenv("MTFJSP_FUSE_PAIR") ? atoi(getenv("MTFJSP_FUSE_PAIR")) : 0;
     int stream_order = getenv("MTFJSP_NO_STREAM_ORDER") ? 0 : 1;   // streaming GIN launches: alternating row direction + non-temporal input reads (A/B switch)
-    int fuse_pool = getenv("MTFJSP_FUSE_POOL") ? atoi(getenv("MTFJSP_FUSE_POOL")) : 1;   // run_gin: the last Linear's output pooled / gathered in a second pass' epilogue instead of stored
-    int fuse_gin0 = getenv("MTFJSP_FUSE_GIN0") ? atoi(getenv("MTFJSP_FUSE_GIN0")) : 1;   // run_gin: the first Linear's output formed again by the second launch's producers instead of stored
+    // (what each of these switches changes in a forward's launches: gin_plan, mtfjsp_gin_select.h — the handle only holds their values)
+    int fuse_pool = getenv("MTFJSP_FUSE_POOL") ? atoi(getenv("MTFJSP_FUSE_POOL")) : 1;   // the last Linear's output pooled / gathered in a second pass' epilogue instead of stored
+    int fuse_gin0 = getenv("MTFJSP_FUSE_GIN0") ? atoi(getenv("MTFJSP_FUSE_GIN0")) : 1;   // the first Linear's output formed again by the second launch's producers instead of stored
     int pool_s = getenv("MTFJSP_POOL_S") ? atoi(getenv("MTFJSP_POOL_S")) : 4;      // k_job_pool_gather: blocks per row range of the last product (0: plain instance order)
     int stream_nt = getenv("MTFJSP_STREAM_NT") ? atoi(getenv("MTFJSP_STREAM_NT")) : 5;   // which readers use non-temporal loads: 1 BatchNorm+ReLU products, 2 aggregation product, 4 pool / gather
     mtfjsp_mfea1_ctx_t mf_ctx{}; bool mf_armed = false;
@@ -3140,11 +3143,9 @@ static void gin_res_launch(GinResKernel k, int grid, hipStream_t stream, const G
     if (k == GIN_RES_K_T36J6X16) hipLaunchKernelGGL(k_gin_res_t36j6x16, dim3(grid), dim3(256), gin_res_lds_bytes(), stream, a);
     else hipLaunchKernelGGL(k_gin_res, dim3(grid), dim3(256), gin_res_lds_bytes(), stream, a);
 }
-// the rule on this handle for a forward with J candidates per instance (0: none); MTFJSP_GIN_RES_GENERIC as it is NOW (read per call)
-static GinResPlan gin_res_plan_of(const mtfjsp_encoder *e, int J, bool h_nodes, bool ignore_env = false)
-{
-    return gin_res_plan(e->cfg.batch, e->T, e->cfg.n_job, J, e->num_cu, h_nodes, ignore_env ? nullptr : getenv("MTFJSP_GIN_RES_GENERIC"));
-}
+// the rule on this handle's shape for the job actor's forward, whatever MTFJSP_GIN_RES_GENERIC says: eligibility, instances per workgroup and grid (they do
+// not depend on the forward) and the fixed instantiation the handle may launch.  (A forward's own plan: gin_plan, mtfjsp_gin_select.h.)
+static GinResPlan gin_res_plan_of(const mtfjsp_encoder *e) { return gin_res_plan(e->cfg.batch, e->T, e->cfg.n_job, e->cfg.n_job, e->num_cu, false, nullptr); }
 // census: every workgroup must be resident at once for the grid barriers to complete (bounded spins report it) — for each instantiation
 // this handle can launch (the run-time kernel always; the fixed-shape one where the job actor's forward has its shape).  Synchronises the device.
 static bool res_census(mtfjsp_encoder *e)
@@ -3153,7 +3154,7 @@ static bool res_census(mtfjsp_encoder *e)
     if (hipMemset(e->res_bar, 0, (size_t)17 * 16 * 8) != hipSuccess) return false;      // fresh barrier words (a timed-out launch leaves them inconsistent)
     e->res_epoch = 0;
     *e->res_fail_host = 0u;
-    const GinResKernel fixed = gin_res_plan_of(e, e->cfg.n_job, false, true).kernel;
+    const GinResKernel fixed = gin_res_plan_of(e).kernel;
     for (int k = 0; k < GIN_RES_K_COUNT; k++) {
         if (k != GIN_RES_K_ANY && k != fixed) continue;
         GinResArgs a{};
@@ -3172,6 +3173,8 @@ static bool res_census(mtfjsp_encoder *e)
 // handle falls back to the six streaming launches (mtfjsp_encoder_check re-runs the census and re-enables the single launch
 // when the device can hold the grid again) and the caller is told to repeat the work: MTFJSP_ERR_RETRY.
 static bool split_products_in_use(const mtfjsp_encoder *e) { return (e->f32_products & 15) != 15; }
+// the range word for a kernel that reports outputs that are not numbers: only while a split product can be their cause
+static unsigned *range_word(const mtfjsp_encoder *e) { return split_products_in_use(e) ? e->range_flag : nullptr; }
 static int res_poll_failure(mtfjsp_encoder *e)
 {
     if (!e->res_fail_host) return MTFJSP_OK;
@@ -3275,7 +3278,7 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
     e->fuse_mheads = false;
 #endif
     {   // resident GIN kernel: whole instances per workgroup, at most 576 rows, one workgroup per CU
-        const GinResPlan pl = gin_res_plan_of(e, cfg->n_job, false, true);          // (eligibility, ipc and grid do not depend on the forward)
+        const GinResPlan pl = gin_res_plan_of(e);
         if (!getenv("MTFJSP_NO_RESIDENT_GIN") && pl.eligible) {
             const int ipc = pl.ipc, grid = pl.grid;
             if (hipFuncSetAttribute((const void *)k_gin_res, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess &&
@@ -3585,8 +3588,24 @@ struct Timed {
     ~Timed() { if (on) (void)hipEventRecord(ev.second, e->stream); }
 };
 
-template <int PRO, int EPI, bool ACC = false>
-static void launch_gemm(mtfjsp_encoder *e, const GemmArgs &a, const char *name)
+// One launch of a [rows,128] x [128,128] product kernel (each takes a GemmArgs by value and 512 threads): the grid, the range word, the stamps and the
+// debug handling.  WHICH kernel is the caller's: a GIN step's plan names it (gin_gemm_kernel), the critic's head products are k_gemm16 (plain_gemm).
+struct GemmKernel { const void *fn; size_t lds; bool plain; };
+template <int EPI, bool ACC = false>
+static GemmKernel plain_gemm() { return {(const void *)k_gemm16<EPI, ACC>, gemm16_lds_bytes(), true}; }
+static GemmKernel gin_gemm_kernel(GinKernel k)
+{
+    switch (k) {
+    case GIN_K_X6_GIN0: return {(const void *)k_gemm_x6<PRO_GIN0>, gemm_x6_lds_bytes(), false};
+    case GIN_K_X6_GIN0BN: return {(const void *)k_gemm_x6<PRO_GIN0BN>, gemm_x6_lds_bytes(), false};
+    case GIN_K_X6_BNRELU: return {(const void *)k_gemm_x6<PRO_BNRELU>, gemm_x6_lds_bytes(), false};
+    case GIN_K_X6_AGG: return {(const void *)k_gemm_x6<PRO_AGG>, gemm_x6_lds_bytes(), false};
+    case GIN_K_16P_BNRELU: return {(const void *)k_gemm16p<PRO_BNRELU>, gemm16_lds_bytes(), false};
+    case GIN_K_16P_AGG: return {(const void *)k_gemm16p<PRO_AGG>, gemm16_lds_bytes(), false};
+    default: return {nullptr, 0, false};
+    }
+}
+static void launch_gemm(mtfjsp_encoder *e, const GemmArgs &a, const char *name, const GemmKernel &k)
 {
     Timed t(e, name);
     const int ntiles = (a.N + 15) / 16;
@@ -3602,15 +3621,11 @@ static void launch_gemm(mtfjsp_encoder *e, const GemmArgs &a, const char *name)
     (void)hipMemsetAsync(d_st, 0, 2048 * 8 * 8, e->stream);
     b.stamps = d_st;
 #endif
-    if constexpr (PRO == PRO_PLAIN) hipLaunchKernelGGL((k_gemm16<EPI, ACC>), dim3(grid), dim3(512), gemm16_lds_bytes(), e->stream, b);
-    else if constexpr (PRO == PRO_GIN0 || PRO == PRO_GIN0BN) hipLaunchKernelGGL((k_gemm_x6<PRO>), dim3(grid), dim3(512), gemm_x6_lds_bytes(), e->stream, b);
-    else {
-        if (b.Wx6 && !(e->f32_products & 1)) hipLaunchKernelGGL((k_gemm_x6<PRO>), dim3(grid), dim3(512), gemm_x6_lds_bytes(), e->stream, b);
-        else hipLaunchKernelGGL((k_gemm16p<PRO>), dim3(grid), dim3(512), gemm16_lds_bytes(), e->stream, b);
-    }
+    void *args[] = {&b};
+    (void)hipLaunchKernel(k.fn, dim3(grid), dim3(512), args, k.lds, e->stream);
 #ifdef MTFJSP_STAMP
     static int printed = 0;
-    if (PRO != PRO_PLAIN && printed < 40 && getenv("MTFJSP_STAMP_PRINT")) {
+    if (!k.plain && printed < 40 && getenv("MTFJSP_STAMP_PRINT")) {
         (void)hipStreamSynchronize(e->stream);
         std::vector<unsigned long long> hst(2048 * 8);
         (void)hipMemcpy(hst.data(), d_st, 2048 * 8 * 8, hipMemcpyDeviceToHost);
@@ -3637,176 +3652,148 @@ static GemmArgs gemm_args(const float *in, int N, const float *Wt, const float *
     return a;
 }
 
-// GIN encoder (gcn:109-197) with the weights under `pre` ("job_actor." / "global_critic."), followed by the graph mean
-// pool and (optionally) the candidate gather.  Uses BatchNorm accumulator slots 0..5.
+// The GIN encoder's six Linears and the BatchNorm behind each (gcn:109-197), by the reference's names under "<prefix>encoder.feature_extract.": the ONE
+// table of them.  Layer l of mtfjsp_gin_select.h is entry l.
+static const char *const GIN_LIN[6] = {"mlps.0.linears.0", "mlps.0.linears.1", "mlps.0.linears.2", "mlps.1.linears.0", "mlps.1.linears.1", "mlps.1.linears.2"};
+static const char *const GIN_BN[6] = {"mlps.0.batch_norms.0", "mlps.0.batch_norms.1", "batch_norms.0", "mlps.1.batch_norms.0", "mlps.1.batch_norms.1", "batch_norms.1"};
+struct GinLayer {
+    const float *W, *Wt, *bias;             // the Linear: torch layout, [in,out] copy (none for the 12 -> 128 first one), bias
+    const void *Wx6, *Wx32;                 // its operand images for k_gemm_x6 and k_gin_res ...
+    float sinv6, sinv32;                    // ... and 1 / the power-of-two scale folded into each (the first Linear's k_gemm_x6 image is an exact split: 1)
+    const float *gamma, *beta;              // the BatchNorm behind it
+};
+struct GinWeights { GinLayer l[6]; };
+// every device pointer a GIN forward under `pre` ("job_actor." / "global_critic.") can need, looked up once per forward (a weight that was never
+// loaded throws: MTFJSP_ERR_STATE at the C boundary)
+static GinWeights gin_weights(const mtfjsp_encoder *e, const char *pre)
+{
+    const std::string P = std::string(pre) + "encoder.feature_extract.";
+    GinWeights g{};
+    for (int i = 0; i < 6; i++) {
+        const std::string lin = P + GIN_LIN[i], bn = P + GIN_BN[i], w = lin + ".weight";
+        GinLayer &l = g.l[i];
+        l.W = e->w.at(w); l.Wt = i ? e->wt.at(w) : nullptr; l.bias = e->w.at(lin + ".bias");
+        l.Wx6 = e->wx6.at(w); l.sinv6 = i ? e->wx6_sinv.at(w) : 1.0f;
+        l.Wx32 = e->wx32.at(w); l.sinv32 = e->wx32_sinv.at(w);
+        l.gamma = e->w.at(bn + ".weight"); l.beta = e->w.at(bn + ".bias");
+    }
+    return g;
+}
+// what a GIN forward reads and writes (candidate == nullptr: no candidate gather, J = 0)
+struct GinIO {
+    const void *tasks_fea; const int32_t *ell_col; const float *ell_val; const int32_t *candidate; int J;
+    float *h_pooled, *cand_feat, *h_nodes;
+};
+// the request of a forward on this handle (mtfjsp_gin_select.h).  The create-time switches by the handle's values, MTFJSP_FUSE_POOL_MAXT once per process
+// (J10M10 x 8192: 264 us pooled in the heads launch, 240 us apart), MTFJSP_GIN_RES_GENERIC as it is NOW
+static GinRequest gin_request(const mtfjsp_encoder *e, const GinWeights &gw, bool job_actor, int J, bool h_nodes)
+{
+    static const int fuse_maxT = getenv("MTFJSP_FUSE_POOL_MAXT") ? atoi(getenv("MTFJSP_FUSE_POOL_MAXT")) : 64;
+    GinRequest q{};
+    q.B = e->cfg.batch; q.T = e->T; q.n_job = e->cfg.n_job; q.J = J; q.num_cu = e->num_cu; q.obs_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64;
+    q.job_actor = job_actor; q.h_nodes = h_nodes; q.per_instance = e->bn_mode != 0;
+    q.res_ok = e->res_ok; q.reduce = e->reduce_fn != nullptr; q.f32_products = e->f32_products; q.last_wx6 = gw.l[5].Wx6 != nullptr;
+    q.fuse_pair = e->fuse_pair; q.fuse_gin0 = e->fuse_gin0; q.fuse_pool = e->fuse_pool;
+    q.stream_order = e->stream_order; q.stream_nt = e->stream_nt; q.pool_s = e->pool_s; q.heads_pool_maxT = fuse_maxT;
+    q.force_generic = getenv("MTFJSP_GIN_RES_GENERIC");
+    return q;
+}
+static double *gin_slot(const mtfjsp_encoder *e, int s) { return e->stats + s * STAT_REP * 256; }
+// the arguments of a product step: the common ones from its layer's table entry and its slots, then what its kind adds
+static GemmArgs gin_gemm_args(const mtfjsp_encoder *e, const GinWeights &gw, const GinStep &s, const GinIO &io, double invN)
+{
+    const int B = e->cfg.batch, T = e->T;
+    float *const buf[4] = {nullptr, nullptr, e->zA, e->zB};       // (GinBuf; the raw features travel as tfea)
+    const GinLayer &l = gw.l[s.layer];
+    GemmArgs a = gemm_args(buf[s.src], B * T, l.Wt, l.bias, buf[s.dst]);
+    a.rev = s.rev; a.nt = s.nt;
+    a.Wx6 = l.Wx6; a.w_sinv = l.sinv6;
+    if (s.sin >= 0) { a.pro_stats = gin_slot(e, s.sin); a.pro_gamma = gw.l[s.sin].gamma; a.pro_beta = gw.l[s.sin].beta; a.pro_inv_rows = invN; }
+    if (s.sout >= 0) a.epi_stats = gin_slot(e, s.sout);
+    switch (s.kind) {
+    case GIN_STEP_GIN0BN:
+        a.Wx6_0 = gw.l[0].Wx6; a.bias0 = gw.l[0].bias; a.W0 = s.from_moments ? gw.l[0].W : nullptr;
+        [[fallthrough]];
+    case GIN_STEP_GIN0:
+        a.tfea = io.tasks_fea; a.feat_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64;
+        [[fallthrough]];
+    case GIN_STEP_AGG:
+        a.ell_col = io.ell_col; a.ell_val = io.ell_val; a.T = T;
+        break;
+    case GIN_STEP_STATS_ZERO:
+        a.zero_f32 = io.h_pooled; a.zero_count = B * HD;           // (the pooling pass adds into it; no launch of its own for the clearing)
+        break;
+    case GIN_STEP_POOL:
+        a.T = T; a.pooled = io.h_pooled; a.cand_feat = io.candidate ? io.cand_feat : nullptr; a.cand = io.candidate; a.pool_J = io.J;
+        a.pool_stats = gin_slot(e, 5); a.pool_gamma = gw.l[5].gamma; a.pool_beta = gw.l[5].beta; a.pool_inv_rows = invN;
+        break;
+    default: break;
+    }
+    return a;
+}
+
+// The streaming launches of a GIN forward (gcn:109-197), followed by the graph mean pool and (optionally) the candidate gather: the steps of the
+// forward's plan (mtfjsp_gin_select.h states which and why), in order.  Uses BatchNorm accumulator slots 0..5.
 static int reduce_stats(mtfjsp_encoder *e, double *st);
-static int run_gin(mtfjsp_encoder *e, const std::string &pre, const void *tasks_fea, const int32_t *ell_col, const float *ell_val,
-                   const int32_t *candidate, int J, float *h_pooled, float *cand_feat, float *h_nodes)
+static int run_gin(mtfjsp_encoder *e, const GinPlan &pl, const GinWeights &gw, const GinIO &io)
 {
     const int B = e->cfg.batch, T = e->T, N = B * T;
-    const std::string P = pre + "encoder.feature_extract.";
-    auto W = [&](const std::string &k) { return e->w.at(k); };
-    auto WT = [&](const std::string &k) { return e->wt.at(k); };
-    double *st = e->stats;
-    if (!e->gin_stats_clean) HIPCHK(e, hipMemsetAsync(st, 0, 6 * STAT_REP * 256 * sizeof(double), e->stream));
+    if (!e->gin_stats_clean) HIPCHK(e, hipMemsetAsync(e->stats, 0, 6 * STAT_REP * 256 * sizeof(double), e->stream));
     e->gin_stats_clean = false; e->gin_slot5_dirty = false;
     const double invN = 1.0 / ((double)N * e->reduce_scale);      // (exact multi-shard BatchNorm: rows of all shards)
-    const int pgrid = e->num_cu * 8;
-    int rrc = 0;
-    // Two Linears per launch (mtfjsp_gemm_pair.h): split products only
-    const bool pair = !(e->f32_products & 1) && (e->fuse_pair > 0 || (e->fuse_pair < 0 && (size_t)N * HD * 4 > ((size_t)256 << 20)));
-    // Round 6 (e->fuse_gin0; MTFJSP_FUSE_GIN0=0 switches it off): z0 = Linear0(aggregated features) is not stored.  Its BatchNorm sums come from the second
-    // moments of the 12 aggregated features (k_gin0_moments; MTFJSP_FUSE_GIN0=2: from a PRO_GIN0 launch with out == NULL, the two-launch form's bits), and
-    // the producers of the second launch form z0 again from the raw features (PRO_GIN0BN): 838 MB of the forward's traffic at 819 200 rows replaced by
-    // two reads of 52 MB.  f32 observations, split products (tests/test_encoder_sizes_gpu.py holds the forms against each other).
-    const bool fuse0 = e->fuse_gin0 && !(e->f32_products & 9) && !pair && e->cfg.obs_dtype == MTFJSP_OBS_F32 &&
-                       (size_t)N < ((size_t)1 << 24) && T >= 8;    // (row -> instance by an f32 reciprocal + one correction in k_gin0_moments and the PRO_GIN0BN producers: right for quotients below 2^21)
-    // (2: the sums by a statistics-only PRO_GIN0 launch — the two-launch form's bits; A/B and tests.  With a statistics reduction over several ranks
-    // slot 0 must hold the SAME quantities on every rank, and a rank that has left the split products after a range failure sums z0 itself: no moments then)
-    const bool mom0 = fuse0 && e->fuse_gin0 != 2 && !e->reduce_fn;
-    if (mom0) {
-        Timed t(e, "gin0_moments");
-        hipLaunchKernelGGL(k_gin0_moments, dim3(e->num_cu * 2), dim3(256), 0, e->stream, N, T, (const float *)tasks_fea, ell_col, ell_val, st + 0 * STAT_REP * 256);
-        if ((rrc = reduce_stats(e, st + 0 * STAT_REP * 256))) return rrc;
-    } else if (!(e->f32_products & 8)) {   // layer 0 / linear 0 with aggregation of the raw features, on the producer/consumer product kernel
-        GemmArgs a = gemm_args(nullptr, N, nullptr, W(P + "mlps.0.linears.0.bias"), fuse0 ? nullptr : e->zA);
-        a.tfea = tasks_fea; a.feat_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64; a.ell_col = ell_col; a.ell_val = ell_val; a.T = T;
-        a.epi_stats = st + 0 * STAT_REP * 256;
-        a.rev = e->stream_order;
-        a.Wx6 = e->wx6.at(P + "mlps.0.linears.0.weight"); a.w_sinv = 1.0f;
-        launch_gemm<PRO_GIN0, EPI_STATS>(e, a, fuse0 ? "gin0_stats_only" : "gin0_agg_linear12");
-        if ((rrc = reduce_stats(e, st + 0 * STAT_REP * 256))) return rrc;
-    } else {
-        Timed t(e, "gin0_agg_linear12");
-        if (e->cfg.obs_dtype == MTFJSP_OBS_F32)
-            hipLaunchKernelGGL((k_gin0<float>), dim3(pgrid), dim3(256), 0, e->stream, N, T, (const float *)tasks_fea, ell_col, ell_val,
-                               W(P + "mlps.0.linears.0.weight"), W(P + "mlps.0.linears.0.bias"), e->zA, st + 0 * STAT_REP * 256);
-        else
-            hipLaunchKernelGGL((k_gin0<double>), dim3(pgrid), dim3(256), 0, e->stream, N, T, (const double *)tasks_fea, ell_col, ell_val,
-                               W(P + "mlps.0.linears.0.weight"), W(P + "mlps.0.linears.0.bias"), e->zA, st + 0 * STAT_REP * 256);
-        if ((rrc = reduce_stats(e, st + 0 * STAT_REP * 256))) return rrc;      // (the same number of reductions per forward in every product mode)
-    }
-    // the launches alternate the direction in which a workgroup walks its rows (GemmArgs::rev): each starts on the part of its
-    // input that is still in the memory-side cache.  The aggregation product walks FORWARD (a row's job predecessor is the row
-    // before it: read a moment ago and still in L2; backward it was measured 251 against 234 us), which fixes the others
-    const int so = e->stream_order;
-    auto bn_gemm = [&](const float *in, float *out, int sin, const std::string &bn, const std::string &lin, int sout, int rev) {
-        GemmArgs a = gemm_args(in, N, WT(P + lin + ".weight"), W(P + lin + ".bias"), out);
-        a.rev = so ? rev : 0; a.nt = so && (e->stream_nt & 1);
-        a.pro_stats = st + sin * STAT_REP * 256; a.pro_gamma = W(P + bn + ".weight"); a.pro_beta = W(P + bn + ".bias"); a.pro_inv_rows = invN;
-        a.epi_stats = st + sout * STAT_REP * 256;
-        a.Wx6 = e->wx6.at(P + lin + ".weight"); a.w_sinv = e->wx6_sinv.at(P + lin + ".weight");
-        launch_gemm<PRO_BNRELU, EPI_STATS>(e, a, "gin_gemm_bn_relu");
-        if (!rrc) rrc = reduce_stats(e, st + sout * STAT_REP * 256);
-    };
-    // Two Linears per launch (mtfjsp_gemm_pair.h): pass 1 = the first product with no output (its BatchNorm sums only, slot `smid`),
-    // pass 2 = k_gemm_x6f: in -> bn(sin) -> lin1 -> bn(smid) -> lin2 -> out with the sums of slot `sout`.
-    auto bn_gemm_pair = [&](const float *in, float *out, int sin, const std::string &bn1, const std::string &lin1, int smid,
-                            const std::string &bn2, const std::string &lin2, int sout, int rev) {
-        {   // pass 1: statistics of z_b
-            GemmArgs a = gemm_args(in, N, WT(P + lin1 + ".weight"), W(P + lin1 + ".bias"), nullptr);
-            a.rev = so ? rev : 0; a.nt = so && (e->stream_nt & 1);
-            a.pro_stats = st + sin * STAT_REP * 256; a.pro_gamma = W(P + bn1 + ".weight"); a.pro_beta = W(P + bn1 + ".bias"); a.pro_inv_rows = invN;
-            a.epi_stats = st + smid * STAT_REP * 256;
-            a.Wx6 = e->wx6.at(P + lin1 + ".weight"); a.w_sinv = e->wx6_sinv.at(P + lin1 + ".weight");
-            launch_gemm<PRO_BNRELU, EPI_STATS>(e, a, "gin_gemm_stats_only");
-            if (!rrc) rrc = reduce_stats(e, st + smid * STAT_REP * 256);
+    for (int i = 0; i < pl.nsteps; i++) {
+        const GinStep &s = pl.step[i];
+        const GinLayer &l = gw.l[s.layer];
+        switch (s.kind) {
+        case GIN_STEP_MOMENTS: {
+            Timed t(e, s.family);
+            hipLaunchKernelGGL(k_gin0_moments, dim3(e->num_cu * 2), dim3(256), 0, e->stream, N, T, (const float *)io.tasks_fea, io.ell_col, io.ell_val, gin_slot(e, s.sout));
+            break;
         }
-        {   // pass 2
-            Timed t(e, "gin_gemm_pair");
+        case GIN_STEP_GIN0_VALU: {
+            Timed t(e, s.family);
+            if (s.kernel == GIN_K_GIN0_F64)
+                hipLaunchKernelGGL((k_gin0<double>), dim3(e->num_cu * 8), dim3(256), 0, e->stream, N, T, (const double *)io.tasks_fea, io.ell_col, io.ell_val,
+                                   l.W, l.bias, e->zA, gin_slot(e, s.sout));
+            else
+                hipLaunchKernelGGL((k_gin0<float>), dim3(e->num_cu * 8), dim3(256), 0, e->stream, N, T, (const float *)io.tasks_fea, io.ell_col, io.ell_val,
+                                   l.W, l.bias, e->zA, gin_slot(e, s.sout));
+            break;
+        }
+        case GIN_STEP_GIN0: case GIN_STEP_GIN0BN: case GIN_STEP_GEMM: case GIN_STEP_AGG: case GIN_STEP_STATS_ZERO: case GIN_STEP_POOL:
+            launch_gemm(e, gin_gemm_args(e, gw, s, io, invN), s.family, gin_gemm_kernel(s.kernel));
+            break;
+        case GIN_STEP_PAIR: {                                     // in -> bn(sin) -> layer -> bn(layer) -> layer + 1 -> out with the sums of slot sout
+            Timed t(e, s.family);
+            const GinLayer &l2 = gw.l[s.layer + 1];
             Gemm2Args g{};
-            g.a = gemm_args(in, N, WT(P + lin1 + ".weight"), W(P + lin1 + ".bias"), out);
-            g.a.rev = so ? rev ^ 1 : 0; g.a.nt = so && (e->stream_nt & 1);   // (opposite direction: it starts on what pass 1 read last)
-            g.a.pro_stats = st + sin * STAT_REP * 256; g.a.pro_gamma = W(P + bn1 + ".weight"); g.a.pro_beta = W(P + bn1 + ".bias"); g.a.pro_inv_rows = invN;
-            g.a.epi_stats = st + sout * STAT_REP * 256;
-            g.a.Wx6 = e->wx6.at(P + lin1 + ".weight"); g.a.w_sinv = e->wx6_sinv.at(P + lin1 + ".weight");
+            g.a = gin_gemm_args(e, gw, s, io, invN);
             g.a.range_flag = e->range_flag;
-            g.Wx6b = e->wx6.at(P + lin2 + ".weight"); g.w_sinvb = e->wx6_sinv.at(P + lin2 + ".weight"); g.biasb = W(P + lin2 + ".bias");
-            g.mid_stats = st + smid * STAT_REP * 256; g.mid_gamma = W(P + bn2 + ".weight"); g.mid_beta = W(P + bn2 + ".bias"); g.mid_inv_rows = invN;
+            g.Wx6b = l2.Wx6; g.w_sinvb = l2.sinv6; g.biasb = l2.bias;
+            g.mid_stats = gin_slot(e, s.layer); g.mid_gamma = l.gamma; g.mid_beta = l.beta; g.mid_inv_rows = invN;
             const int ntiles = (N + 15) / 16;
             int grid = (ntiles + 7) / 8;
             if (grid > e->num_cu) grid = e->num_cu;
             hipLaunchKernelGGL(k_gemm_x6f, dim3(grid), dim3(512), gemm_x6f_lds_bytes(), e->stream, g);
+            break;
         }
-        if (!rrc) rrc = reduce_stats(e, st + sout * STAT_REP * 256);
-    };
-    if (pair) bn_gemm_pair(e->zA, e->zB, 0, "mlps.0.batch_norms.0", "mlps.0.linears.1", 1, "mlps.0.batch_norms.1", "mlps.0.linears.2", 2, 0);
-    else {
-    if (fuse0) {
-        const std::string lin = "mlps.0.linears.1", bn = "mlps.0.batch_norms.0";
-        GemmArgs a = gemm_args(nullptr, N, WT(P + lin + ".weight"), W(P + lin + ".bias"), e->zB);
-        a.rev = 0; a.nt = 0;
-        a.tfea = tasks_fea; a.feat_f64 = 0; a.ell_col = ell_col; a.ell_val = ell_val; a.T = T;
-        a.Wx6_0 = e->wx6.at(P + "mlps.0.linears.0.weight"); a.bias0 = W(P + "mlps.0.linears.0.bias");
-        a.W0 = mom0 ? W(P + "mlps.0.linears.0.weight") : nullptr;
-        a.pro_stats = st + 0 * STAT_REP * 256; a.pro_gamma = W(P + bn + ".weight"); a.pro_beta = W(P + bn + ".bias"); a.pro_inv_rows = invN;
-        a.epi_stats = st + 1 * STAT_REP * 256;
-        a.Wx6 = e->wx6.at(P + lin + ".weight"); a.w_sinv = e->wx6_sinv.at(P + lin + ".weight");
-        launch_gemm<PRO_GIN0BN, EPI_STATS>(e, a, "gin0_bn_gemm");
-        if (!rrc) rrc = reduce_stats(e, st + 1 * STAT_REP * 256);
-    } else
-    bn_gemm(e->zA, e->zB, 0, "mlps.0.batch_norms.0", "mlps.0.linears.1", 1, 0);
-    bn_gemm(e->zB, e->zA, 1, "mlps.0.batch_norms.1", "mlps.0.linears.2", 2, 1);
-    }
-    const float *z2 = pair ? e->zB : e->zA;                        // where the first MLP's output is
-    float *z3 = pair ? e->zA : e->zB;
-    {   // layer 1 / linear 0: aggregation of h = relu(bn_outer0(z)) over the ELL adjacency
-        GemmArgs a = gemm_args(z2, N, WT(P + "mlps.1.linears.0.weight"), W(P + "mlps.1.linears.0.bias"), z3);
-        a.pro_stats = st + 2 * STAT_REP * 256; a.pro_gamma = W(P + "batch_norms.0.weight"); a.pro_beta = W(P + "batch_norms.0.bias"); a.pro_inv_rows = invN;
-        a.ell_col = ell_col; a.ell_val = ell_val; a.T = T;
-        a.rev = 0; a.nt = so && (e->stream_nt & 2);
-        a.epi_stats = st + 3 * STAT_REP * 256;
-        a.Wx6 = e->wx6.at(P + "mlps.1.linears.0.weight"); a.w_sinv = e->wx6_sinv.at(P + "mlps.1.linears.0.weight");
-        launch_gemm<PRO_AGG, EPI_STATS>(e, a, "gin_gemm_agg");
-        if (!rrc) rrc = reduce_stats(e, st + 3 * STAT_REP * 256);
-    }
-    if (pair) bn_gemm_pair(z3, e->zB, 3, "mlps.1.batch_norms.0", "mlps.1.linears.1", 4, "mlps.1.batch_norms.1", "mlps.1.linears.2", 5, 1);
-    else {
-    bn_gemm(e->zB, e->zA, 3, "mlps.1.batch_norms.0", "mlps.1.linears.1", 4, 1);
-    // Round 6 (e->fuse_pool; MTFJSP_FUSE_POOL=0 switches it off): the LAST Linear's output is not stored either.  A statistics-only pass of the product
-    // leaves its BatchNorm sums, a second pass forms it again and keeps only what the heads read — the per-instance means and the candidates' rows — in
-    // its epilogue: two passes without output instead of a product with output + k_job_pool_gather's read of it
-    const bool fuse_pool = e->fuse_pool && h_pooled && !h_nodes && T >= 16 && T < 65536 && (!candidate || (J > 0 && T % J == 0)) && (size_t)N < ((size_t)1 << 24) &&
-                           e->wx6.count(P + "mlps.1.linears.2.weight") && !(e->f32_products & 1);
-    if (fuse_pool) {
-        const std::string lin = "mlps.1.linears.2", bn = "mlps.1.batch_norms.1";
-        GemmArgs a = gemm_args(e->zA, N, WT(P + lin + ".weight"), W(P + lin + ".bias"), nullptr);
-        a.rev = 0; a.nt = 0;                                      // (read twice: plain loads; the second pass walks back from the end)
-        a.pro_stats = st + 4 * STAT_REP * 256; a.pro_gamma = W(P + bn + ".weight"); a.pro_beta = W(P + bn + ".bias"); a.pro_inv_rows = invN;
-        a.epi_stats = st + 5 * STAT_REP * 256;
-        a.Wx6 = e->wx6.at(P + lin + ".weight"); a.w_sinv = e->wx6_sinv.at(P + lin + ".weight");
-        a.zero_f32 = h_pooled; a.zero_count = B * HD;              // (the second pass adds into it; no launch of its own for the clearing)
-        launch_gemm<PRO_BNRELU, EPI_STATS>(e, a, "gin_gemm_stats_only");
-        a.zero_f32 = nullptr; a.zero_count = 0;
-        if (!rrc) rrc = reduce_stats(e, st + 5 * STAT_REP * 256);
-        if (rrc) return rrc;
-        a.rev = so ? 1 : 0; a.nt = so && (e->stream_nt & 1);
-        a.epi_stats = nullptr;
-        a.T = T; a.pooled = h_pooled; a.cand_feat = candidate ? cand_feat : nullptr; a.cand = candidate; a.pool_J = candidate ? J : 0;
-        a.pool_stats = st + 5 * STAT_REP * 256; a.pool_gamma = W(P + "batch_norms.1.weight"); a.pool_beta = W(P + "batch_norms.1.bias"); a.pool_inv_rows = invN;
-        launch_gemm<PRO_BNRELU, EPI_STATS>(e, a, "gin_gemm_pool");
-        if (candidate) {
-            Timed t(e, "cand_fixup");
-            hipLaunchKernelGGL(k_cand_fixup, dim3((B * J + 127) / 128), dim3(128), 0, e->stream, B, T, J, candidate, e->zA, st + 4 * STAT_REP * 256, W(P + bn + ".weight"), W(P + bn + ".bias"),
-                               WT(P + lin + ".weight"), W(P + lin + ".bias"), st + 5 * STAT_REP * 256, W(P + "batch_norms.1.weight"), W(P + "batch_norms.1.bias"), invN, cand_feat);
+        case GIN_STEP_FIXUP: {
+            Timed t(e, s.family);
+            hipLaunchKernelGGL(k_cand_fixup, dim3((B * io.J + 127) / 128), dim3(128), 0, e->stream, B, T, io.J, io.candidate, e->zA, gin_slot(e, s.sin), gw.l[s.sin].gamma, gw.l[s.sin].beta,
+                               l.Wt, l.bias, gin_slot(e, s.layer), l.gamma, l.beta, invN, io.cand_feat);
+            break;
         }
-        HIPCHK(e, hipGetLastError());
-        return MTFJSP_OK;
-    }
-    bn_gemm(e->zA, e->zB, 4, "mlps.1.batch_norms.1", "mlps.1.linears.2", 5, 0);
-    }
-    if (rrc) return rrc;
-    if (h_pooled) {                                               // h_pooled == NULL: the consumer (k_heads) normalises, pools and gathers itself
-        Timed t(e, "job_pool_gather");
-        // (the last product's partition: launch_gemm's grid and k_gemm_x6's tiles per workgroup)
-        const int ntiles = (N + 15) / 16, ggrid = std::min((ntiles + 7) / 8, e->num_cu), rpr = so && e->pool_s > 0 ? ((ntiles + ggrid - 1) / ggrid) * 16 : 0;
-        const int pool_grid = rpr ? ggrid * e->pool_s : (B < e->num_cu * 8 ? B : e->num_cu * 8);
-        if (so && (e->stream_nt & 4))
-            hipLaunchKernelGGL(k_job_pool_gather<1>, dim3(pool_grid), dim3(256), 0, e->stream, split_products_in_use(e) ? e->range_flag : nullptr, rpr, e->pool_s, B, T, candidate ? J : 0, e->zB, st + 5 * STAT_REP * 256, invN,
-                               W(P + "batch_norms.1.weight"), W(P + "batch_norms.1.bias"), candidate, h_pooled, cand_feat, h_nodes);
-        else
-            hipLaunchKernelGGL(k_job_pool_gather<0>, dim3(pool_grid), dim3(256), 0, e->stream, split_products_in_use(e) ? e->range_flag : nullptr, rpr, e->pool_s, B, T, candidate ? J : 0, e->zB, st + 5 * STAT_REP * 256, invN,
-                               W(P + "batch_norms.1.weight"), W(P + "batch_norms.1.bias"), candidate, h_pooled, cand_feat, h_nodes);
+        case GIN_STEP_GATHER: {
+            Timed t(e, s.family);
+            auto *k = s.kernel == GIN_K_GATHER_NT ? k_job_pool_gather<1> : k_job_pool_gather<0>;
+            hipLaunchKernelGGL(k, dim3(pl.pool_grid), dim3(256), 0, e->stream, range_word(e), pl.pool_rpr, pl.pool_s, B, T, io.J, e->zB, gin_slot(e, s.sin), invN,
+                               l.gamma, l.beta, io.candidate, io.h_pooled, io.cand_feat, io.h_nodes);
+            break;
+        }
+        default:
+            e->err = "streaming GIN launches: the plan holds a step of another path"; return MTFJSP_ERR_STATE;
+        }
+        if (s.reduce) { const int rrc = reduce_stats(e, gin_slot(e, s.sout)); if (rrc) return rrc; }
     }
     HIPCHK(e, hipGetLastError());
     return MTFJSP_OK;
@@ -3814,21 +3801,19 @@ static int run_gin(mtfjsp_encoder *e, const std::string &pre, const void *tasks_
 
 // The same encoder as ONE launch with register-resident activations (mtfjsp_gin_resident.h); h_pooled and cand_feat (when
 // `candidate` is given) are written normalised, as run_gin's k_job_pool_gather would.
-static int run_gin_resident(mtfjsp_encoder *e, const std::string &pre, const void *tasks_fea, const int32_t *ell_col, const float *ell_val,
-                            const int32_t *candidate, int J, float *h_pooled, float *cand_feat, float *h_nodes)
+// `warm`: the job actor's forward, whose heads launch follows this one.
+static int run_gin_resident(mtfjsp_encoder *e, const GinPlan &gp, const GinWeights &gw, const GinIO &io, bool warm)
 {
     const int B = e->cfg.batch, T = e->T;
-    const std::string P = pre + "encoder.feature_extract.";
-    auto W = [&](const std::string &k) { return e->w.at(k); };
+    const int32_t *candidate = io.candidate;
+    float *h_pooled = io.h_pooled, *cand_feat = io.cand_feat, *h_nodes = io.h_nodes;
     GinResArgs a{};
-    a.B = B; a.T = T; a.J = candidate ? J : 0; a.ipc = e->res_ipc;
-    a.tfea = tasks_fea; a.feat_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64; a.ell_col = ell_col; a.ell_val = ell_val;
-    const char *lin[6] = {"mlps.0.linears.0", "mlps.0.linears.1", "mlps.0.linears.2", "mlps.1.linears.0", "mlps.1.linears.1", "mlps.1.linears.2"};
-    const char *bn[6] = {"mlps.0.batch_norms.0", "mlps.0.batch_norms.1", "batch_norms.0", "mlps.1.batch_norms.0", "mlps.1.batch_norms.1", "batch_norms.1"};
+    a.B = B; a.T = T; a.J = io.J; a.ipc = e->res_ipc;
+    a.tfea = io.tasks_fea; a.feat_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64; a.ell_col = io.ell_col; a.ell_val = io.ell_val;
     for (int i = 0; i < 6; i++) {
-        a.Wx32[i] = e->wx32.at(P + lin[i] + ".weight");           // (the Linear biases cancel in the BatchNorms that follow them)
-        a.wsinv[i] = e->wx32_sinv.at(P + lin[i] + ".weight");
-        a.gamma[i] = W(P + bn[i] + ".weight"); a.beta[i] = W(P + bn[i] + ".bias");
+        a.Wx32[i] = gw.l[i].Wx32;                                  // (the Linear biases cancel in the BatchNorms that follow them)
+        a.wsinv[i] = gw.l[i].sinv32;
+        a.gamma[i] = gw.l[i].gamma; a.beta[i] = gw.l[i].beta;
     }
     for (int i = 0; i < 6; i++) {                                 // the image scales are powers of two: their exponents (the fixed-point statistics divide them out)
         int ex = 0;
@@ -3843,7 +3828,7 @@ static int run_gin_resident(mtfjsp_encoder *e, const std::string &pre, const voi
     a.bar = e->res_bar; a.epoch = e->res_epoch++; a.fail = e->res_fail; a.range_flag = e->range_flag;
     a.candidate = candidate; a.pooled = h_pooled; a.cand_feat = cand_feat; a.h_nodes = h_nodes; a.zspill = e->res_zspill;
     a.inv_rows = 1.0 / ((double)B * (double)T);
-    if (pre == "job_actor." && e->warm_heads) {
+    if (warm && e->warm_heads) {
         // what the heads launch behind this one reads first — the weight images of both actors' heads and of the GAT passes, last read a
         // rollout step ago and evicted from the XCDs' L2 since — is requested (one word per 128-byte line, dropped) in this kernel's last phase
         const char *keys[9] = {"job_actor.o_policy.linears.0.weight", "job_actor.job_critic.linears.0.weight", "job_actor.o_policy.linears.1.weight",
@@ -3866,10 +3851,10 @@ static int run_gin_resident(mtfjsp_encoder *e, const std::string &pre, const voi
 #endif
     {
         // (the step's forward, the post-terminal forward and the values-only forward all come through here: one rule, one instantiation per shape)
-        const GinResPlan pl = gin_res_plan_of(e, a.J, h_nodes != nullptr);
+        const GinResPlan &pl = gp.res;
         if (!pl.eligible || pl.ipc != e->res_ipc || pl.grid != e->res_grid) { e->err = "resident GIN: the launch plan does not match the handle"; return MTFJSP_ERR_STATE; }
         e->res_last_kernel = (int)pl.kernel;
-        Timed t(e, "gin_resident");
+        Timed t(e, gp.step[0].family);
         gin_res_launch(pl.kernel, e->res_grid, e->stream, a);
     }
 #ifdef GR_STAMP
@@ -4062,7 +4047,7 @@ static int run_gat(mtfjsp_encoder *e, const std::string &pre, const void *m_fea1
     }
     if (h_pooled) {
         Timed t(e, "mach_bn_pool");
-        hipLaunchKernelGGL(k_mach_bn_pool, dim3(B), dim3(128), 0, e->stream, split_products_in_use(e) ? e->range_flag : nullptr, B, M, e->node, st, 1.0 / ((double)R * e->reduce_scale), W(pre + "bn.weight"),
+        hipLaunchKernelGGL(k_mach_bn_pool, dim3(B), dim3(128), 0, e->stream, range_word(e), B, M, e->node, st, 1.0 / ((double)R * e->reduce_scale), W(pre + "bn.weight"),
                            W(pre + "bn.bias"), h_pooled);
     }
     HIPCHK(e, hipGetLastError());
@@ -4070,26 +4055,32 @@ static int run_gat(mtfjsp_encoder *e, const std::string &pre, const void *m_fea1
 }
 
 // per-instance BatchNorm variants (bn_mode 1): one workgroup per instance, one launch per path
-static int run_gin_inst(mtfjsp_encoder *e, const std::string &pre, const void *tasks_fea, const int32_t *ell_col, const float *ell_val,
-                        const int32_t *candidate, int J, float *h_pooled, float *cand_feat, float *h_nodes)
+static int run_gin_inst(mtfjsp_encoder *e, const GinPlan &gp, const GinWeights &gw, const GinIO &io)
 {
-    const std::string P = pre + "encoder.feature_extract.";
-    auto W = [&](const std::string &k) { return e->w.at(k); };
-    auto WT = [&](const std::string &k) { return e->wt.at(k); };
     GinInstArgs a{};
-    a.B = e->cfg.batch; a.T = e->T; a.J = candidate ? J : 0;
-    a.tfea = tasks_fea; a.feat_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64; a.ell_col = ell_col; a.ell_val = ell_val;
-    a.W0 = W(P + "mlps.0.linears.0.weight"); a.b0 = W(P + "mlps.0.linears.0.bias");
-    const char *lin[5] = {"mlps.0.linears.1", "mlps.0.linears.2", "mlps.1.linears.0", "mlps.1.linears.1", "mlps.1.linears.2"};
-    const char *bn[6] = {"mlps.0.batch_norms.0", "mlps.0.batch_norms.1", "batch_norms.0", "mlps.1.batch_norms.0", "mlps.1.batch_norms.1", "batch_norms.1"};
-    for (int i = 0; i < 5; i++) { a.Wt[i] = WT(P + lin[i] + ".weight"); a.bias[i] = W(P + lin[i] + ".bias"); }
-    for (int i = 0; i < 6; i++) { a.gamma[i] = W(P + bn[i] + ".weight"); a.beta[i] = W(P + bn[i] + ".bias"); }
-    a.zA = e->zA; a.zB = e->zB; a.cand = candidate; a.h_pooled = h_pooled; a.cand_feat = cand_feat; a.h_nodes = h_nodes;
-    Timed t(e, "gin_inst");
-    if (a.feat_f64) hipLaunchKernelGGL((k_gin_inst<double>), dim3(a.B), dim3(512), inst_lds_bytes(), e->stream, a);
+    a.B = e->cfg.batch; a.T = e->T; a.J = io.J;
+    a.tfea = io.tasks_fea; a.feat_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64; a.ell_col = io.ell_col; a.ell_val = io.ell_val;
+    a.W0 = gw.l[0].W; a.b0 = gw.l[0].bias;
+    for (int i = 0; i < 5; i++) { a.Wt[i] = gw.l[i + 1].Wt; a.bias[i] = gw.l[i + 1].bias; }
+    for (int i = 0; i < 6; i++) { a.gamma[i] = gw.l[i].gamma; a.beta[i] = gw.l[i].beta; }
+    a.zA = e->zA; a.zB = e->zB; a.cand = io.candidate; a.h_pooled = io.h_pooled; a.cand_feat = io.cand_feat; a.h_nodes = io.h_nodes;
+    Timed t(e, gp.step[0].family);
+    if (gp.step[0].kernel == GIN_K_INST_F64) hipLaunchKernelGGL((k_gin_inst<double>), dim3(a.B), dim3(512), inst_lds_bytes(), e->stream, a);
     else hipLaunchKernelGGL((k_gin_inst<float>), dim3(a.B), dim3(512), inst_lds_bytes(), e->stream, a);
     HIPCHK(e, hipGetLastError());
     return MTFJSP_OK;
+}
+// A GIN forward: the handle's plan for it (kept in e->gin_last: the caller reads path and pooling form there, mtfjsp_encoder_gin_launches reports it),
+// executed on the path the plan names
+static int gin_forward(mtfjsp_encoder *e, const GinWeights &gw, bool job_actor, const GinIO &io)
+{
+    const GinPlan &gp = e->gin_last = gin_plan(gin_request(e, gw, job_actor, io.J, io.h_nodes != nullptr));
+    e->gin_last_valid = true;
+    switch (gp.path) {
+    case GIN_PATH_INST: return run_gin_inst(e, gp, gw, io);
+    case GIN_PATH_SINGLE: return run_gin_resident(e, gp, gw, io, job_actor);
+    default: return run_gin(e, gp, gw, io);
+    }
 }
 static int run_gat_inst(mtfjsp_encoder *e, const std::string &pre, const void *m_fea1, const void *m_fea2, float *h_pooled)
 {
@@ -4364,16 +4355,11 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
     const int B = e->cfg.batch, J = e->cfg.n_job;
     auto W = [&](const std::string &k) { return e->w.at(k); };
     auto WI = [&](const std::string &k) { return e->wimg.at(k); };
-    // the heads kernel does BatchNorm+ReLU, graph pool and candidate gather itself — while T is small: a workgroup pools 16
-    // instances with 512 threads, which is too little parallelism for 100- or 400-row instances (measured: J20M20 x 2048 199 vs
-    // 81+113 us; J10M10 x 8192 job+machine heads 264 us fused vs 110 + 130 us with the stand-alone pool/gather kernel)
-    const bool resident = !e->bn_mode && e->res_ok && !e->reduce_fn && !(e->f32_products & (1 | 8 | 16));   // (a cross-shard reduction cannot happen inside the single launch)
-    static const int fuse_maxT = getenv("MTFJSP_FUSE_POOL_MAXT") ? atoi(getenv("MTFJSP_FUSE_POOL_MAXT")) : 64;   // (J10M10 x 8192: 264 us fused, 240 us apart)
-    const bool fuse_pool = !e->bn_mode && !resident && !h_nodes && e->T <= fuse_maxT;
-    rc = e->bn_mode ? run_gin_inst(e, "job_actor.", tasks_fea, ell_col, ell_val, candidate, J, h_pooled, e->cand_feat, h_nodes)
-         : resident ? run_gin_resident(e, "job_actor.", tasks_fea, ell_col, ell_val, candidate, J, h_pooled, e->cand_feat, h_nodes)
-                    : run_gin(e, "job_actor.", tasks_fea, ell_col, ell_val, candidate, J, fuse_pool ? nullptr : h_pooled, e->cand_feat, h_nodes);
+    // the path, the launches and who pools (this forward's heads launch among the candidates): mtfjsp_gin_select.h
+    const GinWeights gw = gin_weights(e, "job_actor.");
+    rc = gin_forward(e, gw, true, GinIO{tasks_fea, ell_col, ell_val, candidate, J, h_pooled, e->cand_feat, h_nodes});
     if (rc) return rc;
+    const GinPlan &gp = e->gin_last;
     // ---- heads (ac:205-293): score = L2 tanh(L1 tanh(Wa cand + Wb pooled + Wc hm + b0))
     const float *hm = h_m_prev;
     if (!hm) {                                                     // first decision of an episode: the learned `_input` row for every instance (a constant
@@ -4415,14 +4401,13 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
         ha.Wc1i = WI("job_actor.job_critic.linears.1.weight"); ha.bc1 = W("job_actor.job_critic.linears.1.bias");
         ha.wc2 = W("job_actor.job_critic.linears.2.weight"); ha.bc2 = W("job_actor.job_critic.linears.2.bias");
         ha.mask = job_mask; ha.scale = 1.0f; ha.prob = prob; ha.value = job_v;
-        if (fuse_pool) {
-            const std::string P = "job_actor.encoder.feature_extract.";
+        if (gp.pool == GIN_POOL_HEADS) {
             ha.X = e->zB; ha.pooled = nullptr; ha.pooled_out = h_pooled; ha.xgather = candidate; ha.xT = e->T; ha.xrelu = 1;
-            ha.xbn_stats = e->stats + 5 * STAT_REP * 256; ha.xbn_gamma = W(P + "batch_norms.1.weight"); ha.xbn_beta = W(P + "batch_norms.1.bias");
+            ha.xbn_stats = gin_slot(e, 5); ha.xbn_gamma = gw.l[5].gamma; ha.xbn_beta = gw.l[5].beta;
             ha.xbn_inv_rows = 1.0 / ((double)B * (double)e->T * e->reduce_scale);
             ha.zero_stats = e->stats; ha.zero_count = 5 * STAT_REP * 256;    // slots 0..4 are consumed; slot 5 is being read by this very
             e->gin_slot5_dirty = true;                                       // kernel and is zeroed by the machine heads (or a memset)
-        } else if (!e->bn_mode && !resident) {
+        } else if (gp.path == GIN_PATH_STREAM) {
             ha.zero_stats = e->stats; ha.zero_count = 6 * STAT_REP * 256;    // every GIN accumulator has been consumed by now
             e->gin_stats_clean = true;
         }
@@ -4599,23 +4584,21 @@ static int global_critic_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea,
     const int B = e->cfg.batch;
     auto W = [&](const std::string &k) { return e->w.at(k); };
     auto WT = [&](const std::string &k) { return e->wt.at(k); };
-    const bool resident = e->res_ok && !e->reduce_fn && !(e->f32_products & (1 | 8 | 16));
-    int rc = resident ? run_gin_resident(e, "global_critic.", tasks_fea, ell_col, ell_val, nullptr, 0, e->pooled_int, e->cand_feat, nullptr)
-                      : run_gin(e, "global_critic.", tasks_fea, ell_col, ell_val, nullptr, 0, e->pooled_int, e->cand_feat, nullptr);
+    int rc = gin_forward(e, gin_weights(e, "global_critic."), false, GinIO{tasks_fea, ell_col, ell_val, nullptr, 0, e->pooled_int, e->cand_feat, nullptr});
     if (rc) return rc;
     rc = run_gat(e, "global_critic.", m_fea1, m_fea2, e->u);
     if (rc) return rc;
     const float *W0t = WT("global_critic.critic.linears.0.weight");             // [pooled_m | pooled_o] (ac: torch.cat((h_g_m_pooled, h_g_o_pooled)))
     GemmArgs a = gemm_args(e->u, B, W0t, W("global_critic.critic.linears.0.bias"), e->c1);
-    launch_gemm<PRO_PLAIN, EPI_PLAIN>(e, a, "head_gemm");
+    launch_gemm(e, a, "head_gemm", plain_gemm<EPI_PLAIN>());
     GemmArgs b = gemm_args(e->pooled_int, B, W0t + HD * HD, nullptr, e->c1);
-    launch_gemm<PRO_PLAIN, EPI_TANH, true>(e, b, "head_gemm");
+    launch_gemm(e, b, "head_gemm", plain_gemm<EPI_TANH, true>());
     GemmArgs c = gemm_args(e->c1, B, WT("global_critic.critic.linears.1.weight"), W("global_critic.critic.linears.1.bias"), e->c2);
-    launch_gemm<PRO_PLAIN, EPI_TANH>(e, c, "head_gemm");
+    launch_gemm(e, c, "head_gemm", plain_gemm<EPI_TANH>());
     {
         Timed t(e, "small");
         hipLaunchKernelGGL(k_linear_small, dim3((B * 4 + 255) / 256), dim3(256), 0, e->stream, B, 4, e->c2, W("global_critic.critic.linears.2.weight"),
-                           W("global_critic.critic.linears.2.bias"), value4, split_products_in_use(e) ? e->range_flag : nullptr);
+                           W("global_critic.critic.linears.2.bias"), value4, range_word(e));
     }
     HIPCHK(e, hipGetLastError());
     return MTFJSP_OK;
@@ -4665,7 +4648,7 @@ extern "C" int mtfjsp_encoder_check(mtfjsp_encoder_t e, int32_t *gin_resident_ou
         // grid again the single launch comes back (one transient overlap does not leave the handle on the slow path for good)
         e->res_ok = res_census(e);
     }
-    if (gin_resident_out) *gin_resident_out = (e->res_ok && !e->reduce_fn && !(e->f32_products & (1 | 8 | 16))) ? 1 : 0;
+    if (gin_resident_out) *gin_resident_out = gin_single_launch_ok(e->res_ok, e->reduce_fn != nullptr, e->f32_products) ? 1 : 0;
     return rc;
 }
 extern "C" const char *mtfjsp_gin_res_kernel_name_for(int32_t batch, int32_t rows_per_instance, int32_t n_job, int32_t candidates, int32_t num_cu,
@@ -4679,6 +4662,41 @@ extern "C" const char *mtfjsp_gin_res_kernel_name_for(int32_t batch, int32_t row
 extern "C" const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e)
 {
     return e && e->res_last_kernel >= 0 ? GIN_RES_KERNEL_NAME[e->res_last_kernel] : nullptr;
+}
+// a plan's report: "path;pooling form;family:kernel,family:kernel,..." into buf, rev + 2 nt + 4 reduce of every step, k_job_pool_gather's rows per range and workgroups
+static int32_t gin_plan_report(const GinPlan &pl, char *buf, int32_t buf_len, int32_t *order_out, int32_t *pool_out)
+{
+    std::string s = std::string(GIN_PATH_NAME[pl.path]) + ";" + GIN_POOL_NAME[pl.pool] + ";";
+    for (int i = 0; i < pl.nsteps; i++) {
+        s += std::string(i ? "," : "") + pl.step[i].family + ":" + gin_kernel_name(pl, pl.step[i]);
+        if (order_out) order_out[i] = pl.step[i].rev + 2 * pl.step[i].nt + 4 * pl.step[i].reduce;
+    }
+    if (!buf || buf_len <= (int32_t)s.size()) return MTFJSP_ERR_ARG;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    if (pool_out) { pool_out[0] = pl.pool_rpr; pool_out[1] = pl.pool_grid; }
+    return pl.nsteps;
+}
+extern "C" int32_t mtfjsp_gin_launches_for(int32_t batch, int32_t rows_per_instance, int32_t n_job, int32_t candidates, int32_t num_cu, int32_t product_mode,
+                                           uint32_t flags, char *buf, int32_t buf_len, int32_t *order_out, int32_t *pool_out)
+{
+    if (batch < 1 || rows_per_instance < 1 || n_job < 1 || candidates < 0 || num_cu < 1 || product_mode < 0 || product_mode > 31) return MTFJSP_ERR_ARG;
+    auto env_int = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
+    GinRequest q{};
+    q.B = batch; q.T = rows_per_instance; q.n_job = n_job; q.J = candidates; q.num_cu = num_cu; q.obs_f64 = flags & MTFJSP_GIN_OBS_F64;
+    q.job_actor = !(flags & MTFJSP_GIN_CRITIC); q.h_nodes = flags & MTFJSP_GIN_NODE_OUTPUT; q.per_instance = flags & MTFJSP_GIN_PER_INSTANCE;
+    q.res_ok = !(flags & MTFJSP_GIN_NO_SINGLE) && !getenv("MTFJSP_NO_RESIDENT_GIN"); q.reduce = flags & MTFJSP_GIN_REDUCE; q.f32_products = product_mode;
+    q.last_wx6 = true;
+    q.fuse_pair = env_int("MTFJSP_FUSE_PAIR", 0); q.fuse_gin0 = env_int("MTFJSP_FUSE_GIN0", 1); q.fuse_pool = env_int("MTFJSP_FUSE_POOL", 1);
+    q.stream_order = getenv("MTFJSP_NO_STREAM_ORDER") ? 0 : 1; q.stream_nt = env_int("MTFJSP_STREAM_NT", 5); q.pool_s = env_int("MTFJSP_POOL_S", 4);
+    q.heads_pool_maxT = env_int("MTFJSP_FUSE_POOL_MAXT", 64);
+    q.force_generic = getenv("MTFJSP_GIN_RES_GENERIC");
+    return gin_plan_report(gin_plan(q), buf, buf_len, order_out, pool_out);
+}
+extern "C" int32_t mtfjsp_encoder_gin_launches(mtfjsp_encoder_t e, char *buf, int32_t buf_len, int32_t *order_out, int32_t *pool_out)
+{
+    if (!e) return MTFJSP_ERR_ARG;
+    if (!e->gin_last_valid) return MTFJSP_ERR_STATE;
+    return gin_plan_report(e->gin_last, buf, buf_len, order_out, pool_out);
 }
 extern "C" const char *mtfjsp_fused3_kernel_name_for(int32_t batch, int32_t n_job, int32_t n_machine, int32_t num_cu, int32_t obs_f64, int32_t env_tail, int32_t *grid_out)
 {

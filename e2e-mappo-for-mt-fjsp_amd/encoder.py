@@ -215,6 +215,10 @@ class Encoder:
         name = self.L.mtfjsp_encoder_gin_res_kernel_name(self.h)
         return name.decode() if name else None
 
+    def gin_launches(self):
+        """path, pooling form and launches of this handle's last GIN forward, as capi.gin_launches_for reports a plan (None: none yet)"""
+        return capi.encoder_gin_launches(self.h)
+
     def peek_gin_res(self):
         """diagnostic: (cand_feat [B*J,128] f32, statistics words [6,8,128,2] u64, (time-out, range) words) of the last single-launch GIN forward"""
         cand = np.empty((self.B * self.J, 128), dtype=np.float32)

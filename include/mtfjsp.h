@@ -662,6 +662,36 @@ int mtfjsp_encoder_peek_nodes_host(mtfjsp_encoder_t e, float *out_host, int64_t 
 const char *mtfjsp_gin_res_kernel_name_for(int32_t batch, int32_t rows_per_instance, int32_t n_job, int32_t candidates, int32_t num_cu,
                                            int32_t node_output, int32_t *ipc_out, int32_t *grid_out);
 const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e);
+/* Which path a GIN forward takes, who pools, and every launch it makes, in order — the library's one statement of the rule (csrc/mtfjsp_gin_select.h; both
+ * forwards plan with it and the streaming launches are that plan's steps).  No handle, no GPU.  batch instances of rows_per_instance node rows on num_cu
+ * compute units; n_job bounds the candidate table; candidates = candidates per instance of the forward (0: none); product_mode as
+ * mtfjsp_encoder_set_product_mode takes it.  flags: who asks, and the handle's answers that are not the shape's —
+ *   MTFJSP_GIN_CRITIC        the global critic asks (otherwise the job actor, whose heads launch can pool)
+ *   MTFJSP_GIN_NODE_OUTPUT   the node embeddings are requested
+ *   MTFJSP_GIN_PER_INSTANCE  per-instance BatchNorm mode (mtfjsp_encoder_set_bn_mode)
+ *   MTFJSP_GIN_OBS_F64       f64 observations
+ *   MTFJSP_GIN_NO_SINGLE     the handle's census of co-resident workgroups has not passed (or a launch has timed out since)
+ *   MTFJSP_GIN_REDUCE        a statistics reduction is installed (mtfjsp_encoder_set_stats_reduce)
+ * The weights are taken as loaded.  MTFJSP_FUSE_PAIR, MTFJSP_FUSE_GIN0, MTFJSP_FUSE_POOL, MTFJSP_NO_STREAM_ORDER, MTFJSP_STREAM_NT, MTFJSP_POOL_S,
+ * MTFJSP_FUSE_POOL_MAXT, MTFJSP_NO_RESIDENT_GIN and MTFJSP_GIN_RES_GENERIC are read per call under the names and defaults a handle uses (a handle reads
+ * them when it is created, MTFJSP_FUSE_POOL_MAXT once per process, MTFJSP_GIN_RES_GENERIC per forward).
+ * buf receives "path;pooling form;family:kernel,family:kernel,...": path = "per_instance" | "single_launch" | "streaming"; pooling form = "gin_kernel"
+ * (the per-instance / single-launch kernel itself) | "heads" (the job actor's heads launch) | "epilogue" (the epilogue of a second pass of the last
+ * product, + k_cand_fixup) | "pool_gather" (k_job_pool_gather); then each launch's timing family (mtfjsp_encoder_timing_query) and kernel.
+ * order_out (may be NULL; 12 entries): per launch, GemmArgs::rev (the rows walked backwards) + 2 * GemmArgs::nt (non-temporal input reads) + 4 where
+ * a statistics reduction follows the launch (the mtfjsp_encoder_set_stats_reduce callback, when one is installed).  pool_out (may be NULL; 2 entries): k_job_pool_gather's rows per
+ * range (0: plain instance order) and workgroups, 0 where it does not run.  Returns the number of launches, or MTFJSP_ERR_ARG (a size out of range, buf
+ * too small).
+ * mtfjsp_encoder_gin_launches: the same for the handle's last GIN forward, job actor's or global critic's (MTFJSP_ERR_STATE: none yet). */
+#define MTFJSP_GIN_CRITIC 1u
+#define MTFJSP_GIN_NODE_OUTPUT 2u
+#define MTFJSP_GIN_PER_INSTANCE 4u
+#define MTFJSP_GIN_OBS_F64 8u
+#define MTFJSP_GIN_NO_SINGLE 16u
+#define MTFJSP_GIN_REDUCE 32u
+int32_t mtfjsp_gin_launches_for(int32_t batch, int32_t rows_per_instance, int32_t n_job, int32_t candidates, int32_t num_cu, int32_t product_mode,
+                                uint32_t flags, char *buf, int32_t buf_len, int32_t *order_out, int32_t *pool_out);
+int32_t mtfjsp_encoder_gin_launches(mtfjsp_encoder_t e, char *buf, int32_t buf_len, int32_t *order_out, int32_t *pool_out);
 /* diagnostic (tests): what the handle's last single-launch GIN forward left, copied to host memory after synchronising the stream — the first `count`
  * floats of the candidate rows [B*J,128]; the 6 x 8 x 128 x 2 count-carrying statistics words of its six boundaries (csrc/mtfjsp_gin_resident.h,
  * gr_fix_encode); the (time-out, range) words.  Any of the three pointers may be NULL. */

@@ -127,9 +127,13 @@ def test_streaming_order_switches_do_not_change_results(monkeypatch):
 def test_pooling_epilogue_serves_any_candidate(monkeypatch, J, M, E, B):
     """The pooling epilogue of the last streaming product (MTFJSP_FUSE_POOL, default) takes candidate j from job j's block of rows, where the
     environment's candidates lie; a caller-made candidate elsewhere — another job's row, a row two slots share, a finished job's -1 — goes through
-    k_cand_fixup.  Same forward as the stored-output path (k_job_pool_gather) on a candidate array with all of those; T = 24 (J4M6) puts up to two
-    instances into a 16-row tile and an instance across workgroup ranges; T = 16 (J4M4) is the smallest the epilogue takes (every tile one instance), T = 150
-    with 11 instances a ragged last tile."""
+    k_cand_fixup.  Same forward as the stored-output path on a candidate array with all of those.  Which form pools is the plan's
+    (csrc/mtfjsp_gin_select.h), and the handles report it: the job actor's forward reaches the epilogue and k_cand_fixup only beyond 64 rows per
+    instance — T = 100 (J10M10 x 333: a ragged last tile) and T = 150 (J15M10 with 11 instances: a ragged last tile too) against k_job_pool_gather on
+    the second handle.  At T = 24 (J4M6), T = 16 (J4M4) and T = 32 (J8M4) BOTH handles pool and gather in the heads launch, which takes the
+    caller-made candidates through its own gather: those cases hold the fused first launch (first handle) against the two-launch form
+    (second handle) under such candidates, not the epilogue.  (The epilogue at 16 <= T <= 64 is the global critic's: tests/test_gin_select_gpu.py
+    runs it at T = 24.)"""
     import torch
     import mtfjsp_amd  # noqa: F401
     enc_mod = import_module("e2e-mappo-for-mt-fjsp_amd.encoder")
@@ -160,6 +164,12 @@ def test_pooling_epilogue_serves_any_candidate(monkeypatch, J, M, E, B):
         prob, h_o, job_v = e.job_actor_forward(env.tasks_fea, env.ell_col, env.ell_val, cand_t, mask, hm)
         torch.cuda.synchronize()
         outs.append((prob.cpu().numpy().copy(), h_o.cpu().numpy().copy(), job_v.cpu().numpy().copy()))
+        plan = e.gin_launches()
+        families = [s[0] for s in plan["steps"]]
+        assert plan["path"] == "streaming"
+        assert plan["pool"] == ("heads" if T <= 64 else "epilogue" if fuse == "1" else "pool_gather")
+        assert ("gin0_bn_gemm" in families) == (fuse == "1")
+        assert ("cand_fixup" in families) == (plan["pool"] == "epilogue") and ("job_pool_gather" in families) == (plan["pool"] == "pool_gather")
         e.close()
     scale = max(1.0, float(np.abs(outs[0][1]).max()))
     np.testing.assert_allclose(outs[0][1], outs[1][1], rtol=0, atol=2e-5 * scale)
