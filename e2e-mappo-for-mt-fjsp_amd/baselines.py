@@ -501,3 +501,101 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
     else:
         out.update(start_obj=out[name][2].copy(), history=np.zeros((0, N)), accepted=np.zeros((0, N), np.int8))
     return out
+
+
+# ---- evolutionary search on plans (csrc/mtfjsp_evolve.hip): a population of P plans per instance, recombined generation by generation
+def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.8, p_mut=0.3, moves=ALL_MOVES, left_shift=False, chunk=None,
+           device=0, obs_dtype="f32", name="GA"):
+    """A genetic algorithm on the (job string, machine per task) encoding, seeded with plans the library already has: `start` = one
+    (task [N,T], mach [N,T]) or a list of S <= P of them — any PLANS entry of `pdr_baselines`, `lookahead_baselines`, `beam_baselines`,
+    `random_baselines`, `local_search`, or `plans` of `evaluate.sample_best_of_k` — on the N instances t, p [N,T,M], tt [N,M,M], edge
+    [N,E,M/E] (args as for `pdr_baselines`).  Generation 0's population is member c = start[c % S] word for word; the P-copy handle
+    replays it and `group_reduce` gives every member's Objective and the best member, so "start_obj" is the best start's Objective.
+    Every later generation g = 1..generations: `DeviceBatchEnv.plan_offspring` (child 0 the best member as it is; every other child
+    two parents by binary tournaments, crossed with probability p_cross, one move of `moves` with probability p_mut — thresholds
+    round(p * 2**32), draws keyed by (seed, instance, child, g)), reset, T steps, final_costs, group_reduce: T + 4 launches, no torch
+    kernel, nothing read back before the last generation.  The replacement is generational with one elite: the best Objective never
+    rises and is never above the best start's.  The draws are keyed by the instance's number in the whole set: the results do not
+    depend on `chunk` (instances per pass; None: all N).  After the last generation the best plans are replayed on an n-instance
+    handle step by step, as `local_search` replays its plans; where no member is a valid plan the replay of member 0 ends there
+    (RuntimeError).  generations = 0 is a replay of the best start.
+    -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS {name: (task[N,T], mach[N,T])}, and
+       "start_obj" [N]: the best start's Objective;  "history" [generations, N]: the best Objective after every generation."""
+    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    P, G, moves = int(P), int(generations), int(moves)
+    if not 1 <= P <= 4096:
+        raise ValueError("P must be 1..4096")
+    if G < 0 or not 1 <= moves <= ALL_MOVES:
+        raise ValueError("generations must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN")
+    if not (0.0 <= float(p_cross) <= 1.0 and 0.0 <= float(p_mut) <= 1.0):
+        raise ValueError("p_cross and p_mut must be probabilities")
+    cross_thr, mut_thr = int(round(float(p_cross) * 2 ** 32)), int(round(float(p_mut) * 2 ** 32))
+    _rule_names([(name,), ("start_obj",), ("history",)])
+    t = np.asarray(t, np.float64)
+    N = t.shape[0]
+    starts = [start] if len(start) == 2 and np.ndim(start[0]) == 2 else list(start)
+    starts = [(np.ascontiguousarray(s[0], np.int32), np.ascontiguousarray(s[1], np.int32)) for s in starts]
+    if not 1 <= len(starts) <= P or any(s[0].shape != (N, T) or s[1].shape != (N, T) for s in starts):
+        raise ValueError("start must be (task [N,T], mach [N,T]) or a list of 1..P of them")
+    member = np.arange(P) % len(starts)
+    pop_task = np.stack([s[0] for s in starts], 1)[:, member]          # [N,P,T]: member c = start c % S
+    pop_mach = np.stack([s[1] for s in starts], 1)[:, member]
+    n = N if chunk is None else int(chunk)
+    if n < 1:
+        raise ValueError("chunk must be at least 1")
+    n = min(n, N)
+    src = DeviceBatchEnv(J, M, E, N, **kw)
+    env = top = None
+    parts = []
+    try:
+        src.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
+        dev = src.device
+        top = DeviceBatchEnv(J, M, E, n, **kw)                         # the final replay
+        env = DeviceBatchEnv(J, M, E, n * P, **kw)                     # the population
+        w3_top = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n, 1)
+        w3_all = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n * P, 1)
+        inst_of = torch.arange(n, dtype=torch.int32, device=dev)
+        copy_of = torch.arange(n * P, dtype=torch.int32, device=dev) // P
+        own = torch.arange(n, dtype=torch.int32, device=dev) * P        # every group's member 0
+        bufs = [tuple(torch.empty(T, n * P, dtype=torch.int32, device=dev) for _ in range(2)) for _ in range(2)]
+        cost4 = torch.empty(n * P, 4, dtype=torch.float64, device=dev)
+        done = torch.empty(n * P, dtype=torch.uint8, device=dev)
+        obj = torch.empty(n * P, dtype=torch.float64, device=dev)
+        best = torch.empty(G + 1, n, dtype=torch.int32, device=dev)
+        hist = torch.empty(G + 1, n, dtype=torch.float64, device=dev)
+        for lo in range(0, N, n):
+            m = min(n, N - lo)                                          # a last, smaller pass is padded with copies of its last instance
+            sel = np.minimum(np.arange(n) + lo, N - 1)
+            cur_t, cur_m = bufs[0]
+            cur_t.copy_(torch.as_tensor(np.ascontiguousarray(pop_task[sel].reshape(n * P, T).T)))      # [T,n*P]: row s = the actions of step s
+            cur_m.copy_(torch.as_tensor(np.ascontiguousarray(pop_mach[sel].reshape(n * P, T).T)))
+            top.fork_from(src, torch.clamp(inst_of + lo, max=N - 1), instance=True, state=False, obs=False)
+            env.fork_from(src, torch.clamp(copy_of + lo, max=N - 1), instance=True, state=False, obs=False)
+            env.scaler_init()                                           # the scaled components are produced but not used here
+            for g in range(G + 1):
+                if g:
+                    out_t, out_m = bufs[g & 1]
+                    env.plan_offspring(P, cur_t, cur_m, obj, best[g - 1], seed, g, lo, cross_thr, mut_thr, moves, out_t, out_m, False, False)
+                    cur_t, cur_m = out_t, out_m
+                env.reset(w3_all)
+                for s in range(T):
+                    env.step(cur_t[s], cur_m[s])
+                env.final_costs(cost4, done)                            # a rejected action leaves done = 0: the member is not eligible
+                env.group_reduce(n, P, cost4, done, w, obj=obj, best=best[g], best_obj=hist[g], front=False)
+            col = best[G]
+            pick = torch.where(col < 0, own, col).long()                # a group without an eligible member: its member 0, which the replay rejects
+            fin_t, fin_m = cur_t.index_select(1, pick).contiguous(), cur_m.index_select(1, pick).contiguous()
+            top.scaler_init()
+            top.reset(w3_top)                                           # pdrs:675 reset(Random_weight_type="eval")
+            cum, prev = replay_episode(top, T, lambda s: (fin_t[s], fin_m[s]), f"{name} evolve")
+            host = lambda x, k=m: x[..., :k].cpu().numpy()              # noqa: E731
+            parts.append(dict(cum=cum[:m], prev=prev[:m], task=host(fin_t).T.copy(), mach=host(fin_m).T.copy(), start_obj=host(hist[0]),
+                              history=host(hist[1:])))
+    finally:
+        for e in (top, env, src):
+            if e is not None:
+                e.close()
+    r = {k: np.concatenate([x[k] for x in parts], axis=-1 if k == "history" else 0) for k in parts[0]}
+    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, w)
+    out.update(start_obj=r["start_obj"], history=r["history"].reshape(G, N))
+    return out

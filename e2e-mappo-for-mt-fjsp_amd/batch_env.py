@@ -231,6 +231,46 @@ class DeviceBatchEnv:
             capi.check(self.L.mtfjsp_plan_neighbours_critical(*args, *(C.c_void_p(None if x is None else x.data_ptr()) for x in path)), self.h)
         return task_out, mach_out, kind_out
 
+    def plan_offspring(self, P, src_task, src_mach, src_obj, src_best=None, seed=0, generation=0, first_instance=0, cross_thr=1 << 32,
+                       mut_thr=0, moves=7, task_out=None, mach_out=None, parent_out=True, kind_out=True):
+        """This handle holds N populations of P plans (batch = N*P, member c of group n = element n*P + c).  src_task, src_mach: int32
+        device tensors [T, N*P] in history layout, the current population; src_obj [N*P] f64 and src_best [N] int32 (or None): `obj`
+        and `best` of `group_reduce` for it.
+        -> (task [T, N*P], mach [T, N*P], parent [N*P, 2] int32, kind [N*P] int8) device tensors, the offspring: with src_best child 0
+        of every group is its best member word for word (parent -1, -1; kind -1); every other child has parents A and B chosen by two
+        binary tournaments on src_obj, is crossed (precedence-preserving order crossover of the job strings, a coin per task for
+        the machine) iff its Philox word is below cross_thr, takes one move of `plan_neighbours` out of `moves` iff another is below
+        mut_thr (thresholds in [0, 2^32]), and is decoded.  parent = the columns of A and B (B = -1 without crossover); kind = 0
+        without mutation, else the move drawn.  The draws are keyed by (seed, first_instance + n, c, generation) — include/mtfjsp.h
+        has the rule.  A child that cannot be formed (a parent that is no plan) is a column of -1.  task_out / mach_out: tensors to
+        write into (not overlapping the sources); parent_out / kind_out: True, a tensor, or None / False.  One launch
+        (mtfjsp_plan_offspring), nothing read back."""
+        P, T, B, dev = int(P), self.T, self.B, self.device
+        for x in (src_task, src_mach):
+            assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and tuple(x.shape) == (T, B)
+        assert src_obj.is_cuda and src_obj.dtype == torch.float64 and src_obj.is_contiguous() and src_obj.numel() == B
+        if src_best is not None:
+            assert src_best.is_cuda and src_best.dtype == torch.int32 and src_best.is_contiguous() and src_best.numel() * max(P, 1) == B
+        task_out = torch.empty(T, B, dtype=torch.int32, device=dev) if task_out is None else task_out
+        mach_out = torch.empty(T, B, dtype=torch.int32, device=dev) if mach_out is None else mach_out
+        for x in (task_out, mach_out):
+            assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and tuple(x.shape) == (T, B)
+
+        def buf(x, shape, dt):
+            if x is None or x is False:
+                return None
+            if x is True:
+                return torch.empty(shape, dtype=dt, device=dev)
+            assert x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == int(np.prod(shape))
+            return x
+        parent_out, kind_out = buf(parent_out, (B, 2), torch.int32), buf(kind_out, (B,), torch.int8)
+        self._plan_keep = (src_task, src_mach, src_obj, src_best)       # alive until the launch has run
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else None)     # noqa: E731
+        capi.check(self.L.mtfjsp_plan_offspring(self.h, P, src_task.data_ptr(), src_mach.data_ptr(), src_obj.data_ptr(), ptr(src_best), int(seed),
+                                                int(generation), int(first_instance), int(cross_thr), int(mut_thr), int(moves),
+                                                task_out.data_ptr(), mach_out.data_ptr(), ptr(parent_out), ptr(kind_out)), self.h)
+        return task_out, mach_out, parent_out, kind_out
+
     def critical_path(self, col=None, n=None, task_out=None, arc_out=None, len_out=None):
         """One critical path per row out of this handle's schedules as they stand (mtfjsp_critical_path: one launch, nothing read
         back).  col: int32 device tensor [n] — row i describes instance col[i]; an entry outside [0, B) gives an empty row — or None:

@@ -26,16 +26,9 @@
 #include "../../include/mtfjsp.h"
 
 #include "mtfjsp_env_dev.h"
+#include "mtfjsp_plan_dev.h"
 #include "mtfjsp_wave_select.h"
 
-#define PLAN_WAVES 4
-#define PLAN_THREADS (PLAN_WAVES * WAVE)
-#define PLAN_LDS_SOFT (64 * 1024)      // the tile shrinks (64 -> 32 -> 16 copies) to stay below this: two workgroups per CU
-#define PLAN_LDS_HARD (160 * 1024)     // what a workgroup can have at all: the smallest tile may use it
-#define PLAN_TAG_MOVE 0x6d6f7665u      // "move"
-#define PLAN_SWAP 1
-#define PLAN_INSERT 2
-#define PLAN_REASSIGN 4
 #define PLAN_CRIT_SWAP 8
 #define PLAN_CRIT_REASSIGN 16
 #define PLAN_CRIT (PLAN_CRIT_SWAP | PLAN_CRIT_REASSIGN)
@@ -54,19 +47,6 @@ struct PlanArgs {
     const int *path_task, *path_len;   // [B/K,T], [B/K]: read by the CRIT instantiations only
     const int8_t *path_arc;            // [B/K,T]
 };
-
-// LDS of one wave is written by some lanes and read by others: the hardware keeps a wave's LDS operations in order, this keeps hipcc from moving them
-__device__ __forceinline__ void plan_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t plan_mulhi(uint32_t w, uint32_t n) { return (uint32_t)(((uint64_t)w * (uint64_t)n) >> 32); }
-__device__ __forceinline__ int plan_below(unsigned long long b)          // set bits of b in the lanes below this one
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-}
 
 // bytes of LDS: the tile's cells, then per wave the incumbent's tasks (u16 [T]), the machine of every task (i16 [T]) and the
 // operations of every job seen in earlier passes (i32 [J]); crit: per wave also the position of every task in the incumbent, the
@@ -250,13 +230,6 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_neighbours(PlanArgs A)
             A.mach_out[(size_t)s * B + gl] = (int)(int16_t)(word >> 16);
         }
     }
-}
-
-static bool plan_overlap(const void *a, unsigned __int128 na, const void *b, unsigned __int128 nb)
-{
-    if (!a || !b) return false;
-    const unsigned __int128 x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
 }
 
 // both entry points: max_moves = 7 for the plain one, whose launches are the CRIT = false instantiations whatever else is passed

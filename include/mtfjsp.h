@@ -412,6 +412,52 @@ int mtfjsp_plan_neighbours_critical(mtfjsp_handle_t h, int32_t K, const int32_t 
                                     int32_t *task_out, int32_t *mach_out, int8_t *kind_out, const int32_t *path_task, const int8_t *path_arc,
                                     const int32_t *path_len);
 
+/* ------------------------------------------------------------------ evolutionary search on plans: offspring of a population */
+/* Recombination over the same machinery: a population of P plans per instance lives in one handle of N*P (member c of group n =
+ * element g = n*P + c), one launch turns it into its offspring, the P copies replay them (mtfjsp_reset, T x mtfjsp_step), and
+ * mtfjsp_final_costs and mtfjsp_group_reduce write what the next generation selects by: obj_out and best_out.  T + 4 launches a
+ * generation, nothing read back.  Replacement is generational with one elite, so the best objective never rises.  The reference has
+ * no counterpart.
+ *
+ * mtfjsp_plan_offspring: h = the handle of the copies (batch = N*P); it gives t, the device and the stream, and must hold instances
+ * (MTFJSP_ERR_STATE otherwise).  All inputs are device data that is never read back.  src_task, src_mach: int32 [T, N*P] in history
+ * layout, column g = member g: the current population.  src_obj: binary64 [N*P], what mtfjsp_group_reduce wrote as obj_out (NaN = not
+ * eligible).  src_best: int32 [N], its best_out, or NULL.  cross_thr, mut_thr in [0, 2^32]: an event happens iff its Philox word is
+ * below the threshold (2^32: always, 0: never).  moves: the mutation's mask, 1..7, as for mtfjsp_plan_neighbours.  task_out, mach_out:
+ * int32 [T, N*P], row s ready for mtfjsp_step.  parent_out: int32 [N*P, 2] or NULL: the columns of parents A and B; B = -1 where no
+ * crossover was drawn; -1, -1 for the elite.  kind_out: int8 [N*P] or NULL: -1 for the elite, 0 where no mutation was drawn, else
+ * the move drawn (1, 2, 4), whether or not it changed the plan.
+ * Every draw is Philox4x32-10 of counter ((uint32)(first_instance + n), c, (uint32)generation, tag) under the key ((uint32)seed,
+ * (uint32)(seed >> 32)) — ONLY THE LOW 32 BITS of the instance number and of the generation enter, as in the move stream; every
+ * uniform integer below n is (w * n) >> 32.  Bit i of a stream of tag X is bit i % 32 of word (i / 32) % 4 of the block of tag
+ * X + i / 128.
+ *   child 0     with src_best: column src_best[n] word for word (column n*P where src_best[n] is outside [n*P, (n+1)*P)); no draw.
+ *               With src_best == NULL child 0 is a child like the others
+ *   parents     tag 0x70617265 "pare": i_k = (w_k * P) >> 32, k = 0..3.  A = the better of members i0 and i1, B = the better of i2
+ *               and i3: the smaller src_obj; a NaN loses to any number; equal values, or two NaNs, go to the lower member index
+ *   crossover   tag 0x63726f73 "cros": iff w0 < cross_thr.  Precedence-preserving order crossover of the job strings q_A, q_B
+ *               (q[s] = task[s] / n_machine): job j is in S iff bit j of the stream of tag 0x6a736574 "jset" is set; q'[s] = q_A[s]
+ *               where q_A[s] is in S; the other positions, ascending, take the entries of q_B that are not in S in q_B's order.  The
+ *               machine of task a is mu_A[a] if bit a of the stream of tag 0x6d616368 "mach" is set, else mu_B[a].  Without
+ *               crossover q' = q_A, mu' = mu_A
+ *   mutation    the same "cros" block: iff w1 < mut_thr.  One move exactly as mtfjsp_plan_neighbours defines SWAP, INSERT and
+ *               REASSIGN, from the words of tag "move" with round = generation, applied to q' and mu' (REASSIGN's a = the task at
+ *               position x of q' decoded)
+ *   decode      as mtfjsp_plan_neighbours: task'[s] = q'[s]*n_machine + (number of s' < s with q'[s'] == q'[s]), mach'[s] = mu'[task'[s]]
+ * A child of a parent that is no plan is -1 in every row (mtfjsp_step rejects it, it stays ineligible): a parent (A, and B where a
+ * crossover was drawn) with a task outside [0, T) or a machine outside [0, n_machine), or one that does not hold every task exactly
+ * once (wrong operation counts: the fill would run short or long, a task would have no machine).  The order of a job's operations in
+ * a parent does not matter: only its job string is read.  The elite is -1 in every row iff an entry of its column is out of range.
+ * parent_out and kind_out are written all the same.  No access leaves the arrays.
+ * MTFJSP_ERR_ARG, nothing written: P < 1, batch % P != 0, moves == 0 or > 7, a threshold above 2^32, a null src_task / src_mach /
+ * src_obj / task_out / mach_out, an output array that overlaps a source array or another output; n_job*n_machine too large for 16
+ * plans in a workgroup's LDS (beyond about 1400).
+ * One launch (k_plan_offspring) on h's stream, no read-back, no synchronisation: mtfjsp_plan_neighbours' tile of children in LDS;
+ * a wave keeps both parents of its child in LDS and compacts the fill with ballots. */
+int mtfjsp_plan_offspring(mtfjsp_handle_t h, int32_t P, const int32_t *src_task, const int32_t *src_mach, const double *src_obj,
+                          const int32_t *src_best, uint64_t seed, uint64_t generation, uint64_t first_instance, uint64_t cross_thr,
+                          uint64_t mut_thr, uint32_t moves, int32_t *task_out, int32_t *mach_out, int32_t *parent_out, int8_t *kind_out);
+
 /* ------------------------------------------------------------------ dispatch-rule baselines */
 /* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
  * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"
