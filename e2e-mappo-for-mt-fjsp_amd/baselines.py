@@ -14,7 +14,7 @@ import torch
 
 from . import capi
 from .batch_env import DeviceBatchEnv
-from .evaluate import COST_KEYS, best_of_k_rollout, episode_results, parse_args, replay_episode
+from .evaluate import COST_KEYS, CopyGroups, best_of_k_rollout, episode_results, parse_args, replay_episode
 
 M_RULE_NAMES = ["SPT", "SEC"]                                                        # pdrs:729
 O_RULE_NAMES = ["FIFO", "MOR", "LWKR_T_o", "LWKR_PT_o", "MWKR_T_o", "MWKR_PT_o"]     # pdrs:730
@@ -401,7 +401,8 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
     the reduction keeps the lowest copy among equal objectives: it survives ties, and the best Objective never rises.  The draws
     are keyed by the instance's number in the whole set: the results do not depend on `chunk` (instances per pass; None: all N).
     After the last round the best plans are replayed on an n-instance handle step by step, as `beam_baselines` replays its plans;
-    a start plan that is no valid plan ends there (RuntimeError).  rounds = 0 is a plain replay of `start`; K = 1 never moves.
+    a start plan that is no valid plan ends there (RuntimeError).  The handles, the passes, the round after the move kernel and
+    that replay are `evaluate.CopyGroups`'.  rounds = 0 is a plain replay of `start`; K = 1 never moves.
     `moves` may also hold MOVE_CRIT_SWAP and MOVE_CRIT_REASSIGN (CRIT_MOVES: both; ALL_MOVES | CRIT_MOVES: all five kinds): a move
     changes the makespan only if it breaks an arc of a critical path, so these take one machine arc of the incumbent's critical
     path between two jobs and turn it round, or put one task of the path on another machine.  The path is read off the device
@@ -410,92 +411,51 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS {name: (task[N,T], mach[N,T])}, and
        "start_obj" [N]: the Objective of `start`;  "history" [rounds, N]: the best Objective after every round;
        "accepted" [rounds, N] int8: the move that gave the round's best copy (MOVE_*, 8 and 16 included), -1 where the incumbent stayed."""
-    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    N, T = CopyGroups.sizes(t, args)
     K, R, moves = int(K), int(rounds), int(moves)
     if not 1 <= K <= 4096:
         raise ValueError("K must be 1..4096")
     if R < 0 or not 1 <= moves <= (ALL_MOVES | CRIT_MOVES):
         raise ValueError("rounds must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN | MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN")
     _rule_names([(name,), ("start_obj",), ("history",), ("accepted",)])
-    t = np.asarray(t, np.float64)
-    N = t.shape[0]
     st_task, st_mach = np.ascontiguousarray(start[0], np.int32), np.ascontiguousarray(start[1], np.int32)
     if st_task.shape != (N, T) or st_mach.shape != (N, T):
         raise ValueError("start must be (task [N,T], mach [N,T])")
-    n = N if chunk is None else int(chunk)
-    if n < 1:
-        raise ValueError("chunk must be at least 1")
-    n = min(n, N)
-    src = DeviceBatchEnv(J, M, E, N, **kw)
-    env = top = None
-    parts = []
-    try:
-        src.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
-        dev = src.device
-        top = DeviceBatchEnv(J, M, E, n, **kw)                         # the final replay
-        w3_top = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n, 1)
-        inst_of = torch.arange(n, dtype=torch.int32, device=dev)
+    with CopyGroups(t, p, tt, edge, args, K, chunk, copies=R > 0, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
+        n, dev, env, top = g.n, g.dev, g.env, g.top
+        path = None
         if R:
-            env = DeviceBatchEnv(J, M, E, n * K, **kw)                 # the copies
-            w3_all = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n * K, 1)
-            copy_of = torch.arange(n * K, dtype=torch.int32, device=dev) // K
-            own = torch.arange(n, dtype=torch.int32, device=dev) * K    # every group's copy 0
-            bufs = [tuple(torch.empty(T, n * K, dtype=torch.int32, device=dev) for _ in range(2)) for _ in range(2)]
-            cost4 = torch.empty(n * K, 4, dtype=torch.float64, device=dev)
-            done = torch.empty(n * K, dtype=torch.uint8, device=dev)
             obj0 = torch.empty(n * K, dtype=torch.float64, device=dev)
             best = torch.empty(R, n, dtype=torch.int32, device=dev)
             hist = torch.empty(R, n, dtype=torch.float64, device=dev)
             kind = torch.empty(R, n * K, dtype=torch.int8, device=dev)
-            path = None
             if moves & CRIT_MOVES:                                      # every group's critical path: tasks, arcs, length
                 path = (torch.empty(n, T, dtype=torch.int32, device=dev), torch.empty(n, T, dtype=torch.int8, device=dev),
                         torch.empty(n, dtype=torch.int32, device=dev))
-        for lo in range(0, N, n):
-            m = min(n, N - lo)                                          # a last, smaller pass is padded with copies of its last instance
-            sel = np.minimum(np.arange(n) + lo, N - 1)
-            cur_t = torch.as_tensor(np.ascontiguousarray(st_task[sel].T), device=dev)       # [T,n]: row s = the actions of step s
-            cur_m = torch.as_tensor(np.ascontiguousarray(st_mach[sel].T), device=dev)
-            top.fork_from(src, torch.clamp(inst_of + lo, max=N - 1), instance=True, state=False, obs=False)
-            if R:
-                env.fork_from(src, torch.clamp(copy_of + lo, max=N - 1), instance=True, state=False, obs=False)
-                env.scaler_init()                                       # the scaled components are produced but not used here
+        for lo, m in g.passes():
+            cur_t = torch.as_tensor(np.ascontiguousarray(g.pad(st_task).T), device=dev)     # [T,n]: row s = the actions of step s
+            cur_m = torch.as_tensor(np.ascontiguousarray(g.pad(st_mach).T), device=dev)
             col = None
-            if R and path is not None:                                  # the start plans' schedules, for round 0's directed moves
+            if path is not None:                                        # the start plans' schedules, for round 0's directed moves
                 top.scaler_init()
-                top.reset(w3_top)
+                top.reset(g.w3_top)
                 for s in range(T):
                     top.step(cur_t[s], cur_m[s])
                 top.critical_path(None, None, *path)
             for r in range(R):
-                out_t, out_m = bufs[r & 1]
+                out_t, out_m = g.plan_bufs(r)
                 env.plan_neighbours(K, cur_t, cur_m, col, seed, r, lo, moves, out_t, out_m, kind[r], critical=path)
-                env.reset(w3_all)
-                for s in range(T):
-                    env.step(out_t[s], out_m[s])
-                env.final_costs(cost4, done)                            # a rejected action leaves done = 0: the copy is not eligible
-                env.group_reduce(n, K, cost4, done, w, obj=obj0 if r == 0 else False, best=best[r], best_obj=hist[r], front=False)
+                g.round(out_t, out_m, obj0 if r == 0 else False, best[r], hist[r])
                 if path is not None:                                    # of the best copies, while their state is still there (-1: an empty path)
                     env.critical_path(best[r], None, *path)
                 cur_t, cur_m, col = out_t, out_m, best[r]
             if R:
-                pick = torch.where(col < 0, own, col).long()            # a group without an eligible copy: its copy 0, which the replay rejects
-                cur_t, cur_m = cur_t.index_select(1, pick).contiguous(), cur_m.index_select(1, pick).contiguous()
                 acc = torch.where(best < 0, torch.full_like(best, -1), kind.gather(1, best.clamp(min=0).long()).to(torch.int32)).to(torch.int8)
-            top.scaler_init()
-            top.reset(w3_top)                                           # pdrs:675 reset(Random_weight_type="eval")
-            cum, prev = replay_episode(top, T, lambda s: (cur_t[s], cur_m[s]), f"{name} local-search")
-            host = lambda x, k=m: x[..., :k].cpu().numpy()              # noqa: E731
-            part = dict(cum=cum[:m], prev=prev[:m], task=host(cur_t).T.copy(), mach=host(cur_m).T.copy())
-            if R:
-                part.update(start_obj=host(obj0.view(n, K)[:, 0]), history=host(hist), accepted=host(acc))
-            parts.append(part)
-    finally:
-        for e in (top, env, src):
-            if e is not None:
-                e.close()
-    r = {k: np.concatenate([x[k] for x in parts], axis=-1 if k in ("history", "accepted") else 0) for k in parts[0]}
-    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, w)
+                g.finish(cur_t, cur_m, col, f"{name} local-search", start_obj=obj0.view(n, K)[:, 0], history=hist, accepted=acc)
+            else:
+                g.finish(cur_t, cur_m, None, f"{name} local-search")
+    r = g.collect(last_axis=("history", "accepted"))
+    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
     if R:
         out.update(start_obj=r["start_obj"], history=r["history"], accepted=r["accepted"])
     else:
@@ -517,11 +477,11 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
     kernel, nothing read back before the last generation.  The replacement is generational with one elite: the best Objective never
     rises and is never above the best start's.  The draws are keyed by the instance's number in the whole set: the results do not
     depend on `chunk` (instances per pass; None: all N).  After the last generation the best plans are replayed on an n-instance
-    handle step by step, as `local_search` replays its plans; where no member is a valid plan the replay of member 0 ends there
-    (RuntimeError).  generations = 0 is a replay of the best start.
+    handle step by step, as `local_search` replays its plans (`evaluate.CopyGroups`, which also holds the handles and the round);
+    where no member is a valid plan the replay of member 0 ends there (RuntimeError).  generations = 0 is a replay of the best start.
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS {name: (task[N,T], mach[N,T])}, and
        "start_obj" [N]: the best start's Objective;  "history" [generations, N]: the best Objective after every generation."""
-    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    N, T = CopyGroups.sizes(t, args)
     P, G, moves = int(P), int(generations), int(moves)
     if not 1 <= P <= 4096:
         raise ValueError("P must be 1..4096")
@@ -531,8 +491,6 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
         raise ValueError("p_cross and p_mut must be probabilities")
     cross_thr, mut_thr = int(round(float(p_cross) * 2 ** 32)), int(round(float(p_mut) * 2 ** 32))
     _rule_names([(name,), ("start_obj",), ("history",)])
-    t = np.asarray(t, np.float64)
-    N = t.shape[0]
     starts = [start] if len(start) == 2 and np.ndim(start[0]) == 2 else list(start)
     starts = [(np.ascontiguousarray(s[0], np.int32), np.ascontiguousarray(s[1], np.int32)) for s in starts]
     if not 1 <= len(starts) <= P or any(s[0].shape != (N, T) or s[1].shape != (N, T) for s in starts):
@@ -540,62 +498,23 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
     member = np.arange(P) % len(starts)
     pop_task = np.stack([s[0] for s in starts], 1)[:, member]          # [N,P,T]: member c = start c % S
     pop_mach = np.stack([s[1] for s in starts], 1)[:, member]
-    n = N if chunk is None else int(chunk)
-    if n < 1:
-        raise ValueError("chunk must be at least 1")
-    n = min(n, N)
-    src = DeviceBatchEnv(J, M, E, N, **kw)
-    env = top = None
-    parts = []
-    try:
-        src.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
-        dev = src.device
-        top = DeviceBatchEnv(J, M, E, n, **kw)                         # the final replay
-        env = DeviceBatchEnv(J, M, E, n * P, **kw)                     # the population
-        w3_top = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n, 1)
-        w3_all = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n * P, 1)
-        inst_of = torch.arange(n, dtype=torch.int32, device=dev)
-        copy_of = torch.arange(n * P, dtype=torch.int32, device=dev) // P
-        own = torch.arange(n, dtype=torch.int32, device=dev) * P        # every group's member 0
-        bufs = [tuple(torch.empty(T, n * P, dtype=torch.int32, device=dev) for _ in range(2)) for _ in range(2)]
-        cost4 = torch.empty(n * P, 4, dtype=torch.float64, device=dev)
-        done = torch.empty(n * P, dtype=torch.uint8, device=dev)
+    with CopyGroups(t, p, tt, edge, args, P, chunk, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
+        n, dev, env = g.n, g.dev, g.env
         obj = torch.empty(n * P, dtype=torch.float64, device=dev)
         best = torch.empty(G + 1, n, dtype=torch.int32, device=dev)
         hist = torch.empty(G + 1, n, dtype=torch.float64, device=dev)
-        for lo in range(0, N, n):
-            m = min(n, N - lo)                                          # a last, smaller pass is padded with copies of its last instance
-            sel = np.minimum(np.arange(n) + lo, N - 1)
-            cur_t, cur_m = bufs[0]
-            cur_t.copy_(torch.as_tensor(np.ascontiguousarray(pop_task[sel].reshape(n * P, T).T)))      # [T,n*P]: row s = the actions of step s
-            cur_m.copy_(torch.as_tensor(np.ascontiguousarray(pop_mach[sel].reshape(n * P, T).T)))
-            top.fork_from(src, torch.clamp(inst_of + lo, max=N - 1), instance=True, state=False, obs=False)
-            env.fork_from(src, torch.clamp(copy_of + lo, max=N - 1), instance=True, state=False, obs=False)
-            env.scaler_init()                                           # the scaled components are produced but not used here
-            for g in range(G + 1):
-                if g:
-                    out_t, out_m = bufs[g & 1]
-                    env.plan_offspring(P, cur_t, cur_m, obj, best[g - 1], seed, g, lo, cross_thr, mut_thr, moves, out_t, out_m, False, False)
+        for lo, m in g.passes():
+            cur_t, cur_m = g.plan_bufs(0)
+            cur_t.copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_task).reshape(n * P, T).T)))    # [T,n*P]: row s = the actions of step s
+            cur_m.copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_mach).reshape(n * P, T).T)))
+            for gen in range(G + 1):
+                if gen:
+                    out_t, out_m = g.plan_bufs(gen)
+                    env.plan_offspring(P, cur_t, cur_m, obj, best[gen - 1], seed, gen, lo, cross_thr, mut_thr, moves, out_t, out_m, False, False)
                     cur_t, cur_m = out_t, out_m
-                env.reset(w3_all)
-                for s in range(T):
-                    env.step(cur_t[s], cur_m[s])
-                env.final_costs(cost4, done)                            # a rejected action leaves done = 0: the member is not eligible
-                env.group_reduce(n, P, cost4, done, w, obj=obj, best=best[g], best_obj=hist[g], front=False)
-            col = best[G]
-            pick = torch.where(col < 0, own, col).long()                # a group without an eligible member: its member 0, which the replay rejects
-            fin_t, fin_m = cur_t.index_select(1, pick).contiguous(), cur_m.index_select(1, pick).contiguous()
-            top.scaler_init()
-            top.reset(w3_top)                                           # pdrs:675 reset(Random_weight_type="eval")
-            cum, prev = replay_episode(top, T, lambda s: (fin_t[s], fin_m[s]), f"{name} evolve")
-            host = lambda x, k=m: x[..., :k].cpu().numpy()              # noqa: E731
-            parts.append(dict(cum=cum[:m], prev=prev[:m], task=host(fin_t).T.copy(), mach=host(fin_m).T.copy(), start_obj=host(hist[0]),
-                              history=host(hist[1:])))
-    finally:
-        for e in (top, env, src):
-            if e is not None:
-                e.close()
-    r = {k: np.concatenate([x[k] for x in parts], axis=-1 if k == "history" else 0) for k in parts[0]}
-    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, w)
+                g.round(cur_t, cur_m, obj, best[gen], hist[gen])
+            g.finish(cur_t, cur_m, best[G], f"{name} evolve", start_obj=hist[0], history=hist[1:])
+    r = g.collect(last_axis=("history",))
+    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
     out.update(start_obj=r["start_obj"], history=r["history"].reshape(G, N))
     return out

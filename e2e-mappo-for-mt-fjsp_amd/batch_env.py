@@ -30,6 +30,20 @@ def step_kernel_for(n_job, n_machine, batch, obs_f32=False, lds_max=160 * 1024):
     return name.decode(), g.value, nb.value, bool(ov.value)
 
 
+def _out(x, shape, dt, dev):
+    """an optional output: True -> a new tensor, None / False -> None (not computed), a tensor -> itself, to write into"""
+    if x is None or x is False:
+        return None
+    if x is True:
+        return torch.empty(shape, dtype=dt, device=dev)
+    assert x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == int(np.prod(shape))
+    return x
+
+
+def _ptr(x):
+    return C.c_void_p(None if x is None else x.data_ptr())
+
+
 class DeviceBatchEnv:
     def __init__(self, n_job, n_machine, n_edge, batch, left_shift=True, obs_dtype="f64", device=0,
                  gamma=0.99, w_cfg=(0.4, 0.4, 0.2), scaling_divisor=1.0):
@@ -168,21 +182,12 @@ class DeviceBatchEnv:
         assert cost4.is_cuda and cost4.dtype == torch.float64 and cost4.is_contiguous() and cost4.numel() == N * K * 4
         assert done.is_cuda and done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == N * K
         dev = self.device
-
-        def buf(x, n, dt):
-            if x is None or x is False:
-                return None
-            if x is True:
-                return torch.empty(n, dtype=dt, device=dev)
-            assert x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == n
-            return x
         # (an out-of-range N or K is the library's MTFJSP_ERR_ARG; the buffers below are then never written)
-        obj = buf(obj, max(N * K, 0), torch.float64); best = buf(best, max(N, 0), torch.int32)
-        best_obj = buf(best_obj, max(N, 0), torch.float64); front = buf(front, max(N * K, 0), torch.uint8)
+        obj = _out(obj, max(N * K, 0), torch.float64, dev); best = _out(best, max(N, 0), torch.int32, dev)
+        best_obj = _out(best_obj, max(N, 0), torch.float64, dev); front = _out(front, max(N * K, 0), torch.uint8, dev)
         w = (C.c_double * 3)(*[float(x) for x in w_cfg])
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else None)     # noqa: E731
-        capi.check(self.L.mtfjsp_group_reduce(self.h, N, K, cost4.data_ptr(), done.data_ptr(), w, ptr(obj), ptr(best), ptr(best_obj),
-                                              ptr(front)), self.h)
+        capi.check(self.L.mtfjsp_group_reduce(self.h, N, K, cost4.data_ptr(), done.data_ptr(), w, _ptr(obj), _ptr(best), _ptr(best_obj),
+                                              _ptr(front)), self.h)
         return obj, best, best_obj, front
 
     # ---- neighbourhood moves on plans (csrc/mtfjsp_plan.hip): local search over the groups of copies
@@ -210,16 +215,10 @@ class DeviceBatchEnv:
         mach_out = torch.empty(T, self.B, dtype=torch.int32, device=dev) if mach_out is None else mach_out
         for x in (task_out, mach_out):
             assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and tuple(x.shape) == (T, self.B)
-        if kind_out is True:
-            kind_out = torch.empty(self.B, dtype=torch.int8, device=dev)
-        elif kind_out is False:
-            kind_out = None
-        if kind_out is not None:
-            assert kind_out.is_cuda and kind_out.dtype == torch.int8 and kind_out.is_contiguous() and kind_out.numel() == self.B
+        kind_out = _out(kind_out, (self.B,), torch.int8, dev)
         self._plan_keep = (src_task, src_mach, src_col, critical)       # alive until the launch has run
-        args = (self.h, K, src_task.data_ptr(), src_mach.data_ptr(), src_task.shape[1],
-                C.c_void_p(src_col.data_ptr() if src_col is not None else None), int(seed), int(round), int(first_instance), int(moves),
-                task_out.data_ptr(), mach_out.data_ptr(), C.c_void_p(kind_out.data_ptr() if kind_out is not None else None))
+        args = (self.h, K, src_task.data_ptr(), src_mach.data_ptr(), src_task.shape[1], _ptr(src_col), int(seed), int(round), int(first_instance),
+                int(moves), task_out.data_ptr(), mach_out.data_ptr(), _ptr(kind_out))
         if critical is None and int(moves) <= 7:
             capi.check(self.L.mtfjsp_plan_neighbours(*args), self.h)
         else:
@@ -228,7 +227,7 @@ class DeviceBatchEnv:
                 N = self.B // max(K, 1)
                 for x, dt, shape in zip(path, (torch.int32, torch.int8, torch.int32), ((N, T), (N, T), (N,))):
                     assert x.is_cuda and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape
-            capi.check(self.L.mtfjsp_plan_neighbours_critical(*args, *(C.c_void_p(None if x is None else x.data_ptr()) for x in path)), self.h)
+            capi.check(self.L.mtfjsp_plan_neighbours_critical(*args, *(_ptr(x) for x in path)), self.h)
         return task_out, mach_out, kind_out
 
     def plan_offspring(self, P, src_task, src_mach, src_obj, src_best=None, seed=0, generation=0, first_instance=0, cross_thr=1 << 32,
@@ -255,20 +254,11 @@ class DeviceBatchEnv:
         mach_out = torch.empty(T, B, dtype=torch.int32, device=dev) if mach_out is None else mach_out
         for x in (task_out, mach_out):
             assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and tuple(x.shape) == (T, B)
-
-        def buf(x, shape, dt):
-            if x is None or x is False:
-                return None
-            if x is True:
-                return torch.empty(shape, dtype=dt, device=dev)
-            assert x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == int(np.prod(shape))
-            return x
-        parent_out, kind_out = buf(parent_out, (B, 2), torch.int32), buf(kind_out, (B,), torch.int8)
+        parent_out, kind_out = _out(parent_out, (B, 2), torch.int32, dev), _out(kind_out, (B,), torch.int8, dev)
         self._plan_keep = (src_task, src_mach, src_obj, src_best)       # alive until the launch has run
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else None)     # noqa: E731
-        capi.check(self.L.mtfjsp_plan_offspring(self.h, P, src_task.data_ptr(), src_mach.data_ptr(), src_obj.data_ptr(), ptr(src_best), int(seed),
+        capi.check(self.L.mtfjsp_plan_offspring(self.h, P, src_task.data_ptr(), src_mach.data_ptr(), src_obj.data_ptr(), _ptr(src_best), int(seed),
                                                 int(generation), int(first_instance), int(cross_thr), int(mut_thr), int(moves),
-                                                task_out.data_ptr(), mach_out.data_ptr(), ptr(parent_out), ptr(kind_out)), self.h)
+                                                task_out.data_ptr(), mach_out.data_ptr(), _ptr(parent_out), _ptr(kind_out)), self.h)
         return task_out, mach_out, parent_out, kind_out
 
     def critical_path(self, col=None, n=None, task_out=None, arc_out=None, len_out=None):
@@ -291,7 +281,7 @@ class DeviceBatchEnv:
         for x, dt, shape in ((task_out, torch.int32, (n, T)), (arc_out, torch.int8, (n, T)), (len_out, torch.int32, (n,))):
             assert x.is_cuda and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape
         self._crit_keep = col                                           # alive until the launch has run
-        capi.check(self.L.mtfjsp_critical_path(self.h, n, C.c_void_p(col.data_ptr() if col is not None else None), task_out.data_ptr(),
+        capi.check(self.L.mtfjsp_critical_path(self.h, n, _ptr(col), task_out.data_ptr(),
                                                arc_out.data_ptr(), len_out.data_ptr()), self.h)
         return task_out, arc_out, len_out
 

@@ -8,14 +8,12 @@
 //                           with probability mut_thr / 2^32 takes one move of mtfjsp_plan_neighbours, and is decoded as that kernel decodes.
 // Integer arithmetic and comparisons only (Philox words, (w * n) >> 32, binary64 <): the outputs must equal a host model element for
 // element.
-// Shape: k_plan_neighbours' — a workgroup of 4 waves builds a TILE of consecutive children (64, 32 or 16 by T) in LDS cells of odd row
-// pitch, every wave a quarter of them one after the other, lanes over positions, and every output row leaves as one contiguous run.
-// What differs: a child has parents of its own, so a wave keeps two of them in LDS (tasks by position, machine by task) and reloads one
-// only where it changes; the set S and the machine coins are the Philox words themselves, one block per lane, kept as bit maps; the
-// crossover's fill is a stream compaction (ballot + mbcnt ranks of B's entries outside S into a list, position s outside S reads
-// list[rank(s)]).
+// Shape: k_plan_neighbours' — the tile, the move, the decoding's ranks, the tile's way out and the host side of the launch are
+// mtfjsp_plan_dev.h's, used by both.  What is here: a child has parents of its own, so a wave keeps two of them in LDS (tasks by position,
+// machine by task) and reloads one only where it changes; the set S and the machine coins are the Philox words themselves, one block
+// per lane, kept as bit maps; the crossover's fill is a stream compaction (ballot + mbcnt ranks of B's entries outside S into a list,
+// position s outside S reads list[rank(s)]).
 #include <hip/hip_runtime.h>
-#include <limits.h>
 #include <stdint.h>
 
 #include "../../include/mtfjsp.h"
@@ -37,7 +35,7 @@ struct EvoArgs {
     const int *src_task, *src_mach;    // [T,B]
     const double *src_obj;             // [B]
     const int *src_best;               // [B/P] or null
-    uint32_t seed_lo, seed_hi, gen_lo, first_lo, moves, n_moves;
+    uint32_t seed_lo, seed_hi, ctr_lo, first_lo, moves, n_moves;   // ctr_lo: the generation
     unsigned long long cross_thr, mut_thr;
     int *task_out, *mach_out;          // [T,B]
     int *parent_out;                   // [B,2] or null
@@ -115,17 +113,17 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_offspring(EvoArgs A)
                 const int s = s0 + lane, sc = s < T ? s : T - 1;
                 const int tk = A.src_task[(size_t)sc * B + col], mc = A.src_mach[(size_t)sc * B + col];
                 badm |= __ballot(!((unsigned)tk < (unsigned)T && (unsigned)mc < (unsigned)M));
-                if (s < T) cell[(size_t)s * pitch + ct] = ((uint32_t)tk & 0xFFFFu) | ((uint32_t)mc << 16);
+                if (s < T) cell[(size_t)s * pitch + ct] = plan_cell(tk, mc);   // (an entry out of range: the column is killed below)
             }
             kill = badm != 0;
         } else {
             // ---- the draws (wave-uniform): two tournaments, the crossover and mutation events
-            uint32_t w[4] = {inst, (uint32_t)c, A.gen_lo, EVO_TAG_PARE};
+            uint32_t w[4] = {inst, (uint32_t)c, A.ctr_lo, EVO_TAG_PARE};
             philox4x32(w, A.seed_lo, A.seed_hi);
             const double *obj = A.src_obj + base;
             const int ma = uni(evo_better(obj, (int)plan_mulhi(w[0], (uint32_t)P), (int)plan_mulhi(w[1], (uint32_t)P)));
             const int mbm = uni(evo_better(obj, (int)plan_mulhi(w[2], (uint32_t)P), (int)plan_mulhi(w[3], (uint32_t)P)));
-            uint32_t v[4] = {inst, (uint32_t)c, A.gen_lo, EVO_TAG_CROS};
+            uint32_t v[4] = {inst, (uint32_t)c, A.ctr_lo, EVO_TAG_CROS};
             philox4x32(v, A.seed_lo, A.seed_hi);
             const bool cross = (unsigned long long)v[0] < A.cross_thr, mut = (unsigned long long)v[1] < A.mut_thr;
             const long colA = base + ma, colB = base + mbm;
@@ -136,12 +134,12 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_offspring(EvoArgs A)
             const bool bad = badA || (cross && badB);
             // ---- S and the machine coins: bit j % 32 of word (j / 32) % 4 of block j / 128 = bit j of the map.  No crossover: all of A
             for (int l = lane; l < A.sw; l += WAVE) {
-                uint32_t u[4] = {inst, (uint32_t)c, A.gen_lo, EVO_TAG_JSET + (uint32_t)(l >> 2)};
+                uint32_t u[4] = {inst, (uint32_t)c, A.ctr_lo, EVO_TAG_JSET + (uint32_t)(l >> 2)};
                 philox4x32(u, A.seed_lo, A.seed_hi);
                 sb[l] = cross ? evo_word(u, l & 3) : 0xFFFFFFFFu;
             }
             for (int l = lane; l < A.mw; l += WAVE) {
-                uint32_t u[4] = {inst, (uint32_t)c, A.gen_lo, EVO_TAG_MACH + (uint32_t)(l >> 2)};
+                uint32_t u[4] = {inst, (uint32_t)c, A.ctr_lo, EVO_TAG_MACH + (uint32_t)(l >> 2)};
                 philox4x32(u, A.seed_lo, A.seed_hi);
                 mb[l] = cross ? evo_word(u, l & 3) : 0xFFFFFFFFu;
             }
@@ -171,19 +169,12 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_offspring(EvoArgs A)
                 nH += __popcll(hb);
             }
             plan_wave_sync();
-            // ---- the mutation: one move of k_plan_neighbours on q', mu'
+            // ---- the mutation: one move of k_plan_neighbours (plan_draw) on q', mu'
             int move = 0, kind = 0, x = 0, y = 0, a = 0, am = -1;
             bool reassign = false;
             if (mut) {
-                uint32_t m4[4] = {inst, (uint32_t)c, A.gen_lo, PLAN_TAG_MOVE};
-                philox4x32(m4, A.seed_lo, A.seed_hi);
-                uint32_t mv = A.moves;
-                for (int k = (int)plan_mulhi(m4[0], A.n_moves); k > 0; k--) mv &= mv - 1;
-                kind = (int)(mv & (0u - mv));
-                x = uni((int)plan_mulhi(m4[1], (uint32_t)T));
-                y = T >= 2 ? (int)plan_mulhi(m4[2], (uint32_t)(T - 1)) : 0;
-                y += (T >= 2 && y >= x) ? 1 : 0;
-                move = (T < 2 && kind != PLAN_REASSIGN) ? 0 : kind;
+                const PlanMove d = plan_draw(inst, (uint32_t)c, A.ctr_lo, A.seed_lo, A.seed_hi, A.moves, A.n_moves, T);
+                kind = d.kind; move = d.move; x = d.x; y = d.y;
                 if (move == PLAN_REASSIGN) {                           // a = the task at position x of q' decoded; F = its other feasible machines, ascending = lane order
                     const int jx = uni((int)qn[x]);
                     int rk = 0;
@@ -193,66 +184,32 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_offspring(EvoArgs A)
                     }
                     a = rk < M ? jx * M + rk : 0;                      // (rk >= M only for parents that are no plans: the child is -1 anyway)
                     const int old_m = ((mb[a >> 5] >> (a & 31)) & 1u) ? (int)muA[a] : (int)muB[a];
-                    const double tv = A.t[((size_t)g * T + a) * M + (lane < M ? lane : M - 1)];
-                    const bool feas = lane < M && tv >= 0 && lane != old_m;
-                    const unsigned long long fb = __ballot(feas);
-                    const int nf = __popcll(fb);
-                    const int pick = (int)plan_mulhi(m4[2], (uint32_t)nf);
-                    const unsigned long long sel = __ballot(feas && plan_below(fb) == pick);
-                    reassign = nf > 0;
-                    am = reassign ? (int)__builtin_ctzll(sel) : -1;
+                    reassign = plan_other_machine(A.t, ((size_t)g * T + a) * M, M, old_m, d.wy, lane, &am) > 0;
                 }
             }
             kind_o = mut ? kind : 0;
             // ---- q' gathered through the move's position map, the operation ranks, the machines
             for (int s0 = 0; s0 < T; s0 += WAVE) {
                 const int s = s0 + lane;
-                int src = s;
-                if (move == PLAN_SWAP) src = s == x ? y : (s == y ? x : s);
-                if (move == PLAN_INSERT) {                              // q.pop(x), q.insert(y, it)
-                    if (s == y) src = x;
-                    else if (x < y && s >= x && s < y) src = s + 1;
-                    else if (y < x && s > y && s <= x) src = s - 1;
-                }
-                src = src < T ? src : T - 1;
-                const int qv = (int)qn[src];
+                const int qv = (int)qn[plan_src(move, s, x, y, T)];
                 const bool live = s < T;
-                int rank = 0;
-                bool last = false;                                      // the pass's last position of its job
-                for (int j = 0; j < J; j++) {                           // one wave-uniform ballot per job
-                    const unsigned long long b = __ballot(live && qv == j);
-                    if (qv == j) { rank = plan_below(b); last = (b >> lane) == 1ull; }
-                }
-                rank += cnt[qv];
-                plan_wave_sync();
-                if (live && last) cnt[qv] = rank + 1;
-                plan_wave_sync();
+                const int rank = plan_rank<true>(qv, live, J, lane, cnt);
                 const bool okr = rank < M;                              // (fails only for parents that are no plans, whose child is -1 anyway)
                 const int tn = okr ? qv * M + rank : 0;
                 const int mn = (reassign && tn == a) ? am : (((mb[tn >> 5] >> (tn & 31)) & 1u) ? (int)muA[tn] : (int)muB[tn]);
-                if (live) cell[(size_t)s * pitch + ct] = (uint32_t)tn | ((uint32_t)(uint16_t)mn << 16);
+                if (live) cell[(size_t)s * pitch + ct] = plan_cell(tn, mn);
             }
             kill = bad;
         }
         if (kill)
-            for (int s = lane; s < T; s += WAVE) cell[(size_t)s * pitch + ct] = 0xFFFFFFFFu;
+            for (int s = lane; s < T; s += WAVE) cell[(size_t)s * pitch + ct] = PLAN_CELL_KILLED;
         if (lane == 0 && gl < B) {
             if (A.kind_out) A.kind_out[g] = (int8_t)kind_o;
             if (A.parent_out) { A.parent_out[2 * (size_t)g] = pa; A.parent_out[2 * (size_t)g + 1] = pb; }
         }
     }
     __syncthreads();
-    // ---- the tile leaves row by row: lane = child, one contiguous run per row and array
-    const int total = T << A.tile_log2;
-    for (int e = tid; e < total; e += PLAN_THREADS) {
-        const int s = e >> A.tile_log2, ct = e & (A.tile - 1);
-        const long gl = g0 + ct;
-        const uint32_t word = cell[(size_t)s * pitch + ct];
-        if (gl < B) {
-            A.task_out[(size_t)s * B + gl] = (int)(int16_t)(word & 0xFFFFu);
-            A.mach_out[(size_t)s * B + gl] = (int)(int16_t)(word >> 16);
-        }
-    }
+    plan_tile_store(A, cell, T, pitch, B, g0, tid);
 }
 
 extern "C" int mtfjsp_plan_offspring(mtfjsp_handle_t h, int32_t P, const int32_t *src_task, const int32_t *src_mach, const double *src_obj,
@@ -268,38 +225,14 @@ extern "C" int mtfjsp_plan_offspring(mtfjsp_handle_t h, int32_t P, const int32_t
     if (P < 1 || v.B % P || moves == 0 || moves > 7 || cross_thr > (1ull << 32) || mut_thr > (1ull << 32))
         return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_plan_offspring: P >= 1 must divide the handle's batch, moves must be 1..7, the thresholds at most 2^32");
     const unsigned __int128 n_plan = (unsigned __int128)v.T * v.B * 4;
-    const void *srcs[4] = {src_task, src_mach, src_obj, src_best};
-    const unsigned __int128 n_srcs[4] = {n_plan, n_plan, (unsigned __int128)v.B * 8, (unsigned __int128)(v.B / P) * 4};
-    const void *outs[4] = {task_out, mach_out, parent_out, kind_out};
-    const unsigned __int128 n_outs[4] = {n_plan, n_plan, (unsigned __int128)v.B * 8, (unsigned __int128)v.B};
-    for (int o = 0; o < 4; o++) {
-        for (int s = 0; s < 4; s++)
-            if (plan_overlap(outs[o], n_outs[o], srcs[s], n_srcs[s]))
-                return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_plan_offspring: an output array overlaps a source array");
-        for (int p = 0; p < o; p++)
-            if (plan_overlap(outs[o], n_outs[o], outs[p], n_outs[p]))
-                return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_plan_offspring: the output arrays overlap");
-    }
-    int tile = 64;
-    while (tile > 16 && evo_lds_bytes(v.T, v.J, tile) > PLAN_LDS_SOFT) tile >>= 1;
-    const size_t lds = evo_lds_bytes(v.T, v.J, tile);
-    if (lds > PLAN_LDS_HARD) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_plan_offspring: n_job * n_machine is too large for a tile of 16 plans in LDS");
-    if (int rc = mtfjsp_env_set_device(h, v.device_id, who)) return rc;
+    const PlanSpan srcs[4] = {{src_task, n_plan}, {src_mach, n_plan}, {src_obj, (unsigned __int128)v.B * 8}, {src_best, (unsigned __int128)(v.B / P) * 4}};
+    const PlanSpan outs[4] = {{task_out, n_plan}, {mach_out, n_plan}, {parent_out, (unsigned __int128)v.B * 8}, {kind_out, (unsigned __int128)v.B}};
+    if (int rc = plan_check_overlap(h, who, 4, outs, 4, srcs)) return rc;
+    int tile; size_t lds;
+    if (int rc = plan_choose_tile(h, who, [&](int tl) { return evo_lds_bytes(v.T, v.J, tl); }, &tile, &lds)) return rc;
     EvoArgs A{};
-    A.B = v.B; A.P = P; A.T = v.T; A.J = v.J; A.M = v.M;
-    A.tile = tile; A.tile_log2 = tile == 64 ? 6 : (tile == 32 ? 5 : 4); A.pitch = tile + 1;
-    A.sw = (v.J + 31) / 32; A.mw = (v.T + 31) / 32;
-    A.inv_M = (unsigned)((0x100000000ull + (unsigned)v.M - 1) / (unsigned)v.M);
-    A.t = v.t; A.src_task = src_task; A.src_mach = src_mach; A.src_obj = src_obj; A.src_best = src_best;
-    A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32); A.gen_lo = (uint32_t)generation; A.first_lo = (uint32_t)first_instance;
-    A.moves = moves; A.n_moves = (uint32_t)__builtin_popcount(moves);
-    A.cross_thr = cross_thr; A.mut_thr = mut_thr;
-    A.task_out = task_out; A.mach_out = mach_out; A.parent_out = parent_out; A.kind_out = kind_out;
-    if (lds > 48 * 1024)
-        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)k_plan_offspring, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), who,
-                                          "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
-            return rc;
-    const dim3 grid((unsigned)(((size_t)v.B + tile - 1) / tile));
-    hipLaunchKernelGGL(k_plan_offspring, grid, dim3(PLAN_THREADS), lds, v.stream, A);
-    return mtfjsp_env_launched(h, who);
+    A.P = P; A.sw = (v.J + 31) / 32; A.mw = (v.T + 31) / 32;
+    A.src_task = src_task; A.src_mach = src_mach; A.src_obj = src_obj; A.src_best = src_best;
+    A.cross_thr = cross_thr; A.mut_thr = mut_thr; A.parent_out = parent_out;
+    return plan_launch_tiles(h, who, v, k_plan_offspring, A, tile, lds, seed, generation, first_instance, moves, task_out, mach_out, kind_out);
 }

@@ -12,16 +12,11 @@
 //                            ends last, then from every task its tight route predecessor, else its tight job predecessor.  One wave
 //                            per row, lanes over tasks; the walk is pointer doubling in LDS, not one lane chasing T pointers.
 // Integer arithmetic only (Philox words, (w * n) >> 32): the outputs must equal a host model element for element.
-// Shape: a workgroup of 4 waves builds a TILE of consecutive copies (64, 32 or 16 by T: the tile lives in LDS), every wave a quarter
-// of them one after the other, lanes over positions.  The tile's cells (task | machine << 16) have an odd row pitch: a wave writes
-// one copy's column (lane = position) and reads one row (lane = copy) without a bank conflict, and every output row leaves as one
-// contiguous run of TILE words — with lane = position the 4-byte stores of a copy would lie N*K*4 bytes apart.  The K copies of a
-// group read one source column: the caches serve it, and a wave reloads it only where the group changes.
+// Shape: the tile of mtfjsp_plan_dev.h, which also holds the move itself (draw, position map, REASSIGN's pick, operation ranks), the cell,
+// the tile's way out and the host side of the launch; here are the incumbent's (and the path's) load and what a critical path directs.
+// The K copies of a group read one source column: the caches serve it, and a wave reloads it only where the group changes.
 #include <hip/hip_runtime.h>
-#include <limits.h>
 #include <stdint.h>
-
-#include <string>
 
 #include "../../include/mtfjsp.h"
 
@@ -41,7 +36,7 @@ struct PlanArgs {
     const int *src_task, *src_mach;    // [T,src_stride]
     long long src_stride;
     const int *src_col;                // [B/K] or null
-    uint32_t seed_lo, seed_hi, round_lo, first_lo, moves, n_moves;
+    uint32_t seed_lo, seed_hi, ctr_lo, first_lo, moves, n_moves;   // ctr_lo: the round
     int *task_out, *mach_out;          // [T,B]
     int8_t *kind_out;                  // [B] or null
     const int *path_task, *path_len;   // [B/K,T], [B/K]: read by the CRIT instantiations only
@@ -131,46 +126,34 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_neighbours(PlanArgs A)
             }
             plan_wave_sync();
         }
-        // ---- the draw (wave-uniform).  Copy 0 takes none.
-        uint32_t w[4] = {A.first_lo + (uint32_t)n, (uint32_t)c, A.round_lo, PLAN_TAG_MOVE};
-        philox4x32(w, A.seed_lo, A.seed_hi);
-        uint32_t mv = A.moves;
-        for (int k = (int)plan_mulhi(w[0], A.n_moves); k > 0; k--) mv &= mv - 1;
-        const int kind = (int)(mv & (0u - mv));
-        int x = uni((int)plan_mulhi(w[1], (uint32_t)T));
-        int y = T >= 2 ? (int)plan_mulhi(w[2], (uint32_t)(T - 1)) : 0;
-        y += (T >= 2 && y >= x) ? 1 : 0;
-        int move = (c == 0 || (T < 2 && kind != PLAN_REASSIGN)) ? 0 : kind;   // 0: identity
-        // ---- REASSIGN's candidates: the feasible machines of task a other than its own, ascending = lane order (M <= 64)
-        int a = SMALL ? rl_i(tk_r, x) : (int)inc[x];
+        // ---- the draw (plan_draw: wave-uniform).  Copy 0 takes none.
+        const PlanMove d = plan_draw(A.first_lo + (uint32_t)n, (uint32_t)c, A.ctr_lo, A.seed_lo, A.seed_hi, A.moves, A.n_moves, T);
+        int x = d.x, y = d.y, move = c == 0 ? 0 : d.move;              // 0: identity
+        int a = SMALL ? rl_i(tk_r, x) : (int)inc[x];                   // REASSIGN's task
         if (CRIT) {
-            if (kind == PLAN_CRIT_SWAP) {                               // INSERT of the arc's later task before its earlier one: v = path[k], u = path[k + 1]
+            if (d.kind == PLAN_CRIT_SWAP) {                               // INSERT of the arc's later task before its earlier one: v = path[k], u = path[k + 1]
                 move = 0;
                 if (nA > 0) {
-                    const int k = (int)elig[plan_mulhi(w[1], (uint32_t)nA)];
+                    const int k = (int)elig[plan_mulhi(d.wx, (uint32_t)nA)];
                     x = uni((int)pos[ptk[k]]);
                     y = uni((int)pos[ptk[k + 1]]);
                     move = c == 0 ? 0 : PLAN_INSERT;
                 }
             }
-            if (kind == PLAN_CRIT_REASSIGN) {                           // REASSIGN of a task of the path
+            if (d.kind == PLAN_CRIT_REASSIGN) {                           // REASSIGN of a task of the path
                 move = 0;
                 if (L > 0) {
-                    a = uni((int)ptk[plan_mulhi(w[1], (uint32_t)L)]);
+                    a = uni((int)ptk[plan_mulhi(d.wx, (uint32_t)L)]);
                     move = c == 0 ? 0 : PLAN_REASSIGN;
                 }
             }
         }
         const int old_m = mu[a];
-        const double tv = A.t[((size_t)g * T + a) * M + (lane < M ? lane : M - 1)];
-        const bool feas = lane < M && tv >= 0 && lane != old_m;
-        const unsigned long long fb = __ballot(feas);
-        const int nf = __popcll(fb);
-        const int pick = (int)plan_mulhi(w[2], (uint32_t)nf);
-        const unsigned long long sel = __ballot(feas && plan_below(fb) == pick);
+        int new_m;
+        const int nf = plan_other_machine(A.t, ((size_t)g * T + a) * M, M, old_m, d.wy, lane, &new_m);
         const bool reassign = move == PLAN_REASSIGN && nf > 0;
         if (reassign) {
-            if (lane == 0) mu[a] = (int16_t)__builtin_ctzll(sel);
+            if (lane == 0) mu[a] = (int16_t)new_m;
             plan_wave_sync();
         }
         if (!SMALL) {
@@ -179,36 +162,17 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_neighbours(PlanArgs A)
         }
         // ---- q' = q gathered through the move's position map, the operation ranks, the machines
         for (int s0 = 0; s0 < T; s0 += WAVE) {
-            const int s = s0 + lane;
-            int src = s;
-            if (move == PLAN_SWAP) src = s == x ? y : (s == y ? x : s);
-            if (move == PLAN_INSERT) {                                  // q.pop(x), q.insert(y, it)
-                if (s == y) src = x;
-                else if (x < y && s >= x && s < y) src = s + 1;
-                else if (y < x && s > y && s <= x) src = s - 1;
-            }
-            src = src < T ? src : T - 1;
+            const int s = s0 + lane, src = plan_src(move, s, x, y, T);
             int qn;
             if (SMALL) qn = __builtin_amdgcn_ds_bpermute(src << 2, q_r);
             else qn = (int)plan_mulhi((uint32_t)inc[src], A.inv_M);
             const bool live = s < T;
-            int rank = 0;
-            bool last = false;                                          // the pass's last position of its job
-            for (int j = 0; j < J; j++) {                               // one wave-uniform ballot per job
-                const unsigned long long b = __ballot(live && qn == j);
-                if (qn == j) { rank = plan_below(b); last = (b >> lane) == 1ull; }
-            }
-            if (!SMALL) {
-                rank += cnt[qn];
-                plan_wave_sync();
-                if (live && last) cnt[qn] = rank + 1;
-                plan_wave_sync();
-            }
+            const int rank = plan_rank<!SMALL>(qn, live, J, lane, cnt);
             const bool okr = c == 0 || rank < M;                        // (fails only for an incumbent that is no plan: too many operations of one job)
             int tn = okr ? qn * M + rank : 0;
             if (c == 0) tn = SMALL ? tk_r : (int)inc[live ? s : T - 1];  // copy 0 is the incumbent word for word, not its decoding
             const int mn = mu[tn];
-            const uint32_t word = (bad || !okr) ? 0xFFFFFFFFu : ((uint32_t)tn | ((uint32_t)(uint16_t)mn << 16));
+            const uint32_t word = (bad || !okr) ? PLAN_CELL_KILLED : plan_cell(tn, mn);
             if (live) cell[(size_t)s * pitch + ct] = word;
         }
         if (reassign) {
@@ -216,20 +180,10 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan_neighbours(PlanArgs A)
             if (lane == 0) mu[a] = (int16_t)old_m;
             plan_wave_sync();
         }
-        if (A.kind_out && lane == 0 && gl < B) A.kind_out[g] = (int8_t)(c == 0 ? -1 : kind);
+        if (A.kind_out && lane == 0 && gl < B) A.kind_out[g] = (int8_t)(c == 0 ? -1 : d.kind);
     }
     __syncthreads();
-    // ---- the tile leaves row by row: lane = copy, one contiguous run per row and array
-    const int total = T << A.tile_log2;
-    for (int e = tid; e < total; e += PLAN_THREADS) {
-        const int s = e >> A.tile_log2, ct = e & (A.tile - 1);
-        const long gl = g0 + ct;
-        const uint32_t word = cell[(size_t)s * pitch + ct];
-        if (gl < B) {
-            A.task_out[(size_t)s * B + gl] = (int)(int16_t)(word & 0xFFFFu);
-            A.mach_out[(size_t)s * B + gl] = (int)(int16_t)(word >> 16);
-        }
-    }
+    plan_tile_store(A, cell, T, pitch, B, g0, tid);
 }
 
 // both entry points: max_moves = 7 for the plain one, whose launches are the CRIT = false instantiations whatever else is passed
@@ -249,42 +203,18 @@ static int plan_launch(const char *who, mtfjsp_handle_t h, int32_t K, const int3
     if (crit && (!path_task || !path_arc || !path_len)) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, (pre + "a critical-path move needs path_task, path_arc and path_len").c_str());
     const unsigned __int128 n_src = (unsigned __int128)v.T * (unsigned __int128)src_stride * 4, n_out = (unsigned __int128)v.T * v.B * 4;
     const unsigned __int128 N = (unsigned __int128)(v.B / K);
-    const void *srcs[6] = {src_task, src_mach, src_col, path_task, path_arc, path_len};
-    const unsigned __int128 n_srcs[6] = {n_src, n_src, N * 4, N * v.T * 4, N * v.T, N * 4};
-    const void *outs[3] = {task_out, mach_out, kind_out};
-    const unsigned __int128 n_outs[3] = {n_out, n_out, (unsigned __int128)v.B};
-    for (int o = 0; o < 3; o++) {
-        for (int s = 0; s < 6; s++)
-            if (plan_overlap(outs[o], n_outs[o], srcs[s], n_srcs[s]))
-                return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, (pre + "an output array overlaps a source array").c_str());
-        for (int p = 0; p < o; p++)
-            if (plan_overlap(outs[o], n_outs[o], outs[p], n_outs[p]))
-                return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, (pre + "the output arrays overlap").c_str());
-    }
-    int tile = 64;
-    while (tile > 16 && plan_lds_bytes(v.T, v.J, tile, crit) > PLAN_LDS_SOFT) tile >>= 1;
-    const size_t lds = plan_lds_bytes(v.T, v.J, tile, crit);
-    if (lds > PLAN_LDS_HARD) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, (pre + "n_job * n_machine is too large for a tile of 16 plans in LDS").c_str());
-    if (int rc = mtfjsp_env_set_device(h, v.device_id, who)) return rc;
+    const PlanSpan srcs[6] = {{src_task, n_src}, {src_mach, n_src}, {src_col, N * 4}, {path_task, N * v.T * 4}, {path_arc, N * v.T}, {path_len, N * 4}};
+    const PlanSpan outs[3] = {{task_out, n_out}, {mach_out, n_out}, {kind_out, (unsigned __int128)v.B}};
+    if (int rc = plan_check_overlap(h, who, 3, outs, 6, srcs)) return rc;
+    int tile; size_t lds;
+    if (int rc = plan_choose_tile(h, who, [&](int tl) { return plan_lds_bytes(v.T, v.J, tl, crit); }, &tile, &lds)) return rc;
     PlanArgs A{};
-    A.B = v.B; A.K = K; A.T = v.T; A.J = v.J; A.M = v.M;
-    A.tile = tile; A.tile_log2 = tile == 64 ? 6 : (tile == 32 ? 5 : 4); A.pitch = tile + 1;
-    A.inv_M = (unsigned)((0x100000000ull + (unsigned)v.M - 1) / (unsigned)v.M);
-    A.t = v.t; A.src_task = src_task; A.src_mach = src_mach; A.src_stride = src_stride; A.src_col = src_col;
-    A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32); A.round_lo = (uint32_t)round; A.first_lo = (uint32_t)first_instance;
-    A.moves = moves; A.n_moves = (uint32_t)__builtin_popcount(moves);
-    A.task_out = task_out; A.mach_out = mach_out; A.kind_out = kind_out;
+    A.K = K; A.src_task = src_task; A.src_mach = src_mach; A.src_stride = src_stride; A.src_col = src_col;
     A.path_task = path_task; A.path_arc = path_arc; A.path_len = path_len;
     const bool small = v.T <= WAVE;
     void (*fn)(PlanArgs) = crit ? (small ? k_plan_neighbours<true, true> : k_plan_neighbours<false, true>)
                                 : (small ? k_plan_neighbours<true, false> : k_plan_neighbours<false, false>);
-    if (lds > 48 * 1024)
-        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), who,
-                                          "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
-            return rc;
-    const dim3 grid((unsigned)(((size_t)v.B + tile - 1) / tile));
-    hipLaunchKernelGGL(fn, grid, dim3(PLAN_THREADS), lds, v.stream, A);
-    return mtfjsp_env_launched(h, who);
+    return plan_launch_tiles(h, who, v, fn, A, tile, lds, seed, round, first_instance, moves, task_out, mach_out, kind_out);
 }
 
 extern "C" int mtfjsp_plan_neighbours(mtfjsp_handle_t h, int32_t K, const int32_t *src_task, const int32_t *src_mach, int64_t src_stride,

@@ -115,93 +115,172 @@ def validate_cost_batched(weights, t, p, tt, edge, args, greedy=True, device=0, 
 
 
 
+class CopyGroups:
+    """What every search over groups of copies is built on (`best_of_k_rollout`, `baselines.local_search`, `baselines.evolve`): N
+    instances, n = chunk or N of them per pass, K copies of each side by side.  Three handles: `src` with the N loaded instances, `env`
+    with the n*K copies (copy c of group i = element i*K + c; None with copies=False) and `top` with n, for the best copy of every
+    group; per pass both take their constants from `src` by the explicit-index fork.  The constructor validates `chunk` and builds the
+    handles and index tensors (`copy_of`, `own`: every group's copy 0, `inst_of`, `w3_all`, `w3_top`: args' weights per element, or
+    w3 [K,3]: copy c of every group resets with w3[c]); leaving the `with` block closes the handles.  `passes()` iterates; `host`,
+    `parts` and `collect()` gather the per-pass results.  `sizes(t, args)` gives N and T before anything is built.
+    For searches on plans (plans=True; [T, n*K] int32 histories, row s = the actions of step s): `plan_bufs(i)` are two pairs of them
+    that take turns, `round()` replays one on the copies and reduces the groups, `finish()` replays every group's best plan on `top`."""
+
+    @staticmethod
+    def sizes(t, args):
+        return np.shape(t)[0], parse_args(args)[3]
+
+    def __init__(self, t, p, tt, edge, args, K, chunk=None, copies=True, plans=False, w3=None, **env_kw):
+        J, M, E, self.T, self.w, kw = parse_args(args, **env_kw)
+        t = np.asarray(t, np.float64)
+        self.N, self.K = t.shape[0], int(K)
+        n = self.N if chunk is None else int(chunk)
+        if n < 1:
+            raise ValueError("chunk must be at least 1")
+        self.n = n = min(n, self.N)
+        self.src = self.env = self.top = None
+        self.parts = []
+        try:
+            self.src = DeviceBatchEnv(J, M, E, self.N, **kw)
+            self.src.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
+            self.dev = dev = self.src.device
+            self.top = DeviceBatchEnv(J, M, E, n, **kw)
+            B = n * self.K
+            if copies:                                                  # (every handle before the first tensor)
+                self.env = DeviceBatchEnv(J, M, E, B, **kw)
+            self.w3_top = torch.tensor([self.w], dtype=torch.float64, device=dev).repeat(n, 1)
+            self.inst_of = torch.arange(n, dtype=torch.int32, device=dev)
+            if copies:
+                w3_k = torch.as_tensor(np.ascontiguousarray([self.w] if w3 is None else w3, np.float64), device=dev)
+                if w3 is not None and tuple(w3_k.shape) != (self.K, 3):
+                    raise ValueError("w3 must be [K,3]")
+                self.w3_all = w3_k.repeat(B // w3_k.shape[0], 1).contiguous()
+                self.copy_of = torch.arange(B, dtype=torch.int32, device=dev) // self.K
+                self.own = self.inst_of * self.K
+                if plans:
+                    self.bufs = [tuple(torch.empty(self.T, B, dtype=torch.int32, device=dev) for _ in range(2)) for _ in range(2)]
+                    self.cost4, self.done = torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+        except BaseException:
+            self.close()
+            raise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        for e in (self.top, self.env, self.src):
+            if e is not None:
+                e.close()
+        self.src = self.env = self.top = None
+
+    def passes(self):
+        """-> (lo, m) per pass: the pass holds instances lo .. lo + m - 1 (a last, smaller pass is padded with copies of its last
+        instance); both handles have their instances (`top` first), the copies' scaler is initialised"""
+        for lo in range(0, self.N, self.n):
+            self.lo, self.m = lo, min(self.n, self.N - lo)
+            self.top.fork_from(self.src, torch.clamp(self.inst_of + lo, max=self.N - 1), instance=True, state=False, obs=False)
+            if self.env is not None:
+                self.env.fork_from(self.src, torch.clamp(self.copy_of + lo, max=self.N - 1), instance=True, state=False, obs=False)
+                self.env.scaler_init()                                  # the scaled components are produced but not used here
+            yield lo, self.m
+
+    def pad(self, x):                                                   # host array [N, ...] -> the rows of this pass's n instances
+        return x[np.minimum(np.arange(self.n) + self.lo, self.N - 1)]
+
+    def host(self, x):                                                  # device tensor [..., n] -> host array [..., m]
+        return x[..., :self.m].cpu().numpy()
+
+    def collect(self, last_axis=()):
+        """the per-pass dicts of `parts` -> one dict, concatenated along the instances' axis: the first, or the last for keys in `last_axis`"""
+        return {k: np.concatenate([x[k] for x in self.parts], axis=-1 if k in last_axis else 0) for k in self.parts[0]}
+
+    # ---- searches on plans
+    def plan_bufs(self, i):
+        return self.bufs[i & 1]
+
+    def round(self, task, mach, obj, best, best_obj):
+        """the copies replay the plans (task, mach) and every group is reduced into the tensors given (obj may be False): reset, T steps,
+        final_costs, group_reduce — T + 3 launches, no torch kernel, nothing read back"""
+        env = self.env
+        env.reset(self.w3_all)
+        for s in range(self.T):
+            env.step(task[s], mach[s])
+        env.final_costs(self.cost4, self.done)                          # a rejected action leaves done = 0: the copy is not eligible
+        env.group_reduce(self.n, self.K, self.cost4, self.done, self.w, obj=obj, best=best, best_obj=best_obj, front=False)
+
+    def finish(self, task, mach, col, what, **extra):
+        """the pass's result: column col[i] of (task, mach) for group i — its copy 0 where col[i] < 0, a group without an eligible copy,
+        which the replay rejects; col None: column i — replayed on `top` step by step (`replay_episode`: RuntimeError for a plan that
+        is none) -> appends dict(cum, prev, task [m,T], mach [m,T], **extra) to `parts`, the device tensors of `extra` through `host`"""
+        if col is not None:
+            pick = torch.where(col < 0, self.own, col).long()
+            task, mach = task.index_select(1, pick).contiguous(), mach.index_select(1, pick).contiguous()
+        self.top.scaler_init()
+        self.top.reset(self.w3_top)                                     # pdrs:675 reset(Random_weight_type="eval")
+        cum, prev = replay_episode(self.top, self.T, lambda s: (task[s], mach[s]), what)
+        self.parts.append(dict(cum=cum[:self.m], prev=prev[:self.m], task=self.host(task).T.copy(), mach=self.host(mach).T.copy(),
+                               **{k: self.host(x) for k, x in extra.items()}))
+
+
 def best_of_k_rollout(t, p, tt, edge, args, K, policy, w3=None, chunk=None, device=0, obs_dtype="f32", left_shift=True, what="best-of-K",
                       on_event=None):
     """The K-copy rollout behind `sample_best_of_k` and `baselines.random_baselines`: N instances, K copies of each side by side in
-    one handle of n*K (n = chunk or N instances per pass; copy c of instance i = element i*K + c), every copy playing its own
+    one handle of n*K (`CopyGroups`: n = chunk or N instances per pass; copy c of instance i = element i*K + c), every copy playing its own
     episode with the actions `policy.decide(env, s, task_row, mach_row, job)` writes into row s of the [T, n*K] histories; then the final
     costs, the best copy and the Pareto front per instance on the device (csrc/mtfjsp_group.hip) and a fork of the best copies into an
     n-instance handle, from which their schedules are read.  policy: `open(batch)` once before the first pass, `begin()` at every
     pass's reset, `decide(...)` per step, `close()` at the end.  on_event(event, env, first_instance, hist_task, hist_mach) (tests): called
     with "reset" after every pass's reset and with "end" after its last step, the handle of copies and the [T, n*K] device histories.
     -> the dict `sample_best_of_k` documents, plus `cum` [N,K,5]: every copy's summed raw rewards."""
-    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
     K = int(K)
     if not 1 <= K <= 4096:
         raise ValueError("K must be 1..4096")
-    t = np.asarray(t, np.float64)
-    N = t.shape[0]
-    n = N if chunk is None else int(chunk)
-    if n < 1:
-        raise ValueError("chunk must be at least 1")
-    n = min(n, N)
-    src = DeviceBatchEnv(J, M, E, N, **kw)
-    env = top = None
-    opened = False
-    parts = []
-    try:
-        src.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=np.asarray(edge))
-        dev = src.device
-        env = DeviceBatchEnv(J, M, E, n * K, **kw)                     # the copies
-        top = DeviceBatchEnv(J, M, E, n, **kw)                         # the best copy of every instance
+    with CopyGroups(t, p, tt, edge, args, K, chunk, w3=w3, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
+        n, T, w, dev, env, top = g.n, g.T, g.w, g.dev, g.env, g.top
         policy.open(n * K)
-        opened = True
-        if w3 is None:
-            w3_all = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n * K, 1)
-        else:
-            w3_k = torch.as_tensor(np.ascontiguousarray(w3, np.float64), device=dev)
-            if tuple(w3_k.shape) != (K, 3):
-                raise ValueError("w3 must be [K,3]")
-            w3_all = w3_k.repeat(n, 1).contiguous()                     # copy c of every instance resets with w3[c]
-        copy_of = torch.arange(n * K, dtype=torch.int32, device=dev) // K
-        inst_of = torch.arange(n, dtype=torch.int32, device=dev)
-        hist_task = torch.empty(T, n * K, dtype=torch.int32, device=dev)
-        hist_mach = torch.empty(T, n * K, dtype=torch.int32, device=dev)
-        job = torch.zeros(n * K, dtype=torch.int32, device=dev)
-        cum = torch.empty(n * K, 5, dtype=torch.float64, device=dev)
-        bad = torch.empty(n * K, dtype=torch.int32, device=dev)
-        for lo in range(0, N, n):
-            m = min(n, N - lo)                                          # a last, smaller chunk is padded with copies of its last instance
-            env.fork_from(src, torch.clamp(copy_of + lo, max=N - 1), instance=True, state=False, obs=False)
-            top.fork_from(src, torch.clamp(inst_of + lo, max=N - 1), instance=True, state=False, obs=False)
-            env.scaler_init()                                           # the scaled components are produced but not used here
-            env.reset(w3_all)
-            policy.begin()
-            if on_event is not None:
-                on_event("reset", env, lo, hist_task, hist_mach)
-            cum.zero_(); bad.zero_()
-            for s in range(T):
-                policy.decide(env, s, hist_task[s], hist_mach[s], job)
-                env.step(hist_task[s], hist_mach[s])
-                bad |= env.status
-                cum += env.raw                                          # reward, r_mk, r_idle, r_pt, r_tt (env:1051-1171), unscaled
-            if on_event is not None:
-                on_event("end", env, lo, hist_task, hist_mach)
-            cost4, done = env.final_costs()
-            obj, best, best_obj, front = env.group_reduce(n, K, cost4, done, w)
-            top.fork_from(env, best, instance=False, state=True, obs=False)
-            pick = best.clamp(min=0).long()
-            best_cum, best_c4 = cum.index_select(0, pick), cost4.index_select(0, pick)
-            plan_t, plan_m = hist_task.index_select(1, pick).t().contiguous(), hist_mach.index_select(1, pick).t().contiguous()
-            torch.cuda.synchronize(dev)
-            if int((bad[:m * K] & capi.ST_INVALID).ne(0).sum().item()) != 0:
-                raise RuntimeError(f"{what} evaluation produced an invalid action")
-            if not bool(done[:m * K].all().item()) or int(best[:m].min().item()) < 0:
-                raise RuntimeError(f"{what} evaluation: an episode did not finish")
-            host = lambda x, k=m: x[:k].cpu().numpy()                   # noqa: E731
-            parts.append(dict(
-                best_copy=host(best).astype(np.int64) + lo * K, best_obj=host(best_obj), best_cum=host(best_cum), best_c4=host(best_c4),
-                obj=host(obj, m * K).reshape(m, K), final4=host(cost4, m * K).reshape(m, K, 4), front=host(front, m * K).reshape(m, K).astype(bool),
-                cum=host(cum, m * K).reshape(m, K, 5), plan_t=host(plan_t), plan_m=host(plan_m),
-                machine=top.read_state(capi.STATE_MACHINE)[:m], start=top.read_state(capi.STATE_START)[:m],
-                finish=top.read_state(capi.STATE_FINISH)[:m]))
-    finally:
-        if opened:
+        try:
+            hist_task = torch.empty(T, n * K, dtype=torch.int32, device=dev)
+            hist_mach = torch.empty(T, n * K, dtype=torch.int32, device=dev)
+            job = torch.zeros(n * K, dtype=torch.int32, device=dev)
+            cum = torch.empty(n * K, 5, dtype=torch.float64, device=dev)
+            bad = torch.empty(n * K, dtype=torch.int32, device=dev)
+            for lo, m in g.passes():
+                env.reset(g.w3_all)
+                policy.begin()
+                if on_event is not None:
+                    on_event("reset", env, lo, hist_task, hist_mach)
+                cum.zero_(); bad.zero_()
+                for s in range(T):
+                    policy.decide(env, s, hist_task[s], hist_mach[s], job)
+                    env.step(hist_task[s], hist_mach[s])
+                    bad |= env.status
+                    cum += env.raw                                      # reward, r_mk, r_idle, r_pt, r_tt (env:1051-1171), unscaled
+                if on_event is not None:
+                    on_event("end", env, lo, hist_task, hist_mach)
+                cost4, done = env.final_costs()
+                obj, best, best_obj, front = env.group_reduce(n, K, cost4, done, w)
+                top.fork_from(env, best, instance=False, state=True, obs=False)
+                pick = best.clamp(min=0).long()
+                best_cum, best_c4 = cum.index_select(0, pick), cost4.index_select(0, pick)
+                plan_t, plan_m = hist_task.index_select(1, pick).t().contiguous(), hist_mach.index_select(1, pick).t().contiguous()
+                torch.cuda.synchronize(dev)
+                if int((bad[:m * K] & capi.ST_INVALID).ne(0).sum().item()) != 0:
+                    raise RuntimeError(f"{what} evaluation produced an invalid action")
+                if not bool(done[:m * K].all().item()) or int(best[:m].min().item()) < 0:
+                    raise RuntimeError(f"{what} evaluation: an episode did not finish")
+                host = lambda x, k=m: x[:k].cpu().numpy()               # noqa: E731
+                g.parts.append(dict(
+                    best_copy=host(best).astype(np.int64) + lo * K, best_obj=host(best_obj), best_cum=host(best_cum), best_c4=host(best_c4),
+                    obj=host(obj, m * K).reshape(m, K), final4=host(cost4, m * K).reshape(m, K, 4), front=host(front, m * K).reshape(m, K).astype(bool),
+                    cum=host(cum, m * K).reshape(m, K, 5), plan_t=host(plan_t), plan_m=host(plan_m),
+                    machine=top.read_state(capi.STATE_MACHINE)[:m], start=top.read_state(capi.STATE_START)[:m],
+                    finish=top.read_state(capi.STATE_FINISH)[:m]))
+        finally:
             policy.close()
-        for e in (top, env, src):
-            if e is not None:
-                e.close()
-    r = {k: np.concatenate([x[k] for x in parts]) for k in parts[0]}
+    r = g.collect()
     cost = {key: r["best_cum"][:, i] for i, key in enumerate(COST_KEYS)}
     return {"best": (cost, r["best_c4"], r["best_obj"]), "best_copy": r["best_copy"], "obj": r["obj"], "final4": r["final4"],
             "front": r["front"], "cum": r["cum"], "plans": (r["plan_t"], r["plan_m"]),

@@ -1,7 +1,7 @@
 """GPU: mtfjsp_plan_offspring (csrc/mtfjsp_evolve.hip) EQUALS its host model (tests/plan_crossover_ref.py, pinned by
 tests/test_plan_crossover_cpu.py) element for element — task_out, mach_out, parent_out and kind_out: T = 12 and 36 (one pass), 64 (a
 full pass), 65 (two passes) and 260 = J130 x M2 (M = 2 is the smallest the handle accepts: a second and third word block of the "jset"
-and "mach" streams, the tile of 32); P = 1, 3, 64, 100 with N*P no multiple of the tile wherever P allows it (P = 64 never does), so
+and "mach" streams, the tile of 32) and 400 = J20 x M20 (the tile of 16, once: P = 5, N = 7); P = 1, 3, 64, 100 with N*P no multiple of the tile wherever P allows it (P = 64 never does), so
 that groups straddle workgroups and the last tile is partial; objectives with NaNs and ties, a whole group NaN with best = -1, best
 outside its group, best NULL; every single move mask and all three; thresholds 0, 2^32 and between; parents that are no plans; nothing
 written outside the outputs or on an error return."""
@@ -108,8 +108,11 @@ def _check(S, tag, *a, **kw):
     return got, exp
 
 
-@pytest.mark.parametrize("P,N", GROUPS, ids=[f"P{p}-N{n}" for p, n in GROUPS])
-@pytest.mark.parametrize("shape", SHAPES, ids=[f"J{s[0]}M{s[1]}" for s in SHAPES])
+# every shape with every group, and T = 400: three tiles of 16 children, the last one partial, groups straddling tiles
+CASES = [(s, p, n) for s in SHAPES for p, n in GROUPS] + [((20, 20, 2), 5, 7)]
+
+
+@pytest.mark.parametrize("shape,P,N", CASES, ids=[f"J{s[0]}M{s[1]}-P{p}-N{n}" for s, p, n in CASES])
 def test_offspring_equal_the_model(shape, P, N):
     S = _setup(shape, P, N)
     tag = f"J{shape[0]}M{shape[1]} P={P} N={N}"
