@@ -24,9 +24,12 @@ def shop_of_machine(edge):
 
 def step_kernel_for(n_job, n_machine, batch, obs_f32=False, lds_max=160 * 1024):
     """(name, instances per workgroup, bytes of one instance's LDS region, any diagnostic switch set) of the step kernel a handle of
-    this shape launches where a workgroup may use `lds_max` bytes of LDS (gfx950: 160 KiB): the library's own selection, no GPU needed"""
+    this shape launches where a workgroup may use `lds_max` bytes of LDS (gfx950: 160 KiB): the library's own selection, no GPU needed.
+    ValueError for a shape mtfjsp_create refuses, one whose single instance needs more than `lds_max` bytes included"""
     g, nb, ov = C.c_int32(), C.c_int64(), C.c_int32()
     name = capi.lib().mtfjsp_step_kernel_name_for(n_job, n_machine, batch, int(bool(obs_f32)), lds_max, C.byref(g), C.byref(nb), C.byref(ov))
+    if name is None:
+        raise ValueError(f"no handle takes J{n_job}M{n_machine} B={batch} with {lds_max} bytes of LDS per workgroup")
     return name.decode(), g.value, nb.value, bool(ov.value)
 
 
@@ -342,6 +345,12 @@ class DeviceBatchEnv:
     def step_kernel_name(self):
         """the step kernel the next step() launches (shape, this device's LDS, the diagnostic switches as they are now)"""
         return self.L.mtfjsp_step_kernel_name(self.h).decode()
+
+    def step_launch_info(self):
+        """(instances per workgroup, dynamic LDS bytes, LDS bytes a workgroup may use on this device) of the launch step_kernel_name names"""
+        g, nb, mx = C.c_int32(), C.c_int64(), C.c_int64()
+        capi.check(self.L.mtfjsp_step_launch_info(self.h, C.byref(g), C.byref(nb), C.byref(mx)), self.h)
+        return g.value, nb.value, mx.value
 
     def step_params(self, task_idx, mach_idx, r4_out=None, done_out=None):
         """the parameter block of exactly the step that step() / step_record() with these arguments would launch, for

@@ -69,6 +69,7 @@ PROTOTYPES = {
     "mtfjsp_step_params_bytes": (C.c_int32, []),
     "mtfjsp_step_params": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int32]),
     "mtfjsp_step_kernel_name": (C.c_char_p, [_VP]),
+    "mtfjsp_step_launch_info": (_I, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mtfjsp_step_kernel_name_for": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "mtfjsp_gae": (_I, [_VP, C.c_int32, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, C.c_int64, _VP, C.c_float, C.c_float, _VP]),
     "mtfjsp_normalize_advantages": (_I, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_float, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -1667,6 +1667,14 @@ static int dalloc(mtfjsp_env *h, Tp **ptr, size_t n)
 
 extern "C" const char *mtfjsp_last_error(mtfjsp_handle_t h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
+// LDS one instance needs at least: k_env_step's region (one instance per workgroup: the kernel every shape can fall back to) or
+// k_env_reset's.  mtfjsp_create refuses a shape that needs more than the device gives a workgroup; mtfjsp_step_kernel_name_for says the same
+static size_t env_create_lds_bytes(int J, int M, bool f32)
+{
+    const size_t step = env_step_lds_bytes(J, M, J * M, f32), reset = env_reset_lds_bytes(J * M, false);
+    return reset > step ? reset : step;
+}
+
 extern "C" int mtfjsp_create(const mtfjsp_config_t *cfg, mtfjsp_handle_t *out)
 {
     if (!cfg || !out) { g_create_err = "null argument"; return MTFJSP_ERR_ARG; }
@@ -1684,8 +1692,7 @@ extern "C" int mtfjsp_create(const mtfjsp_config_t *cfg, mtfjsp_handle_t *out)
     h->cfg = *cfg;
     h->T = cfg->n_job * cfg->n_machine;
     const size_t B = cfg->batch, T = h->T, M = cfg->n_machine;
-    size_t lds = env_step_lds_bytes(cfg->n_job, cfg->n_machine, h->T, cfg->obs_dtype == MTFJSP_OBS_F32);
-    if (env_reset_lds_bytes(h->T, false) > lds) lds = env_reset_lds_bytes(h->T, false);
+    const size_t lds = env_create_lds_bytes(cfg->n_job, cfg->n_machine, cfg->obs_dtype == MTFJSP_OBS_F32);
     {   // LDS a workgroup may use on THIS device (gfx950: 160 KiB; asked, not assumed)
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device_id) == hipSuccess && v > 0) h->lds_max = (size_t)v;
@@ -1710,11 +1717,14 @@ extern "C" int mtfjsp_create(const mtfjsp_config_t *cfg, mtfjsp_handle_t *out)
             g_create_err = "pairwise table upload failed"; mtfjsp_destroy(h); return MTFJSP_ERR_HIP;
         }
     }
-    // opt in to large dynamic LDS (every kernel that is launched with a dynamic allocation sized from T)
+    // opt in to large dynamic LDS (every kernel that is launched with a dynamic allocation sized from T).  The attribute belongs to the
+    // kernel, not to the handle: it is set to the device's limit, so that a small handle created later cannot lower it under a large
+    // one that is still alive (this handle's own size only where the device refuses its limit)
     const void *dyn_kernels[] = {(const void *)k_env_step<double>, (const void *)k_env_step<float>,
                                  (const void *)k_env_reset<double>, (const void *)k_env_reset<float>};
     for (const void *k : dyn_kernels)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_max) != hipSuccess &&
+            hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             g_create_err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
             mtfjsp_destroy(h);
             return MTFJSP_ERR_HIP;
@@ -1977,6 +1987,7 @@ extern "C" const char *mtfjsp_step_kernel_name_for(int32_t n_job, int32_t n_mach
                                                    int64_t *lds_bytes_out, int32_t *overridden_out)
 {
     if (n_job < 1 || n_machine < 2 || n_machine > 64 || batch < 1 || (long)n_job * n_machine > 32767 || lds_max < 0) return nullptr;
+    if (env_create_lds_bytes(n_job, n_machine, obs_f32 != 0) > (size_t)lds_max) return nullptr;     // "instance too large for one CU's LDS"
     mtfjsp_env e;                                                          // no device is touched: only the fields the rule reads
     e.cfg.n_job = n_job; e.cfg.n_machine = n_machine; e.cfg.batch = batch; e.cfg.obs_dtype = obs_f32 ? MTFJSP_OBS_F32 : MTFJSP_OBS_F64;
     e.lds_max = (size_t)lds_max; e.pw_nleaf = pw_nleaf(n_job * n_machine);
@@ -1985,6 +1996,16 @@ extern "C" const char *mtfjsp_step_kernel_name_for(int32_t n_job, int32_t n_mach
     if (lds_bytes_out) *lds_bytes_out = (int64_t)pl.lds_inst;
     if (overridden_out) *overridden_out = pl.overridden;
     return ENV_KERNEL_NAME[pl.kernel];
+}
+
+extern "C" int mtfjsp_step_launch_info(mtfjsp_handle_t h, int32_t *group_out, int64_t *lds_launch_out, int64_t *lds_max_out)
+{
+    if (!h) return MTFJSP_ERR_ARG;
+    const EnvStepPlan pl = step_plan(h, true);
+    if (group_out) *group_out = pl.G;
+    if (lds_launch_out) *lds_launch_out = (int64_t)pl.lds;
+    if (lds_max_out) *lds_max_out = (int64_t)h->lds_max;
+    return MTFJSP_OK;
 }
 
 // The parameter block of the step kernel for a launch that runs the step as its own tail (mtfjsp_encoder_arm_env_step: the machine

@@ -185,8 +185,11 @@ int mtfjsp_step_params(mtfjsp_handle_t h, const int32_t *task_idx, const int32_t
  * its device's LDS capacity and the diagnostic switches MTFJSP_ENV_KERNEL / MTFJSP_ENV_LDS / MTFJSP_ENV_STEP_G as they are NOW — they are
  * read on every call).  mtfjsp_step_kernel_name_for: the same for a shape without a handle, where a workgroup may use lds_max bytes of
  * LDS (gfx950: 160 KiB); no device is touched.  Optional outputs: instances per workgroup, bytes of one instance's LDS region (0: register
- * kernels), whether a switch is set.  NULL for a shape mtfjsp_create rejects. */
+ * kernels), whether a switch is set.  NULL for a shape mtfjsp_create rejects, one that needs more than lds_max bytes for a single instance
+ * included.  mtfjsp_step_launch_info: of that same launch on a live handle, the instances per workgroup, the dynamic LDS bytes of the
+ * launch (0: register kernels) and the LDS a workgroup may use on the handle's device; every output is optional. */
 const char *mtfjsp_step_kernel_name(mtfjsp_handle_t h);
+int mtfjsp_step_launch_info(mtfjsp_handle_t h, int32_t *group_out, int64_t *lds_launch_out, int64_t *lds_max_out);
 const char *mtfjsp_step_kernel_name_for(int32_t n_job, int32_t n_machine, int32_t batch, int32_t obs_f32, int64_t lds_max,
                                         int32_t *group_out, int64_t *lds_bytes_out, int32_t *overridden_out);
 /* host variant: returns MTFJSP_ERR_ACTION if any status word carries MTFJSP_ST_INVALID — AFTER the launch: the valid instances of

@@ -419,6 +419,14 @@ def main():
         d, sp = run_trace(ins, 20, 20, 4, 1, episodes=1, policy="free", act_seed=7, w_seed=7, keep_every=20)
         speed["J20M20E4_B1"] = sp
         save("trace_j20m20e4_b1_free", d)
+    # beyond J20M20, towards the limits mtfjsp_create accepts: more than 64 jobs (more than one job per lane in the step kernels), a
+    # pairwise energy sum of 8 leaves (T = 560), and 64 machines (the largest transport matrix and machine rows)
+    for key, (j, m, e, every) in {"j65m2e1": (65, 2, 1, 13), "j70m8e2": (70, 8, 2, 56), "j4m64e4": (4, 64, 4, 32)}.items():
+        if want(key):
+            ins = ref_generate(2, j, m, e, 31)
+            d, sp = run_trace(ins, j, m, e, 1, episodes=1, policy="free", act_seed=8, w_seed=8, keep_every=every)
+            speed[f"J{j}M{m}E{e}_B1"] = sp
+            save(f"trace_{key}_b1_free", d)
     if want("ties"):
         # integer times: exact ties at the three comparisons that choose the scheduling path (env:1548, 1587-1604).  The action
         # seeds are the first for which the oracle's counters (OracleBatch.ties) see each of the three kinds in each trace;

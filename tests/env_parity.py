@@ -15,6 +15,12 @@ front insertion and 21 to 50 % down the gap insertion.  data: "generated" times 
 "integer" times (integer_data) tie everywhere, which is the only input on which `<=` differs from `<` in the three comparisons that
 choose the scheduling path.  oracle_walk runs the oracle alone over the same instances and actions: tests/test_env_insertions_cpu.py
 uses it to prove that a case reaches what it is about.
+
+adjacency: "dense" reads the whole [B, T, T] adjacency after every step — 100 MB per step at T = 2048.  "sparse" compares what the
+kernels write, the two in-edge slots of every row (ell_col / ell_val), with the oracle's own ELL (observe(dense=False)) after every
+step, each row as the SET of its (column, value) pairs with column -1 = an empty slot, and the dense form after the reset and at the
+episode's end only.  tests/test_env_large_shapes_cpu.py proves on the CPU that the oracle's ELL is its dense adjacency in this sense,
+so the sparse comparison is as strong as the dense one.
 """
 import os
 from importlib import import_module
@@ -41,6 +47,17 @@ def dispatch_kernel(J, M, B, force=None):
             os.environ.pop(k, None)
             if saved[k] is not None:
                 os.environ[k] = saved[k]
+
+
+def create_lds_bytes(J, M, f32):
+    """csrc/mtfjsp_env_select.h's env_step_lds_bytes and mtfjsp_env.hip's env_reset_lds_bytes restated: the dynamic LDS of k_env_step
+    (one instance per workgroup) and of k_env_reset, and the larger of the two — what mtfjsp_create holds against the device's limit"""
+    T = J * M
+    Tp = (T + 7) & ~7
+    up16 = lambda x: (x + 15) & ~15
+    step = up16(up16((4 * T + Tp + M * M + 3 * M + 2 * J + 28 + 8) * 8) + M * 12 * (4 if f32 else 8)) + (3 * T + J + 4 * M + 1 + 4) * 4
+    reset = 3 * T * 8 + min(T, 64) * 12 * 8 + 16
+    return step, reset, max(step, reset)
 
 
 def random_valid(rs, cand, mask, feas):
@@ -147,6 +164,15 @@ def oracle_walk(J, M, E, B, left_shift=True, episodes=1, seed=0, policy="mask", 
                 actions=np.array(actions, np.int32).reshape(episodes, T, B, 3))
 
 
+def ell_rows(col, val):
+    """[.., 2] slots of every row in a canonical order (by column, then value), values as float64: two ELL forms hold the same set of
+    (column, value) pairs per row, -1 = empty, exactly when these arrays are equal"""
+    col = np.asarray(col).reshape(-1, 2).astype(np.int32); val = np.asarray(val).reshape(-1, 2).astype(np.float64)
+    swap = (col[:, 0] > col[:, 1]) | ((col[:, 0] == col[:, 1]) & (val[:, 0] > val[:, 1]))
+    col[swap] = col[swap][:, ::-1]; val[swap] = val[swap][:, ::-1]
+    return col, val
+
+
 def _same(got, want, what):
     got, want = np.asarray(got), np.asarray(want)
     assert got.dtype == want.dtype, f"{what}: dtype {got.dtype}, expected {want.dtype}"
@@ -158,17 +184,20 @@ def _same(got, want, what):
 
 
 def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force=None, monkeypatch=None, expect_kernel=None,
-               second_reset="reset", policy="mask", data="generated"):
+               second_reset="reset", policy="mask", data="generated", adjacency="dense", expect_launch=None):
     """-> number of compared steps.  policy, data: the action stream and the instance times (module docstring).
     force: MTFJSP_ENV_KERNEL for the handle's launches (needs monkeypatch).  expect_kernel: the kernel
     the case is about; asserted against the dispatch.  second_reset: how episodes after the first begin — "reset" (scaler_reset_returns
     + reset with fresh weights) or "reset_episode" (the one-launch form; the weights it draws are fed to the oracle's reset).  Every
-    later reset runs over the terminal state of the episode before: it must rewrite every row of a dirty observation buffer."""
+    later reset runs over the terminal state of the episode before: it must rewrite every row of a dirty observation buffer.
+    adjacency: "dense" or "sparse" (module docstring).  expect_launch: (instances per workgroup[, dynamic LDS bytes]) of the live
+    handle's step launch."""
     import mtfjsp_amd  # noqa: F401
     batch_env = import_module("e2e-mappo-for-mt-fjsp_amd.batch_env")
     capi = import_module("e2e-mappo-for-mt-fjsp_amd.capi")
     from oracle.env_oracle import OracleBatch
     assert obs_dtype in ("f32", "f64") and second_reset in ("reset", "reset_episode") and policy in POLICIES and data in DATA
+    assert adjacency in ("dense", "sparse")
     if monkeypatch is not None:
         for k in _SELECTION_VARS:
             monkeypatch.delenv(k, raising=False)
@@ -189,15 +218,23 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
     env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=left_shift, obs_dtype=obs_dtype)
     if expect_kernel is not None:                    # the live handle's own answer: this device's LDS, the switches as set above
         assert env.step_kernel_name() == expect_kernel, (env.step_kernel_name(), expect_kernel)
+    if expect_launch is not None:
+        assert env.step_launch_info()[:len(expect_launch)] == tuple(expect_launch), (env.step_launch_info(), expect_launch)
     env.load_instances(t, p, tt, edge=edge)
     env.scaler_init()
     orc = OracleBatch(t, p, tt, edge, left_shift=left_shift)
     orc.scaler_init()
 
+    sparse = adjacency == "sparse"
+
     def check_observation(o, tag):
         _same(env.tasks_fea.cpu().numpy(), obs(o["tfea"]), tag + " tasks_fea")
         _same(env.m_fea2.cpu().numpy(), obs(o["mfea2"]), tag + " m_fea2")
-        _same(env.dense_adj().cpu().numpy(), o["adj"], tag + " dense_adj")
+        if sparse:
+            got, want = ell_rows(env.ell_col.cpu().numpy(), env.ell_val.cpu().numpy()), ell_rows(o["ell_col"], o["ell_val"])
+            _same(got[0], want[0], tag + " ell_col (rows as sets)"); _same(got[1], want[1], tag + " ell_val (rows as sets)")
+        if "adj" in o:
+            _same(env.dense_adj().cpu().numpy(), o["adj"], tag + " dense_adj")
         _same(env.valid_action_mask().cpu().numpy(), orc.valid_action_mask(), tag + " valid_action_mask")
 
     n = 0
@@ -233,7 +270,7 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
             env.step(task, mach)                                          # host variant: raises on an invalid action
             info, raw, paths = orc.step(task, mach)
             cand, mask = orc.job_mask_update(job)
-            o = orc.observe()
+            o = orc.observe(dense=not sparse or s == T - 1)
             st = env.status.cpu().numpy()
             assert not (st & (capi.ST_INVALID | capi.ST_INFEASIBLE)).any(), tag + " status flags"
             _same(st & capi.PATH_MASK, paths, tag + " scheduling path")

@@ -8,6 +8,9 @@ a regression of the split products by an order of magnitude would pass them.  Ev
   * asserts it against 5x the committed figure for that (case, tensor) when profiles/r05_encoder_errors.json holds one (never tighter
     than a few f32 ulps of the scale), never looser than the tensor class's hard cap (HARD_CAP: 2e-6 probabilities ... 5e-5 pooled
     embeddings) or the caller's blanket tolerance; a missing ledger file fails the import.
+The caps were measured at up to 400 rows per instance and 20 rows per softmax.  A caller that also holds a binary64 evaluation of the same
+network passes `at_least` = twice the float32 oracle's own normalised distance from it: where float32 itself is that far from the exact
+value the kernel is not asked for more (the rule `err_hip <= max(2 * err_f32, cap)` of tests/test_full_size_gpu.py).
 Test infrastructure only; nothing in the product imports it.
 """
 import atexit
@@ -60,24 +63,31 @@ def _flush():
 atexit.register(_flush)
 
 
-def bound(case, tensor, blanket):
+def bound(case, tensor, blanket, at_least=0.0):
     cap = min(blanket, HARD_CAP.get(tensor, DEFAULT_CAP))
     rec = _budget.get(case, {}).get(tensor)
-    if rec is None:
-        return cap
-    return min(cap, max(MARGIN * float(rec), FLOOR))
+    if rec is not None:
+        cap = min(cap, max(MARGIN * float(rec), FLOOR))
+    return max(cap, float(at_least))
 
 
-def check(case, tensor, got, want, blanket, scale=None, relative=False):
+def normalised(got, want, scale=None, relative=False):
+    """the figure check() records: max |got - want| / scale, or elementwise / (1 + |want|) with relative=True"""
+    got = np.asarray(got, dtype=np.float64); want = np.asarray(want, dtype=np.float64)
+    d = np.abs(got - want)
+    return float((d / (1.0 + np.abs(want))).max()) if relative else float(d.max()) / (float(scale) if scale else 1.0)
+
+
+def check(case, tensor, got, want, blanket, scale=None, relative=False, at_least=0.0):
     """max |got - want| / scale (relative=True: elementwise / (1 + |want|), the critic-value form) recorded under (case, tensor)
-    and asserted against bound(); -> the normalised error"""
+    and asserted against bound(); -> the normalised error.  at_least: a lower limit of the bound (module docstring)"""
     got = np.asarray(got, dtype=np.float64); want = np.asarray(want, dtype=np.float64)
     assert got.shape == want.shape, (case, tensor, got.shape, want.shape)
     assert np.isfinite(got).all(), (case, tensor, "not finite")
-    d = np.abs(got - want)
-    err = float((d / (1.0 + np.abs(want))).max()) if relative else float(d.max()) / (float(scale) if scale else 1.0)
+    err = normalised(got, want, scale, relative)
     c = _observed.setdefault(case, {})
     c[tensor] = max(c.get(tensor, 0.0), err)
-    b = bound(case, tensor, blanket)
-    assert err <= b, f"{case} / {tensor}: normalised error {err:.3e} > {b:.3e} (blanket {blanket:.1e}, committed {_budget.get(case, {}).get(tensor)})"
+    b = bound(case, tensor, blanket, at_least)
+    assert err <= b, (f"{case} / {tensor}: normalised error {err:.3e} > {b:.3e} (blanket {blanket:.1e}, committed {_budget.get(case, {}).get(tensor)}, "
+                      f"at least {at_least:.3e})")
     return err

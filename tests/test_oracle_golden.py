@@ -21,7 +21,7 @@ def test_oracle_bit_exact_on_reference_trace(name):
 def test_np_sum_restated():
     rs = np.random.RandomState(0)
     L = lib()
-    for n in (1, 5, 7, 8, 9, 36, 100, 128, 129, 400, 1000):
+    for n in (1, 5, 7, 8, 9, 36, 100, 128, 129, 400, 1000, 2048, 2304, 3000):
         for _ in range(50):
             a = rs.uniform(0.5, 2500.0, n)
             assert L.or_np_sum(a, n) == np.sum(a)

@@ -8,7 +8,7 @@ from types import SimpleNamespace
 import pytest
 
 import mtfjsp_amd  # noqa: F401
-from env_parity import _SELECTION_VARS
+from env_parity import _SELECTION_VARS, create_lds_bytes
 
 batch_env = import_module("e2e-mappo-for-mt-fjsp_amd.batch_env")
 plan = batch_env.step_kernel_for
@@ -43,13 +43,18 @@ BATCHES = (1, 15, 16, 17, 4096, 4097, 8192, 8193)
 
 
 def test_the_library_rule_equals_the_old_python_rule_wherever_two_regions_fit(switches):
-    seen, refused = set(), set()
+    seen, refused, too_large = set(), set(), set()
     for force in (None, "grp16", "grp4", "reg1", "lds", "lds1"):
         for env_lds in (None, "1"):
             for k, v in (("MTFJSP_ENV_KERNEL", force), ("MTFJSP_ENV_LDS", env_lds)):
                 switches.setenv(k, v) if v else switches.delenv(k, raising=False)
             for J, M in SHAPES:
                 for B in BATCHES:
+                    if create_lds_bytes(J, M, False)[2] > LDS:      # mtfjsp_create refuses it ("too large"), whatever the switches: no name
+                        with pytest.raises(ValueError):
+                            plan(J, M, B, False, LDS)
+                        too_large.add((J, M))
+                        continue
                     name, G, nbytes, overridden = plan(J, M, B, False, LDS)
                     want = old_rule(SimpleNamespace(J=J, M=M, T=J * M, B=B))
                     case = (J, M, B, force, env_lds, name, G, nbytes)
@@ -63,6 +68,7 @@ def test_the_library_rule_equals_the_old_python_rule_wherever_two_regions_fit(sw
                     seen.add(name)
     assert len(SHAPES) == 40 * 25 and seen == set(LDS_KERNELS) | {"k_env_grp16", "k_env_grp4", "k_env_grp16x2", "k_env_grp4x2", "k_env_reg"}
     assert refused and all(J * M > 1000 for J, M in refused) and len(refused) < len(SHAPES) // 20, sorted(refused)
+    assert too_large == {(J, 64) for J in range(37, 41)}, sorted(too_large)
 
 
 def test_lds_boundary_is_step_impls_quotient(switches):
@@ -106,8 +112,37 @@ def test_fused_tail_truth_table(switches):
     assert fused_tail(6, 6, 8192)
 
 
+def test_the_rows_beyond_j20m20_keep_their_kernel_group_and_region(switches):
+    """the table of tests/test_env_large_shapes_gpu.py with lds_max fixed at gfx950's 163840 bytes: a change of the LDS layout cannot
+    silently move a row to another kernel or group size"""
+    from test_env_large_shapes_gpu import LDS_GFX950, ROWS
+    assert LDS_GFX950 == LDS == 163840 and len(ROWS) == 7
+    want = {(65, 2, 11): (("k_env_step_grp", 8, 6976), ("k_env_step_grp", 8, 7072)),
+            (70, 8, 7): (("k_env_step_grp", 4, 23984), ("k_env_step_grp", 4, 24368)),
+            (4, 64, 11): (("k_env_step_grp", 8, 16448), ("k_env_step_grp", 8, 19520)),
+            (64, 16, 3): (("k_env_step_grp", 2, 42272), ("k_env_step_grp", 2, 43040)),
+            (30, 64, 3): (("k_env_step_grp", 2, 80304), ("k_env_step", 1, 83376)),
+            (64, 32, 3): (("k_env_step", 1, 82784), ("k_env_step", 1, 84320)),
+            (36, 64, 2): (("k_env_step", 1, 95152), ("k_env_step", 1, 98224))}
+    assert {(r.J, r.M, r.B) for r in ROWS} == set(want)
+    for r in ROWS:
+        for f32, w, row in ((True, want[r.J, r.M, r.B][0], r.f32), (False, want[r.J, r.M, r.B][1], r.f64)):
+            assert plan(r.J, r.M, r.B, f32, LDS) == w + (False,), (r, f32)
+            assert (row.kernel, row.G, row.region) == w, (r, f32)
+    # k_env_step's own launch at the largest accepted shape, and the first shapes past the limit
+    assert [create_lds_bytes(36, 64, f)[0] for f in (True, False)] == [159236, 162308]
+    assert create_lds_bytes(40, 64, True)[0] == 172628
+    for J, f32, fits in ((36, False, True), (37, True, True), (37, False, False), (40, True, False)):
+        if fits:
+            assert plan(J, 64, 2, f32, LDS)[:2] == ("k_env_step", 1)
+        else:
+            with pytest.raises(ValueError):
+                plan(J, 64, 2, f32, LDS)
+        assert (create_lds_bytes(J, 64, f32)[2] <= LDS) == fits
+
+
 def test_shapes_no_handle_takes_have_no_name():
     L = import_module("e2e-mappo-for-mt-fjsp_amd.capi").lib()
-    for J, M, B in [(0, 6, 1), (6, 1, 1), (6, 65, 1), (6, 6, 0), (600, 64, 1)]:
+    for J, M, B in [(0, 6, 1), (6, 1, 1), (6, 65, 1), (6, 6, 0), (600, 64, 1), (40, 64, 1)]:
         assert L.mtfjsp_step_kernel_name_for(J, M, B, 0, LDS, None, None, None) is None
     assert L.mtfjsp_step_kernel_name_for(6, 6, 1, 0, LDS, None, None, None) == b"k_env_grp16"

@@ -10,7 +10,9 @@ TRACES = ["trace_j6m6e2_train16_mask", "trace_j6m6e2_eval16_free", "trace_j6m6e2
           "trace_j6m6e2_eval4_noleftshift", "trace_j10m6e2_b3_free", "trace_j10m10e2_b2_free",
           "trace_j10m10e2_b2_mask", "trace_j20m20e4_b1_free",
           # integer times, mask-free "blocks" actions: exact ties at the three comparisons that choose the scheduling path
-          "trace_j6m6e2_int_b8_blocks", "trace_j10m10e2_int_b2_blocks"]
+          "trace_j6m6e2_int_b8_blocks", "trace_j10m10e2_int_b2_blocks",
+          # beyond J20M20: more than 64 jobs, a pairwise energy sum of 8 leaves (T = 560), 64 machines
+          "trace_j65m2e1_b1_free", "trace_j70m8e2_b1_free", "trace_j4m64e4_b1_free"]
 
 
 def load(name):
