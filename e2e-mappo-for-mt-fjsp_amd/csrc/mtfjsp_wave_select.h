@@ -1,7 +1,8 @@
 // mtfjsp_wave_select.h — the wave-wide selections of the library, once: the step kernels' reductions (mtfjsp_env.hip) and the "first
 // index of the extremum" of the search baselines (mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip).  Values
-// are compared and never computed with (fmax / fmin return one of their operands), so every selection equals a host model's bit for
-// bit, ties, NaNs and signed zeros included.
+// are compared and never computed with, and a reported value is read back from the lane that was picked — fmax / fmin return one of
+// their operands, but of -0.0 and +0.0, which are equal, not necessarily the picked one's — so every selection equals a host model's bit
+// for bit, ties, NaNs and signed zeros included.
 #pragma once
 #include <math.h>
 #include "mtfjsp_env_dev.h"
@@ -51,8 +52,8 @@ __device__ __forceinline__ int wave_scan_incl(int x)
 // The first index of the extremum over any number of candidates, 64 at a time in ascending index.  One pass: lane l offers
 // candidate first + l with value x if ok (a lane that is not ok contributes -/+inf and is never picked: neither is a NaN, which
 // equals nothing); the pass's winner is its lowest lane that holds the wave extremum, and it replaces what is held only with a
-// strictly better value — so the lowest index of the extremum is kept.  i < 0: nothing picked yet (v is then meaningless).  Every
-// lane holds the same (v, i).
+// strictly better value — so the lowest index of the extremum is kept.  v is the picked candidate's own x, not the wave extremum e (which
+// equals it, but may be the other zero).  i < 0: nothing picked yet (v is then meaningless).  Every lane holds the same (v, i).
 template <bool MAX>
 struct WaveBest {
     double v = 0.0;
@@ -62,10 +63,14 @@ struct WaveBest {
     {
         const double e = wave_ext<MAX>(ok ? x : (MAX ? -INFINITY : INFINITY));
         const unsigned long long eq = __ballot(ok && x == e);
-        if (eq && (i < 0 || better(e, v))) { v = e; i = first + __ffsll((long long)eq) - 1; }
+        if (eq && (i < 0 || better(e, v))) {
+            const int l = __ffsll((long long)eq) - 1;
+            v = rl_d(x, l); i = first + l;
+        }
     }
     // one wave's result into a combination of several: (strictly better value, else equal value and lower index); a wave that
-    // picked nothing (j < 0) is skipped.  Whatever the number of waves and their order, the lowest index of the extremum.
+    // picked nothing (j < 0) is skipped.  Whatever the number of waves and their order, the lowest index of the extremum, with the value
+    // that came with that index.
     __device__ __forceinline__ void merge(double x, int j)
     {
         if (j >= 0 && (i < 0 || better(x, v) || (x == v && j < i))) { v = x; i = j; }

@@ -245,10 +245,11 @@ int mtfjsp_fork(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32_t *src_ind
  * copies either way.  Errors as mtfjsp_fork; scratch.batch != src.batch * T: MTFJSP_ERR_ARG.
  * mtfjsp_lookahead_select: per source instance, the copy without those two flags whose raw[column] is LARGEST (rewards are
  * previous minus current cost: the least added cost; column 0..4 = scalar reward, makespan, idle, energy, transport, env:1051-1171),
- * compared as binary64, no arithmetic; ties go to the lowest (j, m) (pdrs:520 draws among tied jobs with random.choice, and the
+ * compared as binary64, no arithmetic; a NaN is never selected (-inf is a value like any other); ties go to the lowest (j, m) (pdrs:520 draws among tied jobs with random.choice, and the
  * reference fixes each task's machine beforehand by a machine rule: here the look-ahead ranges over (job, machine) jointly).
- * task_out, mach_out [B] (device; the action for mtfjsp_step(src, ...)), job_out [B] and best_out [B] f64 (the winning value)
- * may be NULL.  An instance without a valid copy (finished) gets task, machine, job -1 and best NaN.  One launch, one wavefront per
+ * task_out, mach_out [B] (device; the action for mtfjsp_step(src, ...)), job_out [B] and best_out [B] f64 (the winning value:
+ * the picked copy's own raw[column], bit for bit — -0.0 where that copy holds -0.0, whatever equal zero another copy holds)
+ * may be NULL.  An instance without a copy to pick (finished, or NaN in every copy that counts) gets task, machine, job -1 and best NaN.  One launch, one wavefront per
  * source instance, on src's stream; it reads scratch's bound status and raw and src's job records: ordering between the two
  * handles' streams is the caller's duty here too. */
 int mtfjsp_lookahead_expand(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_t *task_c, int32_t *mach_c);
@@ -283,7 +284,8 @@ int mtfjsp_lookahead_select(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_
  * (device u64 [N*W*T], what mtfjsp_state_signature(scratch) wrote; may be NULL) is given, every candidate with the pick's
  * signature is removed with it (duplicates are merged into their best, lowest-c representative).  Outputs, device [N*W], at
  * n*W + k: parent_out = g (the index of the following mtfjsp_fork), from_slot_out = w, task_out / mach_out = the child's action
- * (formed from beam's job records as mtfjsp_lookahead_select forms it), score_out = the value.  A rank left without a candidate
+ * (formed from beam's job records as mtfjsp_lookahead_select forms it), score_out = the value — the picked candidate's own
+ * sum, bit for bit (of -0.0 and +0.0, which tie, each rank reports the zero its candidate holds).  A rank left without a candidate
  * writes -1, -1, -1, -1, -inf: the fork leaves that slot untouched and the score marks it empty.  An instance without any
  * candidate to pick (finished) keeps its beam: parent -1, from_slot = k, task = mach = -1, score_out = score_in.
  * 1 <= W <= 64, beam.batch % W == 0, W*T <= 8192 (the candidates live in one workgroup's LDS), column 0..4, scratch.batch ==

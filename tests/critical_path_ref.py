@@ -178,27 +178,50 @@ def search(data, start, K, rounds, seed, moves=EVERY_MOVE, left_shift=False, w=(
 
 
 # ---- the inputs the CPU and the GPU tests share
-SHAPES = {"J3M4": (3, 4, 2, 3), "J6M6": (6, 6, 2, 4), "J8M8": (8, 8, 2, 5), "J10M10": (10, 10, 2, 3)}   # J, M, E, N
+# J, M, E, N.  T = 128 and 129: the kernel's doubling loop ends its two conditions together, and takes one more doubling; J65M2: more
+# jobs than lanes; J10M20: the first launch of the directed moves above 48 KiB; J28M64 (T = 1792): the first T at M = 64 whose paths
+# need more than 48 KiB of LDS (crit_lds_bytes below), all 64 machines
+SHAPES = {"J3M4": (3, 4, 2, 3), "J6M6": (6, 6, 2, 4), "J8M8": (8, 8, 2, 5), "J10M10": (10, 10, 2, 3),
+          "J16M8": (16, 8, 2, 3), "J43M3": (43, 3, 1, 3), "J65M2": (65, 2, 1, 3), "J10M20": (10, 20, 2, 3), "J28M64": (28, 64, 2, 2)}
+# the shapes of the directed moves alone (tests/test_critical_moves_gpu.py): one replay each, no stops
+MOVE_SHAPES = {"J15M16": (15, 16, 2, 3), "J20M20": (20, 20, 2, 3), "J70M8": (70, 8, 2, 3), "J47M32": (47, 32, 2, 2),
+               "J48M32": (48, 32, 2, 2)}
 CONFIG_W = (0.4, 0.4, 0.2)
 
 
-def on_a_grid(data):
+def on_a_grid(data, dur=8.0, trans=4.0):
     """the instances with every duration a multiple of 8 and every transport time a multiple of 4 (the sign of a duration, which
     marks an infeasible machine, stays): generated times are real-valued and never tie; these tie in the largest finish time and in
     both arcs of a task"""
     t, p, tt, edge = (np.asarray(x) for x in data)
-    tg = np.sign(t) * np.maximum(8.0, np.round(np.abs(t) / 8.0) * 8.0)
-    return tg, p, np.round(tt / 4.0) * 4.0, edge
+    tg = np.sign(t) * np.maximum(dur, np.round(np.abs(t) / dur) * dur)
+    return tg, p, np.round(tt / trans) * trans, edge
+
+
+# Beyond T = 100 the grid of 8 no longer ties in the LARGEST finish time (measured: no schedule of the five shapes below does, at any
+# stop), and never in two passes of 64 tasks.  On a grid of 64 — durations 64 or 128, transport times 0 — every one of these shapes has
+# a schedule whose largest finish time is shared by tasks of different passes (tests/test_critical_path_cpu.py asserts it)
+COARSE = ("J16M8", "J43M3", "J65M2", "J10M20", "J28M64")
 
 
 def shape_inputs(shape):
-    """-> (J, M, E, N), {variant: data}, (task, mach): N generated instances as they are and on the grid, one random plan each"""
+    """-> (J, M, E, N), {variant: data}, (task, mach): N generated instances as they are and on the grid, one random plan each (and on the grid of 64 for the
+    shapes of COARSE)"""
     from importlib import import_module
     import mtfjsp_amd  # noqa: F401
     inst = import_module("e2e-mappo-for-mt-fjsp_amd.instances")
-    J, M, E, N = SHAPES[shape]
+    J, M, E, N = SHAPES[shape] if shape in SHAPES else MOVE_SHAPES[shape]
     data = tuple(np.asarray(x) for x in inst.generate_instances(N, J, M, E, seed=8100 + J * 100 + M, native=False))
-    return (J, M, E, N), {"generated": data, "grid": on_a_grid(data)}, pref.random_plans(data[0], J, M, 17)
+    variants = {"generated": data, "grid": on_a_grid(data)}
+    if shape in COARSE:
+        variants["coarse"] = on_a_grid(data, 64.0, 64.0)
+    return (J, M, E, N), variants, pref.random_plans(data[0], J, M, 17)
+
+
+def crit_lds_bytes(T):
+    """csrc/mtfjsp_plan.hip's crit_lds_bytes restated: the dynamic LDS of k_critical_path — four waves, seven bytes a task (three u16
+    tables and the arc kinds) in rows of T + 1 entries padded to a multiple of 4.  Above 48 KiB the launch first asks for the size"""
+    return 4 * 7 * ((T + 4) & ~3)
 
 
 def stops(T):

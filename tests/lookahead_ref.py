@@ -2,7 +2,7 @@
 the device to it).  The oracle has no fork, so a decision is made the long way, the way the reference's idle-time rule does it
 (tester/pdrs.py:465-540): per step, an OracleBatch of T replicas of every source instance — replica (j, m) tries "job j's candidate
 task on machine m" — is reset, replays the whole prefix and takes the candidate step; replicas of a job whose mask (job_mask_state: 1 = finished) is set or of an
-infeasible machine (t < 0) do not count; the first index of the maximal raw[column] wins.  About B*T^3/2 oracle steps per episode.
+infeasible machine (t < 0) do not count; the first index of the maximal raw[column] wins (`select`).  About B*T^3/2 oracle steps per episode.
 """
 import functools
 
@@ -13,6 +13,18 @@ from oracle.env_oracle import OracleBatch
 
 def replicas(x, T):
     return np.repeat(np.asarray(x), T, axis=0)
+
+
+def select(values, counts):
+    """the selection rule, on one row: values[c] is copy c's value, counts[c] whether copy c counts.  -> the lowest index among the
+    counting copies whose value is not NaN and is not exceeded by any other counting, non-NaN value (a NaN is never selected; -inf
+    is a value like any other), or None where there is none.  The winning value is values[index] itself — it is never the result
+    of a max, so a -0.0 that ties with a +0.0 stays -0.0.  Plain Python comparisons, one copy at a time"""
+    vals, pick = np.asarray(values, np.float64).tolist(), None
+    for c, ok in enumerate(np.asarray(counts, bool).tolist()):
+        if ok and vals[c] == vals[c] and (pick is None or vals[c] > vals[pick]):
+            pick = c
+    return pick
 
 
 def model_step(t, p, tt, edge, w3, prefix, column, left_shift=True, w_cfg=(0.4, 0.4, 0.2)):
@@ -38,10 +50,10 @@ def model_step(t, p, tt, edge, w3, prefix, column, left_shift=True, w_cfg=(0.4, 
     act_m = np.where(valid, mm[None, :], mm[first][:, None]).astype(np.int32)
     _, raw, _ = orc.step(act_t.reshape(-1), act_m.reshape(-1))
     values = raw.reshape(B, T, 5)[:, :, column]
-    masked = np.where(valid, values, -np.inf)
-    best = masked.max(1)
-    pick = (masked == best[:, None]).argmax(1)                           # the first index of the maximum
-    assert valid[np.arange(B), pick].all()
+    pick = [select(values[b], valid[b]) for b in range(B)]
+    assert None not in pick, "a running instance has a counting copy with a value"
+    pick = np.array(pick)
+    best = values[np.arange(B), pick]                                    # the picked copy's own value
     return task_c[np.arange(B), pick].astype(np.int32), mm[pick].astype(np.int32), best, values, valid
 
 

@@ -162,3 +162,14 @@ def search(data, start, P, generations, seed, p_cross=0.8, p_mut=0.3, moves=mref
     return dict(start_obj=history[0], history=np.array(history[1:]).reshape(generations, N), plans=(task, mach),
                 cost={key: cum[:, i] for i, key in enumerate(COST_KEYS)}, final4=final4, obj=obj,
                 parents=np.array(parents, np.int32).reshape(generations, N * P, 2), kinds=np.array(kinds, np.int8).reshape(generations, N * P))
+
+
+def evo_lds_bytes(T, J, tile):
+    """csrc/mtfjsp_evolve.hip's evo_lds_bytes restated: the tile's cells and, per wave, six u16 / i16 arrays of T, the job counts and the
+    two bit maps (the job set: J bits, the machine coins: T bits)"""
+    return T * (tile + 1) * 4 + 4 * (T * 12 + J * 4 + ((J + 31) // 32 + (T + 31) // 32) * 4)
+
+
+def evo_launch(J, M):
+    """-> (tile, bytes, accepted) of mtfjsp_plan_offspring's launch (tests/plan_moves_ref.py: choose_tile)"""
+    return mref.choose_tile(lambda tile: evo_lds_bytes(J * M, J, tile))

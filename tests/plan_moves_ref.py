@@ -133,3 +133,26 @@ def search(data, start, K, rounds, seed, moves=ALL_MOVES, left_shift=False, w=(0
     return dict(start_obj=obj.copy() if start_obj is None else start_obj, history=np.array(history).reshape(rounds, N),
                 accepted=np.array(accepted, np.int8).reshape(rounds, N), plans=(task, mach),
                 cost={key: cum[:, i] for i, key in enumerate(COST_KEYS)}, final4=final4, obj=obj)
+
+
+# ---- the launch of the plan kernels, restated from csrc/mtfjsp_plan_dev.h and csrc/mtfjsp_plan.hip (for the tests that are written to
+# reach one tile or one side of a limit: they assert these numbers, so a case that moves to another branch fails instead of passing)
+PLAN_LDS_SOFT, PLAN_LDS_HARD, PLAN_LDS_ASK = 64 * 1024, 160 * 1024, 48 * 1024      # two workgroups per CU | all a workgroup can have | above: asked for
+
+
+def plan_lds_bytes(T, J, tile, crit=False):
+    """the tile's cells (odd pitch), four waves' position map and job counts, with a critical path three more arrays per wave"""
+    return T * (tile + 1) * 4 + 4 * (T * 4 + J * 4) + (4 * T * 6 if crit else 0)
+
+
+def choose_tile(nbytes):
+    """nbytes(tile) -> (tile, bytes, accepted): the largest of 64, 32, 16 that stays within PLAN_LDS_SOFT, else 16, which may use up to
+    PLAN_LDS_HARD"""
+    tile = 64
+    while tile > 16 and nbytes(tile) > PLAN_LDS_SOFT:
+        tile >>= 1
+    return tile, nbytes(tile), nbytes(tile) <= PLAN_LDS_HARD
+
+
+def plan_launch(J, M, crit=False):
+    return choose_tile(lambda tile: plan_lds_bytes(J * M, J, tile, crit))

@@ -259,9 +259,10 @@ def test_selection_at_the_size_limit_on_synthetic_children(with_sig):
     """J13M10 at W = 63: 8 190 candidates per instance, 128 KB of (value, signature) pairs in LDS — no episode's model is affordable
     there, so the children are synthetic: status words, raw rewards (few distinct values: ties; NaN and -inf among them), signatures
     (few distinct: many duplicates) and parent scores (some slots empty) are written straight into the scratch handle's bound
-    buffers, and the selection rule of tests/beam_ref.py is applied to the same arrays"""
+    buffers, and the selection rule of tests/beam_ref.py is applied to the same arrays.  A third instance has its maximum at zeros
+    of both signs: a score is its own candidate's sum, bit for bit, never the other zero"""
     batch_env, baselines, capi = _mods()
-    J, M, E, N, W, column = 13, 10, 2, 2, 63, 3
+    J, M, E, N, W, column = 13, 10, 2, 3, 63, 3
     T = J * M
     mk = lambda b: batch_env.DeviceBatchEnv(J, M, E, b, left_shift=False, obs_dtype="f32", w_cfg=ref.CONFIG_W)      # noqa: E731
     beam, scratch = mk(N * W), mk(N * W * T)
@@ -269,16 +270,30 @@ def test_selection_at_the_size_limit_on_synthetic_children(with_sig):
         e.generate_instances(3); e.scaler_init()
         e.reset(torch.tensor([ref.CONFIG_W], dtype=torch.float64, device=e.device).repeat(e.B, 1))
     rng = np.random.RandomState(8)
-    R = N * W * T
-    raw = rng.randint(-6, 7, (R, 5)).astype(np.float64) * 0.375
-    raw[rng.rand(R) < 0.01, column] = np.nan
-    raw[rng.rand(R) < 0.01, column] = -np.inf
-    status = np.where(rng.rand(R) < 0.3, capi.ST_INVALID, 0) | np.where(rng.rand(R) < 0.2, capi.ST_INFEASIBLE, 0) | rng.randint(0, 8, R)
-    score = rng.randint(-4, 5, N * W).astype(np.float64) * 0.75
-    score[rng.rand(N * W) < 0.25] = -np.inf
+    R2 = 2 * W * T                                                      # instances 0 and 1
+    raw = rng.randint(-6, 7, (R2, 5)).astype(np.float64) * 0.375
+    raw[rng.rand(R2) < 0.01, column] = np.nan
+    raw[rng.rand(R2) < 0.01, column] = -np.inf
+    status = np.where(rng.rand(R2) < 0.3, capi.ST_INVALID, 0) | np.where(rng.rand(R2) < 0.2, capi.ST_INFEASIBLE, 0) | rng.randint(0, 8, R2)
+    score = rng.randint(-4, 5, 2 * W).astype(np.float64) * 0.75
+    score[rng.rand(2 * W) < 0.25] = -np.inf
     score[W:W + 40] = -np.inf                                           # instance 1: few live slots ...
-    sig = rng.randint(0, 2 if with_sig else 1 << 30, R).astype(np.uint64)
-    sig[W * T:] = rng.randint(0, 40, R - W * T)                          # ... and 40 signatures: ranks run out
+    sig = rng.randint(0, 2 if with_sig else 1 << 30, R2).astype(np.uint64)
+    sig[W * T:] = rng.randint(0, 40, R2 - W * T)                         # ... and 40 signatures: ranks run out
+    # instance 2: nothing above zero, and the zeros carry both signs — the top ranks are ties between -0.0 and +0.0, taken in index
+    # order, and every rank's score is its own candidate's sum (-0.0 only from -0.0 + -0.0).  Signatures all differ: every rank is filled
+    rng = np.random.RandomState(9)
+    raw2 = -np.abs(rng.randint(-6, 7, (W * T, 5)).astype(np.float64)) * 0.375
+    score2 = -np.abs(rng.randint(-4, 5, W).astype(np.float64)) * 0.75
+    raw2[raw2 == 0] = np.where(rng.rand((raw2 == 0).sum()) < 0.5, -0.0, 0.0)
+    score2[score2 == 0] = np.where(rng.rand((score2 == 0).sum()) < 0.5, -0.0, 0.0)
+    status2 = np.where(rng.rand(W * T) < 0.3, capi.ST_INVALID, 0) | np.where(rng.rand(W * T) < 0.2, capi.ST_INFEASIBLE, 0) | rng.randint(0, 8, W * T)
+    score2[0], raw2[7, column], status2[7] = -0.0, -0.0, 0              # the lowest index of the maximum: -0.0 + -0.0
+    score2[W - 1], raw2[(W - 1) * T + 70, column], status2[(W - 1) * T + 70] = -0.0, 0.0, 0     # tied with it, from a later pass of another wave: +0.0
+    raw2[:7, column] = -0.375
+    raw, status, score = np.concatenate([raw, raw2]), np.concatenate([status, status2]), np.concatenate([score, score2])
+    sig = np.concatenate([sig, rng.permutation(W * T).astype(np.uint64)])
+    R = N * W * T
     dev = beam.device
     scratch.raw.copy_(torch.as_tensor(raw, device=dev)); scratch.status.copy_(torch.as_tensor(status.astype(np.int32), device=dev))
     d_score = torch.as_tensor(score, device=dev)
@@ -305,4 +320,7 @@ def test_selection_at_the_size_limit_on_synthetic_children(with_sig):
             assert (parent[i], from_slot[i], task[i], mach[i]) == (lo + c, w, r // M * M, r % M), f"instance {n} rank {k}"
             assert got[i].view(np.int64) == values[lo + c].view(np.int64), f"instance {n} rank {k}: value bits"
     assert empty > 0 if with_sig else empty == 0
+    top = got[2 * W:]                                                   # instance 2: the picks at zero, in rank order
+    zeros = top[top == 0]
+    assert parent[2 * W] == 2 * W * T + 7 and np.signbit(zeros[0]) and len(zeros) >= 4 and not np.signbit(zeros).all(), "rank 0 is the -0.0, later ranks hold +0.0"
     scratch.close(); beam.close()

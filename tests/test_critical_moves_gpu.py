@@ -2,7 +2,9 @@
 (tests/critical_path_ref.py, pinned by tests/test_critical_path_cpu.py) element for element, kinds included.
 The moves: path arrays taken from the device (`critical_path` of a handle that replayed the incumbents), T below, at and above one
 pass of 64 lanes, N*K no multiple of the tile, complete, half and empty schedules, every mask with a new kind, all five kinds, and
-moves = 7 through the new entry against the old entry; path entries out of range; refusals that write nothing.
+moves = 7 through the new entry against the old entry; path entries out of range; refusals that write nothing.  With paths from the host
+model: the tiles of 64, 32 and 16 copies, launches above 48 KiB of LDS, J > 64, the largest shape the directed moves accept (J47M32) and the
+first they refuse (J48M32).
 The search: the two rows of tests/test_local_search_gpu.py, moves = 31 and 24, left shift on and off, in chunks, with one copy, with no
 rounds, twice with one seed — every bit of start_obj, history, accepted, the plans and the three result entries."""
 import ctypes as C
@@ -43,10 +45,10 @@ def _same(got, exp, tag):
 class Setup:
     """N instances with a random plan each, a handle that replays the plans (the paths come from it) and the handle of the N*KN copies"""
 
-    def __init__(self, shape):
+    def __init__(self, shape, KN=KN):
         be, _, _ = _mods()
         (J, M, E, N), variants, (self.task, self.mach) = ref.shape_inputs(shape)
-        self.J, self.M, self.E, self.N, self.T, self.B = J, M, E, N, J * M, N * KN
+        self.J, self.M, self.E, self.N, self.T, self.B, self.KN = J, M, E, N, J * M, N * KN, KN
         self.data = variants["generated"]
         self.t = self.data[0]
         self.env = be.DeviceBatchEnv(J, M, E, self.B, left_shift=False, obs_dtype="f32")
@@ -70,9 +72,14 @@ class Setup:
         finally:
             top.close()
 
+    def host_paths(self, left_shift, steps):
+        """the same from the host model on the oracle's replay (no kernel but the one under test) -> host arrays"""
+        state = ref.replay(self.data, self.task, self.mach, left_shift, ref.CONFIG_W, steps)[4]
+        return ref.path_rows(state, np.asarray(self.data[2]), self.J, self.M)
+
     def run(self, moves, critical, entry="new"):
         """-> host (task [T,B], mach [T,B], kind [B]); the padding around the outputs and the sources are checked here"""
-        T, B = self.T, self.B
+        T, B, KN = self.T, self.B, self.KN
         bt = torch.full((T * B + 2 * PAD,), SENT, dtype=torch.int32, device=self.dev)
         bm = torch.full((T * B + 2 * PAD,), SENT, dtype=torch.int32, device=self.dev)
         bk = torch.full((B + 2 * PAD,), SENT, dtype=torch.int8, device=self.dev)
@@ -88,6 +95,7 @@ class Setup:
         return bt[PAD:PAD + T * B].view(T, B).cpu().numpy(), bm[PAD:PAD + T * B].view(T, B).cpu().numpy(), bk[PAD:PAD + B].cpu().numpy()
 
     def expected(self, moves, paths, bad=()):
+        KN = self.KN
         et, em, ek = ref.neighbours(self.t, self.task, self.mach, KN, SEED, ROUND, FIRST, moves, paths)
         for n in bad:
             et[n * KN:(n + 1) * KN] = -1
@@ -99,21 +107,43 @@ class Setup:
 
 
 @functools.lru_cache(maxsize=1)
-def _setup(shape):
-    return Setup(shape)
+def _setup(shape, KN=KN):
+    return Setup(shape, KN)
 
 
-@pytest.mark.parametrize("shape", ["J3M4", "J8M8", "J10M10"])
+# The launches the larger shapes are there for: shape -> (copies per group, tile, bytes of LDS of k_plan_neighbours<false, true>).  N * K
+# is no multiple of the tile; the paths come from the host model on the oracle's replay.  J47M32 is the largest T the directed moves
+# accept (656 bytes below PLAN_LDS_HARD): 2 x 3 copies, the masks with a directed kind only
+TILES = {"J10M20": (5, 64, 60160),                                      # the first launch above 48 KiB
+         "J15M16": (5, 32, 41520), "J20M20": (5, 16, 43520),
+         "J70M8": (5, 16, 61600),                                       # a tile of 16 above 48 KiB, J > 64
+         "J47M32": (3, 16, 163184)}
+
+
+@pytest.mark.parametrize("shape", ["J3M4", "J8M8", "J10M10"] + list(TILES))
 def test_every_mask_equals_the_model(shape):
-    S = _setup(shape)
+    large = shape in TILES
+    S = _setup(shape, TILES[shape][0]) if large else _setup(shape)
     T = S.T
+    points, masks = ((False, T), (True, T), (False, T // 2), (False, 0)), (8, 16, 24, 31, 7)
+    if large:
+        K, tile, nbytes = TILES[shape]
+        assert pref.plan_launch(S.J, S.M, crit=True) == (tile, nbytes, True) and (S.N * K) % tile != 0 and T > 64
+        assert (nbytes > pref.PLAN_LDS_ASK) == (shape in ("J10M20", "J70M8", "J47M32"))
+    if shape == "J47M32":
+        assert pref.PLAN_LDS_HARD - nbytes == 656 and not pref.plan_launch(48, 32, crit=True)[2]
+        points, masks = ((False, T), (True, T // 2)), (24, 31)
     old = S.run(7, None, entry="old")
     kinds = set()
-    for left_shift, steps in ((False, T), (True, T), (False, T // 2), (False, 0)):
-        dev_paths = S.paths(left_shift, steps)
-        paths = tuple(x.cpu().numpy() for x in dev_paths)
+    for left_shift, steps in points:
+        if large:
+            paths = S.host_paths(left_shift, steps)
+            dev_paths = tuple(torch.as_tensor(x, device=S.dev) for x in paths)
+        else:
+            dev_paths = S.paths(left_shift, steps)
+            paths = tuple(x.cpu().numpy() for x in dev_paths)
         assert (paths[2] > 0).all() if steps else (paths[2] == 0).all()
-        for moves in (8, 16, 24, 31, 7):
+        for moves in masks:
             tag = f"{shape} left_shift={left_shift} steps={steps} moves={moves}"
             et, em, ek = S.expected(moves, paths)
             gt, gm, gk = S.run(moves, dev_paths)
@@ -122,7 +152,33 @@ def test_every_mask_equals_the_model(shape):
             if moves == 7:
                 for got, exp, what in zip((gt, gm, gk), old, ("task", "mach", "kind")):
                     _same(got, exp, tag + " through the new entry against the old entry: " + what)
-    assert kinds == {-1, 1, 2, 4, 8, 16}
+    assert {-1, 8, 16} <= kinds <= {-1, 1, 2, 4, 8, 16} if large else kinds == {-1, 1, 2, 4, 8, 16}        # (12 or 4 drawn copies: not every kind)
+
+
+def test_one_job_more_than_the_directed_moves_accept():
+    """J48M32: a tile of 16 with the path arrays needs 166 656 bytes, more than a workgroup has — refused, nothing written; without
+    them 129 792 bytes, and the same handle takes the plain call"""
+    _, capi, _ = _mods()
+    assert pref.plan_launch(48, 32, crit=True) == (16, 166656, False) and pref.plan_launch(48, 32) == (16, 129792, True)
+    S = _setup("J48M32", 3)
+    L, h, T, B, N, dev, K = S.env.L, S.env.h, S.T, S.B, S.N, S.dev, S.KN
+    paths = tuple(torch.as_tensor(x, device=dev) for x in S.host_paths(False, 4))
+    bt = torch.full((T * B,), SENT, dtype=torch.int32, device=dev)
+    bm = torch.full((T * B,), SENT, dtype=torch.int32, device=dev)
+    bk = torch.full((B,), SENT, dtype=torch.int8, device=dev)
+    P = lambda x: C.c_void_p(x.data_ptr())                              # noqa: E731
+    for moves in (31, 16, 8):                                           # every mask with a directed kind stages the path rows
+        rc = L.mtfjsp_plan_neighbours_critical(h, K, P(S.src[0]), P(S.src[1]), N, None, SEED, ROUND, FIRST, moves, P(bt), P(bm), P(bk), *[P(x) for x in paths])
+        assert rc == capi.ERR_ARG, moves
+        msg = L.mtfjsp_last_error(h)
+        assert b"mtfjsp_plan_neighbours_critical" in msg and b"tile of 16" in msg, msg
+    torch.cuda.synchronize(dev)
+    for whole in (bt, bm, bk):
+        assert (whole.cpu().numpy() == SENT).all(), "an error return wrote to an output"
+    gt, gm, gk = S.run(7, None, entry="old")
+    et, em, ek = pref.neighbours(S.t, S.task, S.mach, K, SEED, ROUND, FIRST, 7)
+    _same(gk, ek, "J48M32 plain call after the refusal: kind")
+    _same(gt, np.ascontiguousarray(et.T), "J48M32 plain call after the refusal: task"); _same(gm, np.ascontiguousarray(em.T), "J48M32 plain call after the refusal: mach")
 
 
 @pytest.mark.parametrize("shape", ["J3M4", "J10M10"])

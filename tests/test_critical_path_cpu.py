@@ -1,6 +1,6 @@
 """CPU: the host model of mtfjsp_critical_path, of the two moves a critical path directs and of baselines.local_search with them
-(tests/critical_path_ref.py) is itself right, on schedules of the C oracle: random plans on J3M4, J6M6, J8M8 (T = 64) and J10M10
-(T = 100), left shift on and off, stopped after 2 steps, half way and complete; the generated instances as they are and with their
+(tests/critical_path_ref.py) is itself right, on schedules of the C oracle: random plans on J3M4, J6M6, J8M8 (T = 64), J10M10
+(T = 100), J16M8 (T = 128), J43M3 (T = 129), J65M2, J10M20 and J28M64 (T = 1792, 64 machines), left shift on and off, stopped after 2 steps, half way and complete; the generated instances as they are and with their
 times on a grid (generated times are real-valued and never tie: the grid gives equal largest finish times and tasks tight on both
 sides).  The GPU tests run the same inputs, so what these inputs cover is asserted here.
 The search runs on the two rows of tests/test_local_search_gpu.py with their seed 11 where left shift is off; with left shift on
@@ -75,6 +75,29 @@ def test_paths_are_critical_paths(shape):
                 assert st[path[-1]] == 0.0, tag + ": without left shift a complete schedule's path starts at 0"
 
 
+def test_the_large_shapes_are_where_the_kernel_changes_path():
+    """what the added shapes are there for, as arithmetic on the kernel's own formulae"""
+    T = {k: v[0] * v[1] for k, v in ref.SHAPES.items()}
+    assert (T["J16M8"], T["J43M3"], T["J65M2"], T["J28M64"]) == (128, 129, 130, 1792)
+    assert ref.crit_lds_bytes(1792) == 50288 > 48 * 1024 >= ref.crit_lds_bytes(27 * 64) and ref.crit_lds_bytes(100) == 4 * 7 * 104
+    doublings = lambda t: sum(1 for bit in range(16) if (1 << bit) < t)         # noqa: E731
+    assert (doublings(128), doublings(129)) == (7, 8)
+
+
+@pytest.mark.parametrize("shape", ref.COARSE)
+def test_the_coarse_variant_ties_in_the_largest_finish_time_across_passes(shape):
+    """the kernel finds element 0 in passes of 64 tasks: some schedule of every large shape must share its largest finish time between
+    two passes (the lowest task wins).  The generated and the grid-of-8 variants do not at these sizes"""
+    J, M, E, N = ref.SHAPES[shape]
+    found = {}
+    for tag, data, left_shift, steps, state in schedules(shape):
+        ft = np.where(state["mach"] >= 0, state["ft"], -1.0)
+        across = sum(len(set((np.flatnonzero(ft[b] == ft[b].max()) // 64).tolist())) > 1 for b in range(N))
+        found[tag.split()[1]] = found.get(tag.split()[1], 0) + across
+    print(shape, found)
+    assert found["coarse"] > 0
+
+
 def test_the_inputs_cover_every_branch():
     kinds, both, equal_max, swaps = set(), 0, 0, []
     for shape, (J, M, E, N) in ref.SHAPES.items():
@@ -88,7 +111,8 @@ def test_the_inputs_cover_every_branch():
                 prev = ref.predecessors(mach, routes, M)
                 sched = [a for a in range(T) if mach[a] >= 0]
                 both += sum(1 for a in pt[b, :pl[b]].tolist() if ref.tight(a, mach, st, ft, prev, ttb, M) == (True, True))
-                equal_max += sum(1 for a in sched if ft[a] == max(ft[c] for c in sched)) > 1
+                last = max(ft[c] for c in sched)
+                equal_max += sum(1 for a in sched if ft[a] == last) > 1
                 swaps.append(len(ref.swap_arcs(pt[b, :pl[b]].tolist(), pa[b, :pl[b]].tolist(), M)))
     print("arc kinds", kinds, "path tasks tight on both sides", both, "schedules with equal largest finish times", equal_max, "swap arcs", swaps)
     assert kinds == {-1, 0, 1}, "both kinds of arc occur"

@@ -1,7 +1,8 @@
 """GPU: mtfjsp_critical_path (k_critical_path, csrc/mtfjsp_plan.hip) EQUALS its host model (tests/critical_path_ref.py, pinned by
 tests/test_critical_path_cpu.py) element for element — path_task, path_arc and path_len — on the inputs that file proves to cover
-both kinds of arc, tasks tight on both sides, equal largest finish times: four shapes with T below, at and above one pass of 64 lanes,
-N = 3..5 rows (the last workgroup's four waves are not all used), left shift on and off, after 0, 2, T / 2 and T steps.  The model
+both kinds of arc, tasks tight on both sides, equal largest finish times (in different passes of 64 tasks too): T below, at and above
+one pass of 64 lanes, T = 128 and 129 (the doubling loop's last round), J > 64, and J28M64 (T = 1792, 50 288 bytes of LDS: the launch
+that asks for more than 48 KiB; 64 machines), N = 2..5 rows (the last workgroup's four waves are not all used), left shift on and off, after 0, 2, T / 2 and T steps.  The model
 reads `read_state` of the very handle the kernel reads.  Every form of `col`, and nothing written outside the outputs or on an
 error return."""
 import ctypes as C
@@ -62,13 +63,23 @@ def _paths(env, col=None):
     return tuple(x.cpu().numpy() for x in out)
 
 
+# every shape on its variants; J28M64 (2 x 1792 replayed steps a case) without the generated one, whose times never tie
+INPUTS = [(shape, variant) for shape in ref.SHAPES for variant in ("generated", "grid") + (("coarse",) if shape in ref.COARSE else ())
+          if (shape, variant) != ("J28M64", "generated")]
+# what the kernel's launch depends on, per shape: bytes of LDS (above 48 KiB the launch asks for them first) and passes of 64 tasks
+LAUNCH = {"J3M4": (448, 1), "J6M6": (1120, 1), "J8M8": (1904, 1), "J10M10": (2912, 2), "J16M8": (3696, 2), "J43M3": (3696, 3), "J65M2": (3696, 3),
+          "J10M20": (5712, 4), "J28M64": (50288, 28)}
+
+
 @pytest.mark.parametrize("left_shift", [False, True], ids=["no_left_shift", "left_shift"])
-@pytest.mark.parametrize("variant", ["generated", "grid"])
-@pytest.mark.parametrize("shape", list(ref.SHAPES))
+@pytest.mark.parametrize("shape,variant", INPUTS, ids=[f"{s}-{v}" for s, v in INPUTS])
 def test_paths_equal_the_model(shape, variant, left_shift):
     (J, M, E, N), variants, (task, mach) = ref.shape_inputs(shape)
     data, T = variants[variant], J * M
+    assert (ref.crit_lds_bytes(T), (T + 63) // 64) == LAUNCH[shape]
     env = _open(shape, data, left_shift)
+    if shape == "J28M64":                                               # M = 64: the copies step two to a workgroup
+        assert ref.crit_lds_bytes(T) > 48 * 1024 and (env.step_kernel_name(), env.step_launch_info()[0]) == ("k_env_step_grp", 2)
     try:
         dt, dm = (torch.as_tensor(np.ascontiguousarray(x.T), device=env.device) for x in (task, mach))     # [T,N]: row s = step s
         pt, pa, pl = _paths(env)

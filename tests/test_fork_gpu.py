@@ -6,7 +6,7 @@ comparison is in full — observation, dense adjacency, masks, info, raw and eve
 after EVERY later step (a step rewrites only the rows its decision changes, see tests/env_parity.py), with the rows a step must
 rewrite poisoned first.
 
-Shapes: one per layout the records are read in (the dispatched kernel is asserted), 5 source and 13 destination instances, f32 and
+Shapes: one per layout the records are read in (the dispatched kernel is asserted; J65M2E1: more jobs than lanes), 5 source and 13 destination instances, f32 and
 f64 observations.  The destination is dirty (it has finished an episode on other instances), the index has duplicates and is not
 monotone.
 """
@@ -29,7 +29,10 @@ SHAPES = {
     "J3M11E1": (3, 11, 1, "k_env_grp16x2"),        # the two-slot register kernel
     "J5M12E2": (5, 12, 2, "k_env_step_grp"),       # the LDS kernel
     "J9M8E2": (9, 8, 2, "k_env_grp16x2"),          # T = 72
+    "J65M2E1": (65, 2, 1, "k_env_step_grp"),       # more jobs than lanes: job records walk more than one job a lane, and job_mask (65 bytes) is copied byte by byte
 }
+# every shape at every point; J65M2E1 (130 steps compared in full) at the reset and half way
+POINTS = [(shape, point) for shape in SHAPES for point in ("reset", "half", "terminal") if (shape, point) != ("J65M2E1", "terminal")]
 
 
 def _mods():
@@ -147,8 +150,7 @@ def _expected(src, prefix, data, mods, left_shift, tag, seed, index=INDEX):
 
 
 @pytest.mark.parametrize("obs_dtype", ["f32", "f64"])
-@pytest.mark.parametrize("point", ["reset", "half", "terminal"])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape,point", POINTS, ids=[f"{s}-{p}" for s, p in POINTS])
 def test_a_fork_equals_the_oracle_at_the_prefix_and_at_every_later_step(shape, point, obs_dtype):
     src, dst, data, mods = _setup(shape, obs_dtype)
     T = src.T

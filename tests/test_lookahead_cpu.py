@@ -1,6 +1,7 @@
 """No GPU: the host model of the one-step look-ahead rules (tests/lookahead_ref.py) on J3M4 — the yardstick of
 tests/test_lookahead_gpu.py must itself be right: every pick is valid, episodes finish in T steps, and at an independently replayed
-step no valid candidate beats the pick (larger value, or equal value at a lower index)."""
+step no valid candidate beats the pick (larger value, or equal value at a lower index).  The selection rule itself (`ref.select`) is
+pinned on hand-written rows: ties across index 63 / 64, -inf, NaN, both zeros, a copy that does not count."""
 import numpy as np
 import pytest
 
@@ -50,3 +51,35 @@ def test_no_valid_candidate_beats_the_pick(column, s):
         assert len(pick) == 1 and pick[0][3] == best[s, b]
         for c, _, _, v in seen:
             assert v <= pick[0][3] and not (v == pick[0][3] and c < pick[0][0]), f"instance {b}: candidate {c} beats the pick"
+
+
+def test_select_on_hand_written_rows():
+    """the selection rule itself (ref.select), where no episode asks: ties across a pass boundary, -inf, NaN, both zeros, and a
+    copy that does not count"""
+    inf, nan = np.inf, np.nan
+    # a tie across index 63 / 64: the lower index; with 63 not counting, the next one
+    v = np.full(130, 1.0); v[[63, 64, 129]] = 7.5
+    ok = np.ones(130, bool)
+    assert ref.select(v, ok) == 63
+    ok[63] = False
+    assert ref.select(v, ok) == 64
+    ok[64] = False
+    assert ref.select(v, ok) == 129
+    # only -inf counts: -inf is a value, the lowest COUNTING index wins (copy 0 does not count, whatever it holds)
+    v = np.array([-inf, 3.0, -inf, -inf, 5.0]); ok = np.array([False, False, True, True, False])
+    assert ref.select(v, ok) == 2 and v[ref.select(v, ok)] == -inf
+    assert ref.select(np.full(4, -inf), np.array([False, True, True, True])) == 1
+    # only NaN counts: nothing; a NaN beside values is passed over, also at index 0
+    assert ref.select(np.array([nan, nan, 1.0]), np.array([True, True, False])) is None
+    assert ref.select(np.array([nan, -2.0, nan, -2.0]), np.ones(4, bool)) == 1
+    assert ref.select(np.array([nan, -inf]), np.ones(2, bool)) == 1
+    # nothing counts, and the empty row
+    assert ref.select(np.array([1.0, 2.0]), np.zeros(2, bool)) is None and ref.select(np.zeros(0), np.zeros(0, bool)) is None
+    # the two zeros are equal: the lower index, and the value is that copy's own zero
+    for lo, hi in ((-0.0, 0.0), (0.0, -0.0)):
+        v = np.array([-1.0, lo, -3.0, hi, -1.0]); ok = np.ones(5, bool)
+        c = ref.select(v, ok)
+        assert c == 1 and np.signbit(v[c]) == np.signbit(lo)
+    # a copy that does not count holds the largest value (+inf included)
+    assert ref.select(np.array([9.0, 1.0, 2.0, inf]), np.array([False, True, True, False])) == 2
+    assert ref.select(np.array([1.0, inf, inf]), np.ones(3, bool)) == 1

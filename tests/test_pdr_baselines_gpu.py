@@ -173,6 +173,28 @@ def test_more_jobs_than_lanes():
     env.close()
 
 
+def test_sixty_four_machines():
+    """J4M64: the machine rule walks a full wave of entries, a planned machine is a byte up to 63, and the job sums of the restatement
+    are numpy's 8-way unrolled loop over exactly eight blocks — the order the kernel has to add in.  All 12 pairs against the restatement"""
+    J, M, E, N = 4, 64, 2, 8
+    t, p, tt, edge = instances.generate_instances(N, J, M, E, seed=35)
+    assert (t < 0).any(), "the set must contain infeasible machines"
+    rng = np.random.RandomState(7)
+    mor = np.stack([np.stack([rng.permutation(J) for _ in range(M)]) for _ in range(N)]).astype(np.int32)
+    o, m = all_rules(N)
+    env = env_with(rep12(t), rep12(p), rep12(tt), rep12(edge), J, M, E, left_shift=False)
+    task, mach = baselines.pdr_plan(env, o, m, mor_order=rep12(mor))
+    task, mach = task.cpu().numpy(), mach.cpu().numpy()
+    rt, rm = ref.plan_batch(rep12(t), rep12(p), J, M, o, m, rep12(mor))
+    bad = np.flatnonzero((task != rt).any(1) | (mach != rm).any(1))
+    print(f"J{J}M{M}: {len(bad)} of {12 * N} plans differ from the restatement", bad[:8])
+    assert np.array_equal(task, rt) and np.array_equal(mach, rm)
+    assert np.array_equal(np.sort(task, 1), np.tile(np.arange(J * M), (12 * N, 1))), "every task exactly once"
+    assert (rep12(t)[np.arange(12 * N)[:, None], task, mach] > 0).all(), "a planned machine cannot process its task"
+    assert mach.max() > 32 and len(np.unique(mach)) > 32, "machines of the upper half of the wave are planned"
+    env.close()
+
+
 def test_device_generated_instances_need_no_host_copy():
     """(7) planned straight after mtfjsp_generate_instances == the same instances read back and loaded again"""
     J, M, E, B = 6, 6, 2, 256

@@ -1,6 +1,6 @@
 """GPU: mtfjsp_plan_neighbours (csrc/mtfjsp_plan.hip) EQUALS its host model (tests/plan_moves_ref.py, pinned by
 tests/test_plan_moves_cpu.py) element for element, kinds included: T below, at and above one pass of 64 lanes, the T where the tile
-of copies shrinks to 32 and to 16, K = 1, 2, 5 (tiles straddle groups), 64, 67, batches that are no multiple of the tile, every
+of copies shrinks to 32 and to 16, the largest shape with 64 machines that fits a workgroup's LDS (J30M64) and the first that does not, K = 1, 2, 5 (tiles straddle groups), 64, 67, batches that are no multiple of the tile, every
 single move mask and all three, every form of the source column, and nothing written outside the outputs or on an error return."""
 import ctypes as C
 import functools
@@ -19,7 +19,11 @@ SEED, ROUND, FIRST = (1 << 45) + 77, 3, 3
 # (J, M, E), K, N: N*K is no multiple of the tile wherever K allows it (64 copies up to T = 236, 32 up to about T = 440, then 16)
 CASES = [((3, 2, 1), 1, 70), ((3, 2, 1), 67, 3), ((3, 4, 2), 2, 35), ((6, 6, 2), 5, 27), ((6, 6, 2), 64, 2), ((8, 8, 2), 64, 3),
          ((8, 8, 2), 5, 15), ((5, 13, 1), 67, 3), ((5, 13, 1), 2, 35), ((10, 10, 2), 5, 27), ((10, 10, 2), 1, 70), ((20, 20, 2), 5, 15),
-         ((15, 30, 2), 2, 9)]
+         ((15, 30, 2), 2, 9), ((30, 64, 2), 3, 2), ((4, 64, 2), 5, 7)]
+# the launches the cases at a limit are there for: (J, M) -> (tile, bytes of LDS, accepted) of k_plan_neighbours<false, false>.  J30M64 is the
+# largest shape with 64 machines the kernel accepts (2 080 bytes below PLAN_LDS_HARD), J31M64 the first it refuses; REASSIGN at M = 64
+# ballots its candidates over all 64 lanes
+LAUNCH = {(15, 30): (16, 38040, True), (30, 64): (16, 161760, True), (4, 64): (32, 37952, True), (31, 64): (16, 167152, False)}
 
 
 def _mods():
@@ -99,6 +103,9 @@ def _same(got, exp, tag):
 @pytest.mark.parametrize("shape,K,N", CASES, ids=[f"J{s[0]}M{s[1]}-K{k}-N{n}" for s, k, n in CASES])
 def test_every_mask_equals_the_model(shape, K, N):
     S = _setup(shape, K, N)
+    if shape[:2] in LAUNCH:
+        tile, nbytes, ok = ref.plan_launch(*shape[:2])
+        assert (tile, nbytes, ok) == LAUNCH[shape[:2]] and ok and (N * K) % tile != 0
     stride = N + 5                                                      # wider than the columns used
     st, sm = S.source(range(N), stride)
     for moves in (1, 2, 4, 7):
@@ -213,3 +220,33 @@ def test_errors_write_nothing():
     assert np.array_equal(dt.cpu().numpy(), st) and np.array_equal(dm.cpu().numpy(), sm)
     et, em, _ = S.expected(7)
     _same(good[0], et, "the call between the errors: task"); _same(good[1], em, "the call between the errors: mach")
+
+
+def test_one_job_more_than_the_largest_shape_with_64_machines_is_refused():
+    """J31M64: a tile of 16 plans needs 167 152 bytes of LDS, J30M64 (a case above) 161 760 of the 163 840 a workgroup has.  The refusal
+    names the tile, writes nothing, and the handle stays usable"""
+    be, capi, _ = _mods()
+    assert ref.plan_launch(31, 64) == LAUNCH[31, 64] and ref.plan_launch(30, 64) == LAUNCH[30, 64]
+    assert LAUNCH[30, 64][1] <= ref.PLAN_LDS_HARD < LAUNCH[31, 64][1]
+    J, M, K, N = 31, 64, 3, 2
+    T, B = J * M, K * N
+    env = be.DeviceBatchEnv(J, M, 2, B, left_shift=False, obs_dtype="f32")
+    try:
+        env.generate_instances(1)
+        dev, L = env.device, env.L
+        src = torch.zeros((T, N), dtype=torch.int32, device=dev)
+        outs = [torch.full((T * B,), SENT, dtype=torch.int32, device=dev) for _ in range(2)] + [torch.full((B,), SENT, dtype=torch.int8, device=dev)]
+        P = lambda x: C.c_void_p(x.data_ptr())                          # noqa: E731
+        for moves in (7, 1, 4):
+            assert L.mtfjsp_plan_neighbours(env.h, K, P(src), P(src.clone()), N, None, SEED, ROUND, FIRST, moves, *[P(x) for x in outs]) == capi.ERR_ARG
+            msg = L.mtfjsp_last_error(env.h)
+            assert b"mtfjsp_plan_neighbours" in msg and b"tile of 16" in msg, msg
+        torch.cuda.synchronize(dev)
+        assert all((x.cpu().numpy() == SENT).all() for x in outs), "an error return wrote to an output"
+        # the handle still works: it reads back its instances and is reset
+        t = env.read_instances()[0]
+        assert t.shape == (B, T, M)
+        env.scaler_init(); env.reset(torch.full((B, 3), 1 / 3, dtype=torch.float64, device=dev))
+        assert (env.read_state(capi.STATE_MACHINE) == -1).all()
+    finally:
+        env.close()

@@ -1,7 +1,8 @@
 """GPU: mtfjsp_plan_offspring (csrc/mtfjsp_evolve.hip) EQUALS its host model (tests/plan_crossover_ref.py, pinned by
 tests/test_plan_crossover_cpu.py) element for element — task_out, mach_out, parent_out and kind_out: T = 12 and 36 (one pass), 64 (a
 full pass), 65 (two passes) and 260 = J130 x M2 (M = 2 is the smallest the handle accepts: a second and third word block of the "jset"
-and "mach" streams, the tile of 32) and 400 = J20 x M20 (the tile of 16, once: P = 5, N = 7); P = 1, 3, 64, 100 with N*P no multiple of the tile wherever P allows it (P = 64 never does), so
+and "mach" streams, the tile of 32) and 400 = J20 x M20 (the tile of 16, once: P = 5, N = 7); the launches above 48 KiB of LDS — J10M20 (tile 64), J70M8 (tile 16 above
+the soft cap), J21M64 (the largest shape with 64 machines that is accepted) — and the refusal of J22M64 right at that edge; P = 1, 3, 64, 100 with N*P no multiple of the tile wherever P allows it (P = 64 never does), so
 that groups straddle workgroups and the last tile is partial; objectives with NaNs and ties, a whole group NaN with best = -1, best
 outside its group, best NULL; every single move mask and all three; thresholds 0, 2^32 and between; parents that are no plans; nothing
 written outside the outputs or on an error return."""
@@ -110,18 +111,29 @@ def _check(S, tag, *a, **kw):
 
 # every shape with every group, and T = 400: three tiles of 16 children, the last one partial, groups straddling tiles
 CASES = [(s, p, n) for s in SHAPES for p, n in GROUPS] + [((20, 20, 2), 5, 7)]
+# the launches above 48 KiB of LDS: (J, M) -> (tile, bytes, accepted) of k_plan_offspring.  J10M20: the first at the tile of 64; J70M8: a tile
+# of 16 above the soft cap of 64 KiB, three words of the job set; J21M64: the largest shape with 64 machines the kernel accepts, J22M64
+# the first it refuses (J30M50, further out, is refused in test_errors_write_nothing)
+LAUNCH = {(20, 20): (16, 46944, True), (10, 20): (64, 61888, True), (70, 8): (16, 66416, True), (21, 64): (16, 156928, True),
+          (22, 64): (16, 164400, False), (30, 50): (16, 175248, False)}
+CASES += [((10, 20, 2), 5, 7), ((70, 8, 2), 5, 7), ((21, 64, 2), 3, 2)]
 
 
 @pytest.mark.parametrize("shape,P,N", CASES, ids=[f"J{s[0]}M{s[1]}-P{p}-N{n}" for s, p, n in CASES])
 def test_offspring_equal_the_model(shape, P, N):
     S = _setup(shape, P, N)
     tag = f"J{shape[0]}M{shape[1]} P={P} N={N}"
+    if shape[:2] in LAUNCH:
+        tile, nbytes, ok = ref.evo_launch(*shape[:2])
+        assert (tile, nbytes, ok) == LAUNCH[shape[:2]] and ok and (N * P) % tile != 0
+        assert (nbytes > mref.PLAN_LDS_ASK) == (shape[:2] != (20, 20)) and (nbytes > mref.PLAN_LDS_SOFT) == (shape[:2] in ((70, 8), (21, 64)))
     # thresholds between the ends, all three moves, the elite from `best` (one -1 beside a group of NaNs, one outside its group)
     got, exp = _check(S, tag + " mid", MID_CROSS, MID_MUT, 7)
     assert (got[2][::P] == -1).all() and (got[3][::P] == -1).all(), "child 0 is the elite"
     if P > 1:
         crossed, kinds = got[2][:, 1] >= 0, got[3]
-        assert crossed.any() and (~crossed[np.arange(S.B) % P != 0]).any() and {0} < set(kinds[kinds >= 0].tolist()) <= {0, 1, 2, 4}
+        # (what a batch of 20 or more is bound to draw; the six children of the largest shape need not)
+        assert S.B < 20 or crossed.any() and (~crossed[np.arange(S.B) % P != 0]).any() and {0} < set(kinds[kinds >= 0].tolist()) <= {0, 1, 2, 4}
         n = S.nan_group
         i = [(x * P) >> 32 for x in ref.words(SEED, GEN, FIRST + n, 1, ref.TAG_PARE)]
         assert got[2][n * P + 1, 0] == n * P + min(i[0], i[1]), "a whole group NaN selects by index"
@@ -225,6 +237,24 @@ def test_errors_write_nothing():
         assert all((x.cpu().numpy() == SENT).all() for x in outs)
     finally:
         big.close()
+    # right at the edge: J22M64 needs 164 400 bytes, 560 more than a workgroup has; J21M64 (a case above) is accepted with 156 928
+    assert ref.evo_launch(22, 64) == LAUNCH[22, 64] and ref.evo_launch(21, 64) == LAUNCH[21, 64] and ref.evo_launch(30, 50) == LAUNCH[30, 50]
+    assert LAUNCH[21, 64][1] <= mref.PLAN_LDS_HARD < LAUNCH[22, 64][1]
+    edge = be.DeviceBatchEnv(22, 64, 2, 6, left_shift=False, obs_dtype="f32")
+    try:
+        edge.generate_instances(1)
+        z = torch.zeros(1408 * 6, dtype=torch.int32, device=S.dev)
+        outs = [torch.full((1408 * 6,), SENT, dtype=torch.int32, device=S.dev) for _ in range(2)]
+        rc = L.mtfjsp_plan_offspring(edge.h, 3, ptr(z), ptr(z), ptr(torch.zeros(6, dtype=torch.float64, device=S.dev)), None, SEED, GEN, FIRST,
+                                     MID_CROSS, MID_MUT, 7, ptr(outs[0]), ptr(outs[1]), None, None)
+        msg = L.mtfjsp_last_error(edge.h)
+        assert rc == capi.ERR_ARG and b"mtfjsp_plan_offspring" in msg and b"tile of 16" in msg, msg
+        torch.cuda.synchronize(S.dev)
+        assert all((x.cpu().numpy() == SENT).all() for x in outs)
+        edge.scaler_init(); edge.reset(torch.full((6, 3), 1 / 3, dtype=torch.float64, device=S.dev))     # the handle stays usable
+        assert (edge.read_state(capi.STATE_MACHINE) == -1).all()
+    finally:
+        edge.close()
     for tag, kw in cases.items():
         assert call(**kw) == capi.ERR_ARG, tag
     torch.cuda.synchronize(S.dev)
