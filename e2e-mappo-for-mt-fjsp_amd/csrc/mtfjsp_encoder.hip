@@ -143,12 +143,15 @@ __device__ __forceinline__ void stage_bn(float *s_bn, const double *stats, doubl
         s_bn[HD + tid] = beta[tid] - (float)mean * sc;
     }
 }
-// the same from workgroup-local sums (LDS, no replicas): per-instance BatchNorm
-__device__ __forceinline__ void stage_bn_local(float *s_bn, const double *st, double inv_rows, const float *gamma, const float *beta, int tid)
+// the same from workgroup-local sums (LDS, no replicas): per-instance BatchNorm.  st is [nparts][256], one row of partial sums per
+// contributor (a wave or a row group), folded here in index order: the statistics do not depend on the order in which the contributors arrived
+__device__ __forceinline__ void stage_bn_local(float *s_bn, const double *st, int nparts, double inv_rows, const float *gamma, const float *beta, int tid)
 {
     if (tid < HD) {
-        const double mean = st[tid] * inv_rows;
-        double var = st[HD + tid] * inv_rows - mean * mean;
+        double su = 0.0, sq = 0.0;
+        for (int p = 0; p < nparts; p++) { su += st[p * 256 + tid]; sq += st[p * 256 + HD + tid]; }
+        const double mean = su * inv_rows;
+        double var = sq * inv_rows - mean * mean;
         if (var < 0) var = 0;
         const float rstd = 1.0f / sqrtf((float)(var + BN_EPS));
         const float sc = rstd * gamma[tid];
@@ -2681,7 +2684,8 @@ __global__ __launch_bounds__(512) void k_gin_inst(GinInstArgs A)
     float *s_w = reinterpret_cast<float *>(smem);                 // 128*128, swizzled
     float *s_a = s_w + HD * HD;                                   // 8 * 16 * LDA16
     float *s_bn = s_a + 8 * 16 * LDA16;                           // scale | shift of the producer's BatchNorm
-    double *s_st = reinterpret_cast<double *>(s_bn + 2 * HD);     // [2][256] column sum | sum of squares (ping-pong per layer)
+    double *s_st = reinterpret_cast<double *>(s_bn + 2 * HD);     // [8][256] column sum | sum of squares, one row per contributor (row group / wave):
+                                                                  // written before a barrier, folded in index order after it (stage_bn_local)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int j = lane & 31, h = lane >> 5, c4 = j * 4;
     const int m = lane & 15, q = lane >> 4, qo = q & 1;
@@ -2694,9 +2698,7 @@ __global__ __launch_bounds__(512) void k_gin_inst(GinInstArgs A)
     const float *bp = s_w + q * HD + m;
     int bo[8];
     for (int c = 0; c < 8; c++) bo[c] = (c ^ qo) * 16;
-    for (int i = tid; i < 512; i += 512) s_st[i] = 0.0;
-    __syncthreads();
-    // ---- layer 0: z0 = W0 agg(x) + b0 (gcn:125-153) -> zA, column sums -> s_st[0]
+    // ---- layer 0: z0 = W0 agg(x) + b0 (gcn:125-153) -> zA, column sums of row group rg -> s_st[rg]
     {
         const int c = tid & 127, rg = tid >> 7;                  // column, row group (4)
         float w[12];
@@ -2721,18 +2723,16 @@ __global__ __launch_bounds__(512) void k_gin_inst(GinInstArgs A)
             A.zA[g * HD + c] = a;
             su += (double)a; sq += (double)a * (double)a;
         }
-        atomicAdd(&s_st[c], su); atomicAdd(&s_st[HD + c], sq);
+        s_st[rg * 256 + c] = su; s_st[rg * 256 + HD + c] = sq;
     }
     __syncthreads();
     const float *in = A.zA;
     float *out = A.zB;
     for (int L = 0; L < 5; L++) {
-        double *st_in = s_st + (L & 1) * 256, *st_out = s_st + ((L + 1) & 1) * 256;
         stage_w16(s_w, A.Wt[L], tid);
         // BatchNorm feeding this product: L=0: mlps.0.bn0, 1: mlps.0.bn1, 2: outer bn0 (then aggregation), 3: mlps.1.bn0, 4: mlps.1.bn1
-        stage_bn_local(s_bn, st_in, invT, A.gamma[L], A.beta[L], tid);
-        if (tid < 256) st_out[tid] = 0.0;
-        __syncthreads();
+        stage_bn_local(s_bn, s_st, L == 0 ? 4 : 8, invT, A.gamma[L], A.beta[L], tid);
+        __syncthreads();                                          // the partial sums are read: this product's waves may replace them
         const float sc0 = s_bn[c4], sc1 = s_bn[c4 + 1], sc2 = s_bn[c4 + 2], sc3 = s_bn[c4 + 3];
         const float sh0 = s_bn[HD + c4], sh1 = s_bn[HD + c4 + 1], sh2 = s_bn[HD + c4 + 2], sh3 = s_bn[HD + c4 + 3];
         float bias8[8];
@@ -2797,13 +2797,13 @@ __global__ __launch_bounds__(512) void k_gin_inst(GinInstArgs A)
             double a = su[c], bq = sq[c];
             a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
             bq += __shfl_xor(bq, 16); bq += __shfl_xor(bq, 32);
-            if (q == 0) { atomicAdd(&st_out[c * 16 + m], a); atomicAdd(&st_out[HD + c * 16 + m], bq); }
+            if (q == 0) { s_st[wave * 256 + c * 16 + m] = a; s_st[wave * 256 + HD + c * 16 + m] = bq; }     // (a wave without a tile: zeros)
         }
-        __syncthreads();                                          // rows of `out` and st_out complete (vmcnt drained by the barrier)
+        __syncthreads();                                          // rows of `out` and the partial sums complete (vmcnt drained by the barrier)
         const float *tmp = in; in = out; out = const_cast<float *>(tmp);
     }
     // ---- h = relu(bn_outer1(z5)); graph mean pool (gcn:192) and candidate gather (ac:197-207)
-    stage_bn_local(s_bn, s_st + 256, invT, A.gamma[5], A.beta[5], tid);     // five products: the last sums are in buffer 1
+    stage_bn_local(s_bn, s_st, 8, invT, A.gamma[5], A.beta[5], tid);
     __syncthreads();
     {
         const int rg = tid >> 5, cc = (tid & 31) * 4;             // 16 row groups x 4 columns
@@ -2847,16 +2847,13 @@ __global__ __launch_bounds__(512) void k_gat_inst(GatInstArgs A)
     float *s_w = reinterpret_cast<float *>(smem);
     float *s_a = s_w + HD * HD;                                   // 8 tiles
     float *s_bn = s_a + 8 * 16 * LDA16;
-    double *s_st = reinterpret_cast<double *>(s_bn + 2 * HD);     // [256]
-    float *s_pool = reinterpret_cast<float *>(s_st + 512);        // [128]
-    float *s_feat = s_pool + HD;                                  // 8 waves * 16 rows * 8
+    double *s_st = reinterpret_cast<double *>(s_bn + 2 * HD);     // [8][256] partial BatchNorm sums, one row per wave
+    float *s_feat = reinterpret_cast<float *>(s_st + 8 * 256);    // 8 waves * 16 rows * 8
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int j = lane & 31, h = lane >> 5, c4 = j * 4;
     const int m = lane & 15, q = lane >> 4, qo = q & 1;
     const int b = blockIdx.x, M = A.M, N = 2 * M;                 // tile rows of this instance: (machine, node) interleaved
     stage_w16(s_w, A.Wt, tid);
-    if (tid < 256) s_st[tid] = 0.0;
-    if (tid < HD) s_pool[tid] = 0.f;
     __syncthreads();
     float *my_a = s_a + wave * 16 * LDA16;
     float *my_f = s_feat + wave * 128;
@@ -2868,6 +2865,7 @@ __global__ __launch_bounds__(512) void k_gat_inst(GatInstArgs A)
     for (int c = 0; c < 8; c++) { asrc[c] = A.gat_a[c * 16 + m]; adst[c] = A.gat_a[HD + c * 16 + m]; }
     const int t = wave;                                           // 2M <= 128 rows: at most one tile per wave
     const bool active = t * 16 < N;
+    const int nact = (N + 15) / 16;                               // active waves: 0 .. nact-1
     float mv[8][2];                                               // node means of this lane's two machines, 8 column blocks
     for (int c = 0; c < 8; c++) { mv[c][0] = 0.f; mv[c][1] = 0.f; }
     if (active) {
@@ -2944,11 +2942,11 @@ __global__ __launch_bounds__(512) void k_gat_inst(GatInstArgs A)
                 if (t * 16 + 4 * q + 2 * u < N) { a += (double)mv[c][u]; bq += (double)mv[c][u] * (double)mv[c][u]; }
             a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
             bq += __shfl_xor(bq, 16); bq += __shfl_xor(bq, 32);
-            if (q == 0) { atomicAdd(&s_st[c * 16 + m], a); atomicAdd(&s_st[HD + c * 16 + m], bq); }
+            if (q == 0) { s_st[wave * 256 + c * 16 + m] = a; s_st[wave * 256 + HD + c * 16 + m] = bq; }
         }
     }
     __syncthreads();
-    stage_bn_local(s_bn, s_st, 1.0 / (double)M, A.gamma, A.beta, tid);
+    stage_bn_local(s_bn, s_st, nact, 1.0 / (double)M, A.gamma, A.beta, tid);
     __syncthreads();
     if (active) {
         for (int c = 0; c < 8; c++) {
@@ -2963,13 +2961,18 @@ __global__ __launch_bounds__(512) void k_gat_inst(GatInstArgs A)
                 }
             }
             pl += __shfl_xor(pl, 16); pl += __shfl_xor(pl, 32);
-            if (q == 0) atomicAdd(&s_pool[col], pl);
+            if (q == 0) my_a[col] = pl;                           // this wave's share of the pool, in its own tile (free after the last pass)
         }
     }
     __syncthreads();
-    if (tid < HD) A.h_pooled[(size_t)b * HD + tid] = s_pool[tid] / (float)M;
+    if (tid < HD) {
+        float pl = 0.f;
+        for (int w = 0; w < nact; w++) pl += s_a[w * 16 * LDA16 + tid];       // folded in wave order
+        A.h_pooled[(size_t)b * HD + tid] = pl / (float)M;
+    }
 }
-static size_t inst_lds_bytes() { return (size_t)(HD * HD + 8 * 16 * LDA16 + 2 * HD) * 4 + 512 * 8 + (HD + 8 * 128) * 4 + 64; }
+// weights | 8 tiles | BatchNorm scale, shift | [8][256] f64 partial sums | k_gat_inst's feature words
+static size_t inst_lds_bytes() { return (size_t)(HD * HD + 8 * 16 * LDA16 + 2 * HD) * 4 + 8 * 256 * 8 + 8 * 128 * 4 + 64; }
 
 // =================================================================================================
 // host side

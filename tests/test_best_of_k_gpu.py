@@ -15,7 +15,7 @@ from env_parity import _same
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = {"J6M6": (6, 6, 2, 4), "J3M4": (3, 4, 2, 3)}
+SHAPES = {"J6M6": (6, 6, 2, 4), "J3M4": (3, 4, 2, 3), "J3M17": (3, 17, 1, 3)}
 CONFIG_W = (0.4, 0.4, 0.2)
 KEYS = ("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")
 

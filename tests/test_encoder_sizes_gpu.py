@@ -126,8 +126,9 @@ def test_streaming_order_switches_do_not_change_results(monkeypatch):
 @pytest.mark.parametrize("J,M,E,B", [(10, 10, 2, 333), (4, 6, 2, 50), (4, 4, 2, 97), (8, 4, 2, 53), (15, 10, 5, 11)])
 def test_pooling_epilogue_serves_any_candidate(monkeypatch, J, M, E, B):
     """The pooling epilogue of the last streaming product (MTFJSP_FUSE_POOL, default) takes candidate j from job j's block of rows, where the
-    environment's candidates lie; a caller-made candidate elsewhere — another job's row, a row two slots share, a finished job's -1 — goes through
-    k_cand_fixup.  Same forward as the stored-output path on a candidate array with all of those.  Which form pools is the plan's
+    environment's candidates lie; a caller-made candidate elsewhere — another job's row, a row two slots share — goes through
+    k_cand_fixup.  Same forward as the stored-output path on a candidate array with both of those.  (A finished job's -1 is not among them: this
+    test holds no such slot, and none of the gathering kernels is meant to fill one.)  Which form pools is the plan's
     (csrc/mtfjsp_gin_select.h), and the handles report it: the job actor's forward reaches the epilogue and k_cand_fixup only beyond 64 rows per
     instance — T = 100 (J10M10 x 333: a ragged last tile) and T = 150 (J15M10 with 11 instances: a ragged last tile too) against k_job_pool_gather on
     the second handle.  At T = 24 (J4M6), T = 16 (J4M4) and T = 32 (J8M4) BOTH handles pool and gather in the heads launch, which takes the
