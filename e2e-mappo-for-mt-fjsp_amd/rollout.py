@@ -27,7 +27,7 @@ class Rollout:
     def __init__(self, n_job, n_machine, n_edge, batch, device=0, policy="random", obs_dtype="f32",
                  instance_seed=0, rank=0, world=1, weights=None, w3_pool_episodes=32, greedy=False, seed=1234,
                  buffer_episodes=5, gamma=0.99, lam=0.98, collect=True, instances=None, w3_episodes=None, w3="device",
-                 exact_bn=False, global_handoff=True, time_handoff=False):
+                 exact_bn=False, global_handoff=True, time_handoff=False, w_cfg=(0.4, 0.4, 0.2), scaling_divisor=1.0):
         """instances: (t, p, tt, edge) host arrays for THIS shard; default = rows [rank*batch, (rank+1)*batch) of the
         reference generator's `Instance_Dataset(samples=world*batch, seed=instance_seed)` (every
         instance distinct).  w3_episodes: [n,B,3] reward weights to use episode by episode (tests); otherwise w3 = "device"
@@ -37,12 +37,15 @@ class Rollout:
         weights = (job actor, machine actor[, global critic]) state dicts.  With collect="full" and global-critic weights the
         hand-off is the reference's whole one (global_handoff; ppo:628-703).  time_handoff (bench.py): device events around the
         all-gather and a synchronisation to read them — off in production, where the hand-off stays asynchronous.
-        Only rank's own instances are generated when none are passed (generate_instances(first=...))."""
+        Only rank's own instances are generated when none are passed (generate_instances(first=...)).
+        gamma is the discount of the advantages AND of the environment's reward scaler (pe:82: both are args['GAMMA']); w_cfg =
+        (weight_mk, weight_ec, weight_tt) and scaling_divisor are the environment's reward configuration (env:1164)."""
         self.J, self.M, self.E, self.B = n_job, n_machine, n_edge, batch
         self.T = n_job * n_machine
         self.policy = policy
         self.rank, self.world = rank, world
-        self.env = DeviceBatchEnv(n_job, n_machine, n_edge, batch, obs_dtype=obs_dtype, device=device)
+        self.env = DeviceBatchEnv(n_job, n_machine, n_edge, batch, obs_dtype=obs_dtype, device=device, gamma=gamma, w_cfg=w_cfg,
+                                  scaling_divisor=scaling_divisor)
         dev = self.env.device
         if instances is None:
             lo, hi = rank * batch, (rank + 1) * batch               # only this rank's rows are kept (the stream is the whole set's)

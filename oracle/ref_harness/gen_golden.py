@@ -117,12 +117,13 @@ def scaler_state(s):
 
 
 def run_trace(ins, n_job, n_machine, n_edge, B, episodes, policy, left_shift=True,
-              act_seed=0, w_seed=0, keep_every=1):
+              act_seed=0, w_seed=0, keep_every=1, cfg_over=None):
     """Drive the reference exactly like Run.py does, with a scripted policy.  policy="blocks": the mask-free action stream of
     tests/env_parity.py::Actions (a job is kept for a run of steps, else redrawn among the unfinished ones with p = 0.3; all
-    randomness drawn up front), checked here against the reference's own candidate bookkeeping."""
+    randomness drawn up front), checked here against the reference's own candidate bookkeeping.  cfg_over: entries of the
+    reference's configuration other than default_config's (the reward weights, the divisor, GAMMA); they are recorded in cfg_w."""
     J, M, T = n_job, n_machine, n_job * n_machine
-    cfg = default_config(J, M, n_edge, B)
+    cfg = default_config(J, M, n_edge, B, **(cfg_over or {}))
     t_all, p_all, tt_all, edge_all = [np.asarray(x[:B]) for x in ins]
     penv = Parallel_env(cfg)
     batch = {"t": torch.tensor(t_all), "p": torch.tensor(p_all),
@@ -350,6 +351,18 @@ def encoder_vectors(ins, weights, B=16, steps=(0, 17), seed=0, size=(6, 6, 2), k
 TIE_TRACES = {"trace_j6m6e2_int_b8_blocks": (6, 6, 8, 21, 1, 1), "trace_j10m10e2_int_b2_blocks": (10, 10, 2, 22, 2, 5)}
 
 
+def cfg_over(w_mk, w_ec, w_tt, divisor, gamma):
+    """(w_mk, w_ec, w_tt, divisor, gamma) as the reference's configuration entries"""
+    return dict(weight_mk=w_mk, weight_ec=w_ec, weight_tt=w_tt, reward_scaling={"scaling_divisor": divisor}, GAMMA=gamma)
+
+
+# every other trace runs default_config's (0.4, 0.4, 0.2), 1, 0.99.  A: three different weights, a divisor whose reciprocal is not
+# exact, a gamma other than the default.  B: two zero weights, a negative divisor, no discounting of the scaler's return.
+# name: (w_mk, w_ec, w_tt, divisor, gamma), B, generator seed, action seed
+CFG_TRACES = {"trace_j6m6e2_cfgA_b8_blocks": ((0.55, 0.15, 0.30, 7.0, 0.9), 8, 23, 3),
+              "trace_j6m6e2_cfgB_b4_blocks": ((0.0, 1.0, 0.0, -3.0, 1.0), 4, 24, 4)}
+
+
 # ------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -436,6 +449,17 @@ def main():
             t_, p_, tt_, edge_ = ref_generate(b, j, m, 2, gen_seed)
             ins = list(integer_data(t_, p_, tt_)) + [edge_]
             d, _ = run_trace(ins, j, m, 2, b, episodes=1, policy="blocks", act_seed=act_seed, w_seed=act_seed, keep_every=every)
+            save(name, d)
+    if want("cfg"):
+        # J6M6E2, two episodes (the scaler's mean and S carry over the boundary: that is where GAMMA shows), every step kept.
+        # Integer times keep the observations compressible; the scaler's state and the scaled rewards are not (B = 8: 86 KiB)
+        from env_parity import integer_data
+        for name, (cfg5, b, gen_seed, act_seed) in CFG_TRACES.items():
+            t_, p_, tt_, edge_ = ref_generate(b, 6, 6, 2, gen_seed)
+            ins = list(integer_data(t_, p_, tt_)) + [edge_]
+            d, _ = run_trace(ins, 6, 6, 2, b, episodes=2, policy="blocks", act_seed=act_seed, w_seed=act_seed, keep_every=1,
+                             cfg_over=cfg_over(*cfg5))
+            assert np.array_equal(d["cfg_w"], np.array(cfg5, np.float64))
             save(name, d)
     if want("enc"):
         save("encoder_j6m6e2_top1", encoder_vectors(ev, "top1"))

@@ -68,7 +68,7 @@ def select(values, eligible, sigs, W):
     return picks
 
 
-def model_step(data, prefixes, scores, W, column, dedupe, left_shift):
+def model_step(data, prefixes, scores, W, column, dedupe, left_shift, w_cfg=CONFIG_W):
     """prefixes: list [N*W] of lists of (task, mach), None for an empty slot (slot 0 of every instance is never empty); scores [N*W].
     -> dict: parent, from_slot, task, mach [N*W] int32, score [N*W] f64, the next prefixes, and what the pick was made from
     (values, eligible, sigs [N*W*T]; the children's states)"""
@@ -76,7 +76,7 @@ def model_step(data, prefixes, scores, W, column, dedupe, left_shift):
     N, T, M = t.shape
     J, NW, R = T // M, N * W, N * W * T
     src = np.repeat(np.arange(N), W * T)
-    orc = OracleBatch(t[src], p[src], tt[src], edge[src], left_shift=left_shift, w_cfg=CONFIG_W)
+    orc = OracleBatch(t[src], p[src], tt[src], edge[src], left_shift=left_shift, w_cfg=w_cfg)
     orc.scaler_init()
     orc.reset(w3[src])
     live = np.array([x is not None for x in prefixes])
@@ -130,13 +130,13 @@ def start(N, W):
     return prefixes, scores
 
 
-def model_episode(data, W, column, dedupe, left_shift, steps=None):
+def model_episode(data, W, column, dedupe, left_shift, steps=None, w_cfg=CONFIG_W):
     """-> list of the steps' records (model_step's dicts, each with "before": the prefixes and scores it started from)"""
     N, T, _ = data[0].shape
     prefixes, scores = start(N, W)
     recs = []
     for _ in range(T if steps is None else steps):
-        rec = model_step(data, prefixes, scores, W, column, dedupe, left_shift)
+        rec = model_step(data, prefixes, scores, W, column, dedupe, left_shift, w_cfg)
         rec["before"] = (prefixes, scores)
         recs.append(rec)
         prefixes, scores = rec["prefixes"], rec["score"]
@@ -161,12 +161,12 @@ def tie_rich(data, constant=10.0):
 
 
 @functools.lru_cache(maxsize=None)
-def cached_data(J, M, E, N, ties=False):
+def cached_data(J, M, E, N, ties=False, w_cfg=CONFIG_W):
     from importlib import import_module
     import mtfjsp_amd  # noqa: F401
     inst = import_module("e2e-mappo-for-mt-fjsp_amd.instances")
     t, p, tt, edge = inst.generate_instances(N, J, M, E, seed=5300 + J * 100 + M)
-    data = (t, p, tt, np.asarray(edge), np.tile(np.array([CONFIG_W]), (N, 1)))
+    data = (t, p, tt, np.asarray(edge), np.tile(np.array([w_cfg], np.float64), (N, 1)))
     if ties:
         data = tie_rich(data)
     data = tuple(np.ascontiguousarray(x) for x in data)
@@ -176,11 +176,11 @@ def cached_data(J, M, E, N, ties=False):
 
 
 @functools.lru_cache(maxsize=None)
-def cached_episode(J, M, E, N, W, column, dedupe, left_shift, ties=False):
-    """the model's episode on the test instances of a shape, computed once per session and shared; reward weights = CONFIG_W.
-    -> (data, records)"""
-    data = cached_data(J, M, E, N, ties)
-    recs = model_episode(data, W, column, dedupe, left_shift)
+def cached_episode(J, M, E, N, W, column, dedupe, left_shift, ties=False, w_cfg=CONFIG_W):
+    """the model's episode on the test instances of a shape, computed once per session and shared; w_cfg: the configuration's reward
+    weights (w_mk, w_ec, w_tt), which are also every instance's own.  -> (data, records)"""
+    data = cached_data(J, M, E, N, ties, w_cfg)
+    recs = model_episode(data, W, column, dedupe, left_shift, w_cfg=w_cfg)
     for r in recs:
         for v in r.values():
             if isinstance(v, np.ndarray):

@@ -135,17 +135,28 @@ class Actions:
         return job, task, mach
 
 
-def oracle_walk(J, M, E, B, left_shift=True, episodes=1, seed=0, policy="mask", data="generated"):
+def config_kwargs(config):
+    """config = (w_mk, w_ec, w_tt, divisor, gamma) or None (both sides' defaults: 0.4, 0.4, 0.2, 1, 0.99) -> the keywords of
+    DeviceBatchEnv and of OracleBatch"""
+    if config is None:
+        return {}, {}
+    w_mk, w_ec, w_tt, divisor, gamma = (float(x) for x in config)
+    return (dict(w_cfg=(w_mk, w_ec, w_tt), scaling_divisor=divisor, gamma=gamma),
+            dict(w_cfg=(w_mk, w_ec, w_tt), divisor=divisor, gamma=gamma))
+
+
+def oracle_walk(J, M, E, B, left_shift=True, episodes=1, seed=0, policy="mask", data="generated", config=None):
     """the oracle alone over run_parity's instances and actions (no device, no reset_episode): -> dict of paths [episodes, T, B],
-    ties [episodes, B, 3] (OracleBatch.ties at each episode's end) and actions [episodes, T, B, 3] = job, task, machine"""
+    ties [episodes, B, 3] (OracleBatch.ties at each episode's end), actions [episodes, T, B, 3] = job, task, machine, and info
+    [episodes, T, B, 6], raw [episodes, T, B, 5] of every step.  config: config_kwargs"""
     from oracle.env_oracle import OracleBatch
     T = J * M
     t, p, tt, edge = parity_instances(J, M, E, B, seed, data)
     feas = t >= 0
     rs = np.random.RandomState(seed)
-    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift)
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift, **config_kwargs(config)[1])
     orc.scaler_init()
-    paths, ties, actions = [], [], []
+    paths, ties, actions, infos, raws = [], [], [], [], []
     for ep in range(episodes):
         w3 = rs.dirichlet([1, 1, 1], B)
         if ep > 0:
@@ -155,13 +166,14 @@ def oracle_walk(J, M, E, B, left_shift=True, episodes=1, seed=0, policy="mask", 
         act = Actions(policy, rs, J, M, B, feas)
         for s in range(T):
             job, task, mach = act.next(s, cand, mask)
-            info, _, pth = orc.step(task, mach)
+            info, raw, pth = orc.step(task, mach)
             cand, mask = orc.job_mask_update(job)
-            paths.append(pth); actions.append(np.stack([job, task, mach], 1))
+            paths.append(pth); actions.append(np.stack([job, task, mach], 1)); infos.append(info); raws.append(raw)
         assert info[:, 1].all()
         ties.append(orc.ties())
     return dict(paths=np.array(paths).reshape(episodes, T, B), ties=np.array(ties),
-                actions=np.array(actions, np.int32).reshape(episodes, T, B, 3))
+                actions=np.array(actions, np.int32).reshape(episodes, T, B, 3),
+                info=np.array(infos).reshape(episodes, T, B, 6), raw=np.array(raws).reshape(episodes, T, B, 5))
 
 
 def ell_rows(col, val):
@@ -184,14 +196,15 @@ def _same(got, want, what):
 
 
 def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force=None, monkeypatch=None, expect_kernel=None,
-               second_reset="reset", policy="mask", data="generated", adjacency="dense", expect_launch=None):
+               second_reset="reset", policy="mask", data="generated", adjacency="dense", expect_launch=None, config=None):
     """-> number of compared steps.  policy, data: the action stream and the instance times (module docstring).
     force: MTFJSP_ENV_KERNEL for the handle's launches (needs monkeypatch).  expect_kernel: the kernel
     the case is about; asserted against the dispatch.  second_reset: how episodes after the first begin — "reset" (scaler_reset_returns
     + reset with fresh weights) or "reset_episode" (the one-launch form; the weights it draws are fed to the oracle's reset).  Every
     later reset runs over the terminal state of the episode before: it must rewrite every row of a dirty observation buffer.
     adjacency: "dense" or "sparse" (module docstring).  expect_launch: (instances per workgroup[, dynamic LDS bytes]) of the live
-    handle's step launch."""
+    handle's step launch.  config: (w_mk, w_ec, w_tt, divisor, gamma) for the handle and the oracle (config_kwargs); None = the
+    defaults of both."""
     import mtfjsp_amd  # noqa: F401
     batch_env = import_module("e2e-mappo-for-mt-fjsp_amd.batch_env")
     capi = import_module("e2e-mappo-for-mt-fjsp_amd.capi")
@@ -208,6 +221,9 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
     T = J * M
     odt = np.float32 if obs_dtype == "f32" else np.float64
     case = f"J{J}M{M}E{E} B={B} {obs_dtype} force={force} left_shift={left_shift} policy={policy} data={data}"
+    if config is not None:
+        case += f" config={tuple(config)}"
+    env_kw, orc_kw = config_kwargs(config)
 
     def obs(x):                                      # the oracle's f64 observation in the handle's observation type
         return np.asarray(x, np.float64).astype(odt)
@@ -215,14 +231,14 @@ def run_parity(J, M, E, B, obs_dtype, left_shift=True, episodes=1, seed=0, force
     t, p, tt, edge = parity_instances(J, M, E, B, seed, data)
     feas = t >= 0
     rs = np.random.RandomState(seed)
-    env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=left_shift, obs_dtype=obs_dtype)
+    env = batch_env.DeviceBatchEnv(J, M, E, B, left_shift=left_shift, obs_dtype=obs_dtype, **env_kw)
     if expect_kernel is not None:                    # the live handle's own answer: this device's LDS, the switches as set above
         assert env.step_kernel_name() == expect_kernel, (env.step_kernel_name(), expect_kernel)
     if expect_launch is not None:
         assert env.step_launch_info()[:len(expect_launch)] == tuple(expect_launch), (env.step_launch_info(), expect_launch)
     env.load_instances(t, p, tt, edge=edge)
     env.scaler_init()
-    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift)
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift, **orc_kw)
     orc.scaler_init()
 
     sparse = adjacency == "sparse"

@@ -77,8 +77,9 @@ SHARED_MAXIMA = {}                    # cached_episode's arguments -> decisions 
 
 
 @functools.lru_cache(maxsize=None)
-def cached_episode(J, M, E, B, column, left_shift, data="generated"):
-    """the model's episode on the test instances of a shape, computed once per session and shared; reward weights = CONFIG_W.
+def cached_episode(J, M, E, B, column, left_shift, data="generated", w_cfg=CONFIG_W):
+    """the model's episode on the test instances of a shape, computed once per session and shared; w_cfg: the configuration's reward
+    weights (w_mk, w_ec, w_tt), which are also every instance's own (pdrs:675).
     data="integer": the same instances with small-integer times (env_parity.integer_data), where replicas tie"""
     from importlib import import_module
     import mtfjsp_amd  # noqa: F401
@@ -87,10 +88,10 @@ def cached_episode(J, M, E, B, column, left_shift, data="generated"):
     if data == "integer":
         from env_parity import integer_data
         t, p, tt = integer_data(t, p, tt)
-    w3 = np.tile(np.array([CONFIG_W]), (B, 1))
+    w3 = np.tile(np.array([w_cfg], np.float64), (B, 1))
     shared = []
-    task, mach, best = model_episode(t, p, tt, edge, w3, column, left_shift, CONFIG_W, shared)
-    SHARED_MAXIMA[(J, M, E, B, column, left_shift, data)] = sum(shared)
+    task, mach, best = model_episode(t, p, tt, edge, w3, column, left_shift, w_cfg, shared)
+    SHARED_MAXIMA[(J, M, E, B, column, left_shift, data) + (() if w_cfg == CONFIG_W else (w_cfg,))] = sum(shared)
     for x in (t, p, tt, edge, w3, task, mach, best):
         x.setflags(write=False)
     return (t, p, tt, edge, w3), task, mach, best

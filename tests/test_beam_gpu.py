@@ -203,6 +203,50 @@ def test_beam_baselines_equal_the_oracle_driven_by_the_models_plans():
         _same(one[baselines.PLANS][name][0], task, f"{name} plan: tasks, chunk=1"); _same(one[baselines.PLANS][name][1], mach, f"{name} plan: machines, chunk=1")
 
 
+def test_beam_and_scratch_handles_inherit_reward_weights_off_the_default():
+    """BS_R (raw[0], the weighted total) at W = 2 with the configuration's weights at (0.55, 0.15, 0.30), divisor 1 (the host model
+    takes none), on the smallest shape of this file: the children are stepped by the scratch handle and the winners live in the beam
+    handle, which must both have taken their source's weights (baselines.BeamSearch)"""
+    from oracle.env_oracle import OracleBatch
+    _, baselines, _ = _mods()
+    J, M, E, N = CASES["J3M3_W3"][:4]
+    T, W, W_A, left_shift = J * M, 2, (0.55, 0.15, 0.30), True
+    assert min(v[0] * v[1] for v in CASES.values()) == T
+    args = dict(n_job=J, n_machine=M, n_edge=E, weight_mk=W_A[0], weight_ec=W_A[1], weight_tt=W_A[2])
+    (t, p, tt, edge, w3), recs = ref.cached_episode(J, M, E, N, W, 0, True, left_shift, False, W_A)
+    _same(w3, np.tile(np.array([W_A]), (N, 1)), "the model's weights")
+    _, default = ref.cached_episode(J, M, E, N, W, 0, True, left_shift, False)
+    assert not np.array_equal(_bits(default[-1]["score"]), _bits(recs[-1]["score"])), "the weights must change the model's scores"
+    res = baselines.beam_baselines(t, p, tt, edge, args, rules=[("BS_R", 0)], width=W, left_shift=left_shift)
+    task, mach = ref.plan_arrays(recs[-1]["prefixes"], T)
+    task, mach = np.ascontiguousarray(task[::W]), np.ascontiguousarray(mach[::W])
+    _same(res[baselines.PLANS]["BS_R"][0], task, "BS_R plan: tasks"); _same(res[baselines.PLANS]["BS_R"][1], mach, "BS_R plan: machines")
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift, w_cfg=W_A); orc.scaler_init(); orc.reset(w3)
+    cum, total = np.zeros((N, 5)), np.zeros(N)
+    for s in range(T):
+        raw = orc.step(task[:, s], mach[:, s])[1]
+        cum += raw
+        total = total + raw[:, 0]
+    _same(_bits(total), _bits(recs[-1]["score"][::W]), "the best plan's running sum is the model's best score (bits)")
+    prev = orc.state()["prev"]
+    cost, final4, obj = res["BS_R"]
+    for k, key in enumerate(("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")):
+        _same(cost[key], cum[:, k], f"BS_R {key}")
+    want4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
+    _same(final4, want4, "BS_R Final_4cost")
+    _same(obj, W_A[0] * want4[:, 0] + W_A[1] * (want4[:, 1] + want4[:, 3]) + W_A[2] * want4[:, 2], "BS_R Objective")
+    # the device's own scores, every slot at every step, through the class the baseline drives
+    batch_env = _mods()[0]
+    env = batch_env.DeviceBatchEnv(J, M, E, N, left_shift=left_shift, obs_dtype="f32", w_cfg=W_A)
+    env.load_instances(t, p, tt, edge=edge); env.scaler_init(); env.reset(w3)
+    bs = baselines.BeamSearch(env, W)
+    assert bs.beam.w_cfg == W_A and bs.scratch.w_cfg == W_A
+    for s in range(T):
+        assert bs.advance(0) == s
+        _check_row(bs, s, recs[s], f"weights {W_A} step {s}")
+    bs.close(); env.close()
+
+
 def test_argument_errors_write_nothing():
     batch_env, baselines, capi = _mods()
     J, M, E, N, W, _, left_shift = CASES["J3M3_W3"]

@@ -31,7 +31,9 @@ def test_hip_env_bit_exact_on_reference_trace(name):
     assert n > 0
 
 
-@pytest.mark.parametrize("name", ["trace_j6m6e2_eval16_free", "trace_j10m10e2_b2_free"])
+@pytest.mark.parametrize("name", ["trace_j6m6e2_eval16_free", "trace_j10m10e2_b2_free",
+                                  # reward weights, divisor and gamma off their defaults (trace_utils.TRACES)
+                                  "trace_j6m6e2_cfgA_b8_blocks", "trace_j6m6e2_cfgB_b4_blocks"])
 def test_hip_env_f32_observations_are_the_rounded_f64_ones(name):
     """obs_dtype=f32 must be exactly float32(reference f64 observation) — what actor_critic.py:143 `.float()` does.
     State, rewards and masks stay f64/int and bit-exact."""

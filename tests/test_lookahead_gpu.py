@@ -126,6 +126,38 @@ def test_lookahead_baselines_equal_the_oracle_driven_by_the_models_plans(left_sh
         _same(final4, np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1), f"{name} Final_4cost")
 
 
+def test_the_scratch_handle_inherits_reward_weights_off_the_default():
+    """LA_R (raw[0], the weighted total) with the configuration's weights at (0.55, 0.15, 0.30), divisor 1 (the host model takes
+    none), on the smallest shape of this file: the B*T copies are stepped by the SCRATCH handle, which must have taken its source's
+    weights (baselines.Lookahead) — with the default (0.4, 0.4, 0.2) its totals, and with them the plan, are others"""
+    from oracle.env_oracle import OracleBatch
+    _, baselines, _ = _mods()
+    J, M, E, B = SHAPES["J3M4"]
+    T, W_A, left_shift = J * M, (0.55, 0.15, 0.30), True
+    assert min(v[0] * v[1] for v in SHAPES.values()) == T
+    args = dict(n_job=J, n_machine=M, n_edge=E, weight_mk=W_A[0], weight_ec=W_A[1], weight_tt=W_A[2])
+    (t, p, tt, edge, w3), task, mach, best = ref.cached_episode(J, M, E, B, 0, left_shift, w_cfg=W_A)
+    _same(w3, np.tile(np.array([W_A]), (B, 1)), "the model's weights")
+    default = ref.cached_episode(J, M, E, B, 0, left_shift)
+    assert not (np.array_equal(default[1], task) and np.array_equal(default[2], mach)), "the weights must change the model's plan"
+    res = baselines.lookahead_baselines(t, p, tt, edge, args, rules=[("LA_R", 0)], left_shift=left_shift)
+    _same(res[baselines.PLANS]["LA_R"][0], np.ascontiguousarray(task.T), "LA_R plan: tasks")
+    _same(res[baselines.PLANS]["LA_R"][1], np.ascontiguousarray(mach.T), "LA_R plan: machines")
+    orc = OracleBatch(t, p, tt, edge, left_shift=left_shift, w_cfg=W_A); orc.scaler_init(); orc.reset(w3)
+    cum = np.zeros((B, 5))
+    for s in range(T):
+        raw = orc.step(task[s], mach[s])[1]
+        _same(raw[:, 0].view(np.int64), best[s].view(np.int64), f"step {s}: the model's promised value (bits)")
+        cum += raw
+    prev = orc.state()["prev"]
+    cost, final4, obj = res["LA_R"]
+    for k, key in enumerate(("opr_Gt", "opr_mk", "opr_idleT", "opr_pt", "opr_transT")):
+        _same(cost[key], cum[:, k], f"LA_R {key}")
+    want4 = np.stack([prev[:, 0], prev[:, 1] / T, prev[:, 2], prev[:, 3]], 1)
+    _same(final4, want4, "LA_R Final_4cost")
+    _same(obj, W_A[0] * want4[:, 0] + W_A[1] * (want4[:, 1] + want4[:, 3]) + W_A[2] * want4[:, 2], "LA_R Objective")
+
+
 # ---- the other bands of the LDS step kernel (J5M12 takes groups of 8 by default) and J > 64
 BANDS = [("MTFJSP_ENV_STEP_G", "4", "k_env_step_grp", 4), ("MTFJSP_ENV_STEP_G", "2", "k_env_step_grp", 2), ("MTFJSP_ENV_KERNEL", "lds1", "k_env_step", 1)]
 

@@ -45,18 +45,37 @@ def _esa_mask_from_proxies(penv, J, M):
 
 
 def test_parallel_env_mirror_replays_run_py_loop():
+    _replay_run_py_loop("trace_j6m6e2_train16_mask", 0)  # the fixture was generated with random.seed(0) (gen_golden.py: w_seed=0)
+
+
+def test_parallel_env_mirror_takes_weights_divisor_and_gamma_from_its_arguments():
+    """the same loop on the trace recorded under (0.55, 0.15, 0.30), divisor 7, GAMMA 0.9: the mirror is built from the trace's own
+    cfg_w — args['weight_*'], args['reward_scaling'] and args['GAMMA'], which the reference hands to its environments (pe:111) and
+    to its RewardScaling (pe:82) — and held to the recorded rewards and scaler state"""
+    g = load("trace_j6m6e2_cfgA_b8_blocks")
+    assert tuple(g["cfg_w"]) == (0.55, 0.15, 0.30, 7.0, 0.9)
+    _replay_run_py_loop("trace_j6m6e2_cfgA_b8_blocks", 3)  # gen_golden.py CFG_TRACES: w_seed = the action seed, 3
+
+
+def _replay_run_py_loop(name, w_seed):
     import torch
     import mtfjsp_amd  # noqa: F401
     pe = import_module("e2e-mappo-for-mt-fjsp_amd.parallel_env")
-    g = load("trace_j6m6e2_train16_mask")
-    J, M, E, B, episodes, left_shift, _ = [int(x) for x in g["meta"]]
+    capi = import_module("e2e-mappo-for-mt-fjsp_amd.capi")
+    g = load(name)
+    J, M, E, B, episodes, left_shift, keep_every = [int(x) for x in g["meta"]]
     T = J * M
-    penv = pe.Parallel_env(_args(J, M, E, B))
+    assert keep_every == 1 and left_shift == 1
+    w_mk, w_ec, w_tt, divisor, gamma = (float(x) for x in g["cfg_w"])
+    args = dict(_args(J, M, E, B), weight_mk=w_mk, weight_ec=w_ec, weight_tt=w_tt, reward_scaling={"scaling_divisor": divisor}, GAMMA=gamma)
+    if name == "trace_j6m6e2_train16_mask":
+        assert args == _args(J, M, E, B)
+    penv = pe.Parallel_env(args)
     assert penv.batch_size == B
     penv.get_batch({"t": torch.tensor(g["t"]), "p": torch.tensor(g["p"]), "transT": torch.tensor(g["tt"]), "edge": torch.tensor(g["edge"])})
     assert len(penv.ability_instance) == B and np.array_equal(penv.ability_instance[3][0], g["t"][3])
     penv.init_RewardScaling_sameBATCH(shape=4)
-    random.seed(0)                                      # the fixture was generated with random.seed(0) (gen_golden.py: w_seed=0)
+    random.seed(w_seed)
     feas = g["t"] >= 0
     for ep in range(episodes):
         adj, mfea2, tfea = penv.init_DGFJSPEnv_state0()
@@ -75,6 +94,8 @@ def test_parallel_env_mirror_replays_run_py_loop():
             adj, info, mfea2, tfea = penv.DGFJSPEnv_paral_step(joint)
             assert isinstance(info, list) and len(info) == B and len(info[0]) == 6 and isinstance(info[0][1], bool)
             assert np.array_equal(np.array([[float(x) for x in r] for r in info]), g["info"][ep, step])
+            assert np.array_equal(penv._dev.raw.cpu().numpy(), g["raw_rewards"][ep, step])
+            assert np.array_equal(penv._dev.read_state(capi.STATE_SCALER), g["scaler"][ep, step])
             assert np.array_equal(adj, g["adj"][ep, step]) and np.array_equal(tfea, g["tfea"][ep, step])
             assert np.array_equal(mfea2, g["mfea2"][ep, step])
             # the proxies the unmodified PPO code reads

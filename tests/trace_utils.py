@@ -12,7 +12,10 @@ TRACES = ["trace_j6m6e2_train16_mask", "trace_j6m6e2_eval16_free", "trace_j6m6e2
           # integer times, mask-free "blocks" actions: exact ties at the three comparisons that choose the scheduling path
           "trace_j6m6e2_int_b8_blocks", "trace_j10m10e2_int_b2_blocks",
           # beyond J20M20: more than 64 jobs, a pairwise energy sum of 8 leaves (T = 560), 64 machines
-          "trace_j65m2e1_b1_free", "trace_j70m8e2_b1_free", "trace_j4m64e4_b1_free"]
+          "trace_j65m2e1_b1_free", "trace_j70m8e2_b1_free", "trace_j4m64e4_b1_free",
+          # reward weights, divisor and gamma off their defaults (every trace above: 0.4, 0.4, 0.2, 1, 0.99), two episodes each:
+          # A = (0.55, 0.15, 0.30, 7, 0.9), B = (0, 1, 0, -3, 1)
+          "trace_j6m6e2_cfgA_b8_blocks", "trace_j6m6e2_cfgB_b4_blocks"]
 
 
 def load(name):
