@@ -518,3 +518,110 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
     out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
     out.update(start_obj=r["start_obj"], history=r["history"].reshape(G, N))
     return out
+
+
+# ---- Pareto-front evolutionary search (csrc/mtfjsp_nsga.hip): parents and children ranked into fronts, the first P survive
+def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.8, p_mut=0.3, moves=ALL_MOVES, left_shift=False,
+                  chunk=None, device=0, obs_dtype="f32", name="NSGA"):
+    """`evolve` without collapsing the three objectives before it selects: an NSGA-II style search that returns one Pareto front of
+    schedules in (makespan, energy + idle, transport) per instance.  `start`, the P-member generation 0 (member c = start[c % S]), the
+    thresholds round(p * 2**32) and the draws keyed by (seed, instance, child, g) are `evolve`'s; 8 <= P <= 1024.
+    Generation 0: the P-copy handle replays the population, `DeviceBatchEnv.front_rank` ranks it and `plan_survivors` stores it in
+    selection order with fit = the position.  Every later generation g = 1..generations: `plan_offspring(P, pop, fit, None, ...)` — a
+    binary tournament on the position is NSGA-II's crowded comparison: lower front first, then larger crowding distance — into a second
+    buffer; reset, T steps, final_costs of the children; `front_rank` over parents and children together (K = 2P); `plan_survivors`
+    keeps the first P of the order in a third buffer, and the three take turns: T + 5 launches, no torch kernel, nothing read back
+    before the last generation.  Selection (include/mtfjsp.h has the rule): fronts by peeling, inside a front the larger crowding
+    distance, and — the one addition to the textbook rule — the member of a front with its smallest Objective counts as +inf, so at
+    most seven members of front 0 carry +inf and with P >= 8 and weights that are not negative the smallest Objective always survives:
+    the best Objective never rises and is never above the best start's.  Ties go to the lower index; of exact duplicates the lowest
+    index keeps its front and the others fall to later ones; there is no archive across generations.  The results do not depend on
+    `chunk`.  After the last generation one `group_reduce` over the survivors gives the best-Objective member, which is replayed on
+    an n-instance handle as `evolve` replays its best plan (RuntimeError where no member is a valid plan), and the population's
+    plans, costs and ranks are read back once.
+    -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout and PLANS {name: (task[N,T], mach[N,T])} for the
+       best-Objective member; "start_obj" [N]: the best start's Objective; "history" [generations, N]: the best Objective among
+       parents and children of every generation; "front_size" [generations + 1, N] int32: the members of front 0 among the ranked
+       candidates of every generation (generation 0 included); "fronts": a list of N dicts {"cost" [F,3] (mk, ec, tt), "final4"
+       [F,4], "obj" [F], "task" [F,T], "mach" [F,T]}: the front-0 survivors in selection order."""
+    N, T = CopyGroups.sizes(t, args)
+    P, G, moves = int(P), int(generations), int(moves)
+    if not 8 <= P <= 1024:
+        raise ValueError("P must be 8..1024 (the best Objective is only sure to survive among 8 or more)")
+    if G < 0 or not 1 <= moves <= ALL_MOVES:
+        raise ValueError("generations must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN")
+    if not (0.0 <= float(p_cross) <= 1.0 and 0.0 <= float(p_mut) <= 1.0):
+        raise ValueError("p_cross and p_mut must be probabilities")
+    cross_thr, mut_thr = int(round(float(p_cross) * 2 ** 32)), int(round(float(p_mut) * 2 ** 32))
+    _rule_names([(name,), ("start_obj",), ("history",), ("front_size",), ("fronts",)])
+    starts = [start] if len(start) == 2 and np.ndim(start[0]) == 2 else list(start)
+    starts = [(np.ascontiguousarray(s[0], np.int32), np.ascontiguousarray(s[1], np.int32)) for s in starts]
+    if not 1 <= len(starts) <= P or any(s[0].shape != (N, T) or s[1].shape != (N, T) for s in starts):
+        raise ValueError("start must be (task [N,T], mach [N,T]) or a list of 1..P of them")
+    member = np.arange(P) % len(starts)
+    pop_task = np.stack([s[0] for s in starts], 1)[:, member]          # [N,P,T]: member c = start c % S
+    pop_mach = np.stack([s[1] for s in starts], 1)[:, member]
+    fronts = []
+    with CopyGroups(t, p, tt, edge, args, P, chunk, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
+        n, dev, env = g.n, g.dev, g.env
+        B = n * P
+        plans = list(g.bufs) + [tuple(torch.empty(T, B, dtype=torch.int32, device=dev) for _ in range(2))]
+        # three slots (task, mach, cost4, done) that take turns as parents, children and survivors
+        slots = [pl + (torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)) for pl in plans]
+        rank, order = torch.empty(2 * B, dtype=torch.int32, device=dev), torch.empty(2 * B, dtype=torch.int32, device=dev)
+        fit, pop_rank = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+        size = torch.empty(G + 1, n, dtype=torch.int32, device=dev)
+        hist = torch.empty(G + 1, n, dtype=torch.float64, device=dev)
+        obj, best = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        for lo, m in g.passes():
+            pop, child, spare = slots
+            pop[0].copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_task).reshape(B, T).T)))      # [T,n*P]: row s = the actions of step s
+            pop[1].copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_mach).reshape(B, T).T)))
+            g.replay(*pop)
+            env.front_rank(n, pop[2], pop[3], None, None, g.w, rank[:B], False, order[:B], size[0], hist[0])
+            env.plan_survivors(P, order[:B], rank[:B], pop, None, child[0], child[1], child[2], child[3], pop_rank, False, fit)
+            pop, child = child, pop
+            for gen in range(1, G + 1):
+                env.plan_offspring(P, pop[0], pop[1], fit, None, seed, gen, lo, cross_thr, mut_thr, moves, child[0], child[1], False, False)
+                g.replay(*child)
+                env.front_rank(n, pop[2], pop[3], child[2], child[3], g.w, rank, False, order, size[gen], hist[gen])
+                env.plan_survivors(P, order, rank, pop, child, spare[0], spare[1], spare[2], spare[3], pop_rank, False, fit)
+                pop, child, spare = spare, pop, child
+            env.group_reduce(n, P, pop[2], pop[3], g.w, obj=obj, best=best, best_obj=False, front=False)
+            g.finish(pop[0], pop[1], best, f"{name} evolve_pareto", start_obj=hist[0], history=hist[1:], front_size=size)
+            h_task, h_mach = pop[0][:, :m * P].t().cpu().numpy(), pop[1][:, :m * P].t().cpu().numpy()   # the population, read back once
+            h_c4, h_obj, h_rank = pop[2][:m * P].cpu().numpy(), obj[:m * P].cpu().numpy(), pop_rank[:m * P].cpu().numpy()
+            for i in range(m):
+                sel = np.flatnonzero(h_rank[i * P:(i + 1) * P] == 0) + i * P
+                f4 = h_c4[sel]
+                fronts.append({"cost": np.stack([f4[:, 0], f4[:, 1] + f4[:, 3], f4[:, 2]], 1), "final4": f4, "obj": h_obj[sel],
+                               "task": np.ascontiguousarray(h_task[sel]), "mach": np.ascontiguousarray(h_mach[sel])})
+    r = g.collect(last_axis=("history", "front_size"))
+    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
+    out.update(start_obj=r["start_obj"], history=r["history"].reshape(G, N), front_size=r["front_size"].reshape(G + 1, N), fronts=fronts)
+    return out
+
+
+def hypervolume(points, ref):
+    """The volume that `points` [F,3] dominate below the reference point `ref` [3], all three axes minimised — one number per front
+    (`evolve_pareto`'s "cost").  Exact slicing on the host: along the first axis the space falls into slabs between consecutive
+    coordinates, and a slab's cross-section is the area the points met so far dominate in the other two axes, a staircase.
+    Points that are not strictly below `ref` on every axis contribute nothing; dominated points and duplicates are harmless."""
+    pts = np.asarray(points, np.float64).reshape(-1, 3)
+    ref = np.asarray(ref, np.float64).reshape(3)
+    pts = pts[(pts < ref).all(1)]
+    if not len(pts):
+        return 0.0
+    pts = pts[np.argsort(pts[:, 0], kind="stable")]
+    vol = 0.0
+    for i in range(len(pts)):
+        depth = (pts[i + 1, 0] if i + 1 < len(pts) else ref[0]) - pts[i, 0]
+        if depth <= 0.0:
+            continue
+        area, low = 0.0, ref[2]                                         # the staircase of pts[:i + 1] in axes 1 and 2
+        for y, z in sorted(map(tuple, pts[:i + 1, 1:])):
+            if z < low:
+                area += (ref[1] - y) * (low - z)
+                low = z
+        vol += depth * area
+    return float(vol)

@@ -264,6 +264,83 @@ class DeviceBatchEnv:
                                                 task_out.data_ptr(), mach_out.data_ptr(), _ptr(parent_out), _ptr(kind_out)), self.h)
         return task_out, mach_out, parent_out, kind_out
 
+    # ---- multi-front selection (csrc/mtfjsp_nsga.hip): front ranks and survivors of parents and children together
+    def front_rank(self, N, cost4_a, done_a, cost4_b=None, done_b=None, w_cfg=None, rank=True, crowd=True, order=True, front_size=True,
+                   best_obj=True):
+        """N groups of K = Ka + Kb candidates in two array sets (parents and children need no concatenation): candidate c < Ka of
+        group n = element n*Ka + c of cost4_a [N*Ka,4] f64 and done_a [N*Ka] uint8, candidate c >= Ka = element n*Kb + (c - Ka) of
+        cost4_b, done_b (None: Kb = 0).  Device tensors from any source; this handle gives the device and the stream only.  w_cfg =
+        (w_mk, w_ec, w_tt), None: the handle's.  Objectives, eligibility and dominance are `group_reduce`'s.
+        -> (rank [N*K] int32: the front index by peeling — rank 0 = `group_reduce`'s front, then the front of the rest, ...; -1 where
+                not eligible;
+            crowd [N*K] f64: the crowding distance inside the candidate's rank, +inf at the ends of an axis and for the member with
+                the rank's smallest obj, NaN where not eligible;
+            order [N*K] int32: the group's candidates in selection order (eligible first, ascending rank, descending crowd with NaN
+                last, ascending index), order[n*K + i] = the local index c of the i-th;
+            front_size [N] int32: the members of rank 0;  best_obj [N] f64: the smallest obj, NaN without an eligible candidate)
+        device tensors — include/mtfjsp.h has the rule; an output switched off (False) is None and is not computed, an output may also
+        be given as a tensor to write into.  1 <= K <= 2048.  One launch (mtfjsp_front_rank), nothing read back."""
+        N, dev = int(N), self.device
+        assert cost4_a.is_cuda and cost4_a.dtype == torch.float64 and cost4_a.is_contiguous() and N >= 1 and cost4_a.numel() % (4 * N) == 0
+        Ka = cost4_a.numel() // (4 * N)
+        assert done_a.is_cuda and done_a.dtype == torch.uint8 and done_a.is_contiguous() and done_a.numel() == N * Ka
+        Kb = 0
+        if cost4_b is not None:
+            assert cost4_b.is_cuda and cost4_b.dtype == torch.float64 and cost4_b.is_contiguous() and cost4_b.numel() % (4 * N) == 0
+            Kb = cost4_b.numel() // (4 * N)
+            assert done_b is not None and done_b.is_cuda and done_b.dtype == torch.uint8 and done_b.is_contiguous() and done_b.numel() == N * Kb
+        NK = N * (Ka + Kb)
+        # (an out-of-range K is the library's MTFJSP_ERR_ARG; the buffers below are then never written)
+        rank, crowd, order = _out(rank, NK, torch.int32, dev), _out(crowd, NK, torch.float64, dev), _out(order, NK, torch.int32, dev)
+        front_size, best_obj = _out(front_size, N, torch.int32, dev), _out(best_obj, N, torch.float64, dev)
+        w = (C.c_double * 3)(*[float(x) for x in (self.w_cfg if w_cfg is None else w_cfg)])
+        capi.check(self.L.mtfjsp_front_rank(self.h, N, Ka, Kb, cost4_a.data_ptr(), done_a.data_ptr(), _ptr(cost4_b if Kb else None),
+                                            _ptr(done_b if Kb else None), w, _ptr(rank), _ptr(crowd), _ptr(order), _ptr(front_size),
+                                            _ptr(best_obj)), self.h)
+        return rank, crowd, order, front_size, best_obj
+
+    def plan_survivors(self, P, order, rank, a, b=None, task_out=None, mach_out=None, cost4_out=True, done_out=True, rank_out=True,
+                       src_out=True, fit_out=True):
+        """This handle holds N populations of P plans (batch = N*P).  a = (task [T, N*Ka], mach [T, N*Ka], cost4 [N*Ka,4], done [N*Ka]),
+        b the same with Kb or None: the candidates `front_rank` ranked, plans in history layout; order, rank [N*K] int32: its
+        outputs; 1 <= P <= K = Ka + Kb.  Column n*P + i of the outputs takes candidate c = order[n*K + i]:
+        -> (task [T, N*P], mach [T, N*P] int32, cost4 [N*P,4] f64, done [N*P] uint8, rank [N*P] int32: the survivor's rank,
+            src [N*P] int32: c, fit [N*P] f64: float(i) for an eligible survivor, NaN otherwise)
+        device tensors.  The population is stored in selection order, so `plan_offspring` with src_obj = fit and no src_best runs
+        the crowded tournaments of NSGA-II.  An order entry outside [0, K) gives a column of -1 with done 0.  task_out / mach_out:
+        tensors to write into; the others True, a tensor, or None / False.  No output may overlap an input or another output.
+        One launch (mtfjsp_plan_survivors), nothing read back."""
+        P, T, B, dev = int(P), self.T, self.B, self.device
+        assert P >= 1 and B % P == 0
+        N = B // P
+        K = []
+        for s in (a, b):
+            if s is None:
+                K.append(0)
+                continue
+            tk, mc, c4, dn = s
+            assert tk.is_cuda and tk.dtype == torch.int32 and tk.is_contiguous() and tk.dim() == 2 and tk.shape[0] == T and tk.shape[1] % N == 0
+            k = tk.shape[1] // N
+            assert mc.is_cuda and mc.dtype == torch.int32 and mc.is_contiguous() and mc.shape == tk.shape
+            assert c4.is_cuda and c4.dtype == torch.float64 and c4.is_contiguous() and c4.numel() == N * k * 4
+            assert dn.is_cuda and dn.dtype == torch.uint8 and dn.is_contiguous() and dn.numel() == N * k
+            K.append(k)
+        Ka, Kb = K
+        for x in (order, rank):
+            assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and x.numel() == N * (Ka + Kb)
+        task_out = torch.empty(T, B, dtype=torch.int32, device=dev) if task_out is None else task_out
+        mach_out = torch.empty(T, B, dtype=torch.int32, device=dev) if mach_out is None else mach_out
+        for x in (task_out, mach_out):
+            assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and tuple(x.shape) == (T, B)
+        cost4_out, done_out = _out(cost4_out, (B, 4), torch.float64, dev), _out(done_out, (B,), torch.uint8, dev)
+        rank_out, src_out, fit_out = _out(rank_out, (B,), torch.int32, dev), _out(src_out, (B,), torch.int32, dev), _out(fit_out, (B,), torch.float64, dev)
+        self._plan_keep = (order, rank, a, b)                           # alive until the launch has run
+        srcs = [_ptr(x) for x in a] + [_ptr(x) for x in (b if Kb else (None,) * 4)]
+        capi.check(self.L.mtfjsp_plan_survivors(self.h, N, Ka, Kb, P, order.data_ptr(), rank.data_ptr(), *srcs, task_out.data_ptr(),
+                                                mach_out.data_ptr(), _ptr(cost4_out), _ptr(done_out), _ptr(rank_out), _ptr(src_out),
+                                                _ptr(fit_out)), self.h)
+        return task_out, mach_out, cost4_out, done_out, rank_out, src_out, fit_out
+
     def critical_path(self, col=None, n=None, task_out=None, arc_out=None, len_out=None):
         """One critical path per row out of this handle's schedules as they stand (mtfjsp_critical_path: one launch, nothing read
         back).  col: int32 device tensor [n] — row i describes instance col[i]; an entry outside [0, B) gives an empty row — or None:

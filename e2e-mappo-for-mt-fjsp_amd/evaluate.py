@@ -116,7 +116,7 @@ def validate_cost_batched(weights, t, p, tt, edge, args, greedy=True, device=0, 
 
 
 class CopyGroups:
-    """What every search over groups of copies is built on (`best_of_k_rollout`, `baselines.local_search`, `baselines.evolve`): N
+    """What every search over groups of copies is built on (`best_of_k_rollout`, `baselines.local_search`, `baselines.evolve`, `baselines.evolve_pareto`): N
     instances, n = chunk or N of them per pass, K copies of each side by side.  Three handles: `src` with the N loaded instances, `env`
     with the n*K copies (copy c of group i = element i*K + c; None with copies=False) and `top` with n, for the best copy of every
     group; per pass both take their constants from `src` by the explicit-index fork.  The constructor validates `chunk` and builds the
@@ -124,7 +124,7 @@ class CopyGroups:
     w3 [K,3]: copy c of every group resets with w3[c]); leaving the `with` block closes the handles.  `passes()` iterates; `host`,
     `parts` and `collect()` gather the per-pass results.  `sizes(t, args)` gives N and T before anything is built.
     For searches on plans (plans=True; [T, n*K] int32 histories, row s = the actions of step s): `plan_bufs(i)` are two pairs of them
-    that take turns, `round()` replays one on the copies and reduces the groups, `finish()` replays every group's best plan on `top`."""
+    that take turns, `round()` replays one on the copies (`replay()`) and reduces the groups, `finish()` replays every group's best plan on `top`."""
 
     @staticmethod
     def sizes(t, args):
@@ -204,12 +204,17 @@ class CopyGroups:
     def round(self, task, mach, obj, best, best_obj):
         """the copies replay the plans (task, mach) and every group is reduced into the tensors given (obj may be False): reset, T steps,
         final_costs, group_reduce — T + 3 launches, no torch kernel, nothing read back"""
+        self.replay(task, mach, self.cost4, self.done)
+        self.env.group_reduce(self.n, self.K, self.cost4, self.done, self.w, obj=obj, best=best, best_obj=best_obj, front=False)
+
+    def replay(self, task, mach, cost4, done):
+        """the copies replay the plans (task, mach), their final costs into the tensors given: reset, T steps, final_costs — T + 2
+        launches, no torch kernel, nothing read back"""
         env = self.env
         env.reset(self.w3_all)
         for s in range(self.T):
             env.step(task[s], mach[s])
-        env.final_costs(self.cost4, self.done)                          # a rejected action leaves done = 0: the copy is not eligible
-        env.group_reduce(self.n, self.K, self.cost4, self.done, self.w, obj=obj, best=best, best_obj=best_obj, front=False)
+        env.final_costs(cost4, done)                                    # a rejected action leaves done = 0: the copy is not eligible
 
     def finish(self, task, mach, col, what, **extra):
         """the pass's result: column col[i] of (task, mach) for group i — its copy 0 where col[i] < 0, a group without an eligible copy,

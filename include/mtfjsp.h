@@ -463,6 +463,73 @@ int mtfjsp_plan_offspring(mtfjsp_handle_t h, int32_t P, const int32_t *src_task,
                           const int32_t *src_best, uint64_t seed, uint64_t generation, uint64_t first_instance, uint64_t cross_thr,
                           uint64_t mut_thr, uint32_t moves, int32_t *task_out, int32_t *mach_out, int32_t *parent_out, int8_t *kind_out);
 
+/* ------------------------------------------------------------------ Pareto-front evolutionary search: front ranks, survivors */
+/* Multi-front (NSGA-II style) selection over the same machinery: the three objectives are not collapsed before selecting.  Parents
+ * and children of an instance are ranked together into fronts, a crowding distance orders the members of one front, and the first P
+ * of that order are the next population ((mu + lambda) survival).  The survivors are stored in selection order, so the position of
+ * a member IS its fitness: mtfjsp_plan_offspring with src_obj = fit_out and src_best = NULL runs NSGA-II's crowded tournaments as
+ * it stands.  A generation: mtfjsp_plan_offspring, mtfjsp_reset, T x mtfjsp_step, mtfjsp_final_costs, mtfjsp_front_rank,
+ * mtfjsp_plan_survivors — T + 5 launches, nothing read back.  The reference has no counterpart.
+ *
+ * Both calls see N groups of K = Ka + Kb candidates in two array sets, so that parents (a) and children (b) need no concatenation:
+ * candidate c < Ka of group n is element n*Ka + c of the a arrays, candidate c >= Ka element n*Kb + (c - Ka) of the b arrays.
+ * Kb = 0: the b arrays are not read and may be NULL; with Kb > 0 they are required.
+ *
+ * mtfjsp_front_rank: h gives the device and the stream only.  cost4_a [N*Ka,4], done_a [N*Ka], cost4_b [N*Kb,4], done_b [N*Kb]:
+ * device arrays as mtfjsp_final_costs writes them; w3cfg_host as for mtfjsp_group_reduce.  Per candidate, exactly as
+ * mtfjsp_group_reduce forms them: mk = cost4[0], ec = cost4[1] + cost4[3], tt = cost4[2], obj = (w_mk*mk + w_ec*ec) + w_tt*tt,
+ * uncontracted; ELIGIBLE iff done != 0 and none of mk, ec, tt is NaN; c' DOMINATES c iff both are eligible, mk' <= mk && ec' <= ec
+ * && tt' <= tt and (one of the three strictly smaller, or all three equal and c' < c).  Outputs (device; each may be NULL):
+ *   rank_out [N*K] int32      the front index by peeling: rank r holds the eligible candidates not yet ranked that no eligible
+ *                             unranked candidate dominates; then r + 1, and so on.  -1 for an ineligible candidate.  Rank 0 is
+ *                             front_out of mtfjsp_group_reduce on the same data; of exact duplicates the lowest index has the
+ *                             lowest rank and every further one falls one rank
+ *   crowd_out [N*K] binary64  the crowding distance among the members of the candidate's own rank.  Per axis x in the order mk, ec,
+ *                             tt, the members ordered by (x, index): pred = the largest x_q among the members q with (x_q, q) <
+ *                             (x_c, c) lexicographically, succ = the smallest among those with >, lo and hi = the rank's extremes
+ *                             on the axis; d_x = +inf where pred or succ does not exist, else 0.0 where hi == lo, else
+ *                             (succ - pred) / (hi - lo).  crowd = (d_mk + d_ec) + d_tt, taken literally in binary64 (an infinite
+ *                             cost can make it NaN).  THEN the member of the rank with the smallest non-NaN obj, the lowest
+ *                             index among equal ones, gets crowd = +inf — the one addition to the textbook rule: at most seven
+ *                             members of a rank carry +inf (two per axis and this one), so where P >= 8 of a group survive and the
+ *                             weights are not negative, the candidate with the smallest obj is among them.  NaN for an ineligible
+ *                             candidate
+ *   order_out [N*K] int32     the group's candidates in selection order, order_out[n*K + i] = the local index c of the i-th:
+ *                             eligible before ineligible; then ascending rank; then descending crowd, a NaN crowd after every
+ *                             number; then ascending index
+ *   front_size_out [N] int32  the members of rank 0
+ *   best_obj_out [N] binary64 the smallest non-NaN obj of the eligible candidates (the lowest candidate's own word among equal
+ *                             ones), NaN if there is none
+ * All but front_size_out's count, obj and the division and sums of crowd are comparisons.
+ * Ka >= 1, Kb >= 0, 1 <= K <= 2048 (a group lives in one workgroup's LDS, 44 bytes per candidate), N >= 1, N*K < 2^31, the a
+ * arrays, w3cfg_host and with Kb > 0 the b arrays not NULL: otherwise MTFJSP_ERR_ARG and nothing is written.
+ * One launch (k_front_rank), one workgroup per group (one wave for K <= 64, else four), on h's stream: the peeling counts every
+ * candidate's dominators once and takes every ranked candidate off the counts once — 2 K dominance tests per candidate whatever the
+ * number of fronts — and per front pays one barrier and one scan of the K ranks; it stops as soon as nothing is left.  A totally
+ * ordered group (every candidate a front of its own) is the slow extreme: K such rounds.
+ *
+ * mtfjsp_plan_survivors: h = the handle of the N*P copies; it gives T, the device and the stream.  order, rank: int32 [N*K] as
+ * mtfjsp_front_rank wrote them; 1 <= P <= K.  task_a, mach_a: int32 [T, N*Ka], task_b, mach_b: int32 [T, N*Kb] in history layout;
+ * cost4_a / done_a, cost4_b / done_b as above.  Output column n*P + i takes candidate c = order[n*K + i]:
+ *   task_out, mach_out [T, N*P] int32   its plan, row s ready for mtfjsp_step
+ *   cost4_out [N*P,4], done_out [N*P]   its costs and done byte (or NULL)
+ *   rank_out [N*P] int32                rank[n*K + c] (or NULL)
+ *   src_out [N*P] int32                 c, as read (or NULL)
+ *   fit_out [N*P] binary64              (double)i where rank[n*K + c] >= 0, NaN otherwise (or NULL): smaller is better, NaN loses
+ * An order entry outside [0, K) gives a column of -1, done_out = 0, rank_out = -1, cost4_out and fit_out NaN (src_out still holds
+ * the entry).  No access leaves the arrays.
+ * MTFJSP_ERR_ARG, nothing written: a null order / rank / a array / task_out / mach_out, a null b array with Kb > 0; Ka < 1, Kb < 0,
+ * N < 1, N*K >= 2^31, P < 1 or P > K, batch != N*P; an output array that overlaps an input array or another output.
+ * One launch (k_plan_survivors) on h's stream: row s is written as contiguous runs, the reads stay inside one group's columns. */
+int mtfjsp_front_rank(mtfjsp_handle_t h, int32_t N, int32_t Ka, int32_t Kb, const double *cost4_a, const uint8_t *done_a,
+                      const double *cost4_b, const uint8_t *done_b, const double *w3cfg_host, int32_t *rank_out, double *crowd_out,
+                      int32_t *order_out, int32_t *front_size_out, double *best_obj_out);
+int mtfjsp_plan_survivors(mtfjsp_handle_t h, int32_t N, int32_t Ka, int32_t Kb, int32_t P, const int32_t *order, const int32_t *rank,
+                          const int32_t *task_a, const int32_t *mach_a, const double *cost4_a, const uint8_t *done_a,
+                          const int32_t *task_b, const int32_t *mach_b, const double *cost4_b, const uint8_t *done_b,
+                          int32_t *task_out, int32_t *mach_out, double *cost4_out, uint8_t *done_out, int32_t *rank_out,
+                          int32_t *src_out, double *fit_out);
+
 /* ------------------------------------------------------------------ dispatch-rule baselines */
 /* = the two lists run_Rules_jointActions_withMinus_1217 fixes before its first step (tester/pdrs.py:680-753) for every instance:
  * o_rule[b] in 0..5 = FIFO (pdrs:123-125), MOR (pdrs:128-137), LWKR_T, LWKR_PT, MWKR_T, MWKR_PT (pdrs:162-286 with the "mean"
