@@ -513,17 +513,6 @@ __device__ __forceinline__ unsigned rem16x2(unsigned hi_pair, float x0, float x1
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(hi_pair), "v"(x1));
     return r;
 }
-#ifdef MTFJSP_SPLIT_PLAIN    // A/B: the split written as conversions and subtractions
-__device__ __forceinline__ void split2x4(const float (&v)[4], uint2 &p0, uint2 &p1)
-{
-    const f32x2 v01 = {v[0], v[1]}, v23 = {v[2], v[3]};
-    const h16x2 a = __builtin_convertvector(v01, h16x2), b = __builtin_convertvector(v23, h16x2);
-    const f32x2 r01 = v01 - __builtin_convertvector(a, f32x2), r23 = v23 - __builtin_convertvector(b, f32x2);
-    const h16x2 c = __builtin_convertvector(r01, h16x2), d = __builtin_convertvector(r23, h16x2);
-    p0 = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-    p1 = make_uint2(__builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d));
-}
-#else
 __device__ __forceinline__ void split2x4(const float (&v)[4], uint2 &p0, uint2 &p1)
 {
     const f32x2 v01 = {v[0], v[1]}, v23 = {v[2], v[3]};
@@ -532,9 +521,8 @@ __device__ __forceinline__ void split2x4(const float (&v)[4], uint2 &p0, uint2 &
     p0 = make_uint2(pa, pb);
     p1 = make_uint2(rem16x2(pa, v[0], v[1]), rem16x2(pb, v[2], v[3]));
 }
-#endif
 // the same split with the remainders taken by v_fma_mix_f32 (f16 piece as an f32 operand: x - (float)hi in ONE instruction
-// instead of two conversions and a subtraction; exactly rounded either way, see gr_rem2 in mtfjsp_gin_resident.h)
+// instead of two conversions and a subtraction; exactly rounded either way, see gr_rem16 in mtfjsp_gin_resident.h)
 __device__ __forceinline__ void split2x4m(const float (&v)[4], uint2 &p0, uint2 &p1)
 {
     const f32x2 v01 = {v[0], v[1]}, v23 = {v[2], v[3]};
@@ -664,14 +652,10 @@ __global__ __launch_bounds__(512) void k_gemm_x6(GemmArgs A)
         const int lane_off = h * HD + c4;
         float4 preA[8], preB[8];
         constexpr int NA = (PRO == PRO_AGG) ? 8 : 1;
-        // PRO_AGG: neighbour rows TWO steps ahead like the tile's own rows (two register stages), the ELL entries they depend on
-        // three (ring of 4).  (Round 2 requested the neighbour rows of step s+1 behind the transform of step s: with the consumers
+        // PRO_AGG: neighbour rows ONE step ahead (one register stage; a second stage, two steps ahead like the tile's own rows, cost 64
+        // registers and measured slower), the ELL entries they depend on three (ring of 4).  (Round 2 requested the neighbour rows of step s+1 behind the transform of step s: with the consumers
         // waiting for the producers — 258 k of 466 k cycles at their barrier — that round trip was exposed in every step.)
-#ifndef X6_NB_AHEAD
-#define X6_NB_AHEAD 1                       // steps the aggregation's neighbour rows are requested ahead (2: a second register stage = 64 registers more, 256 + 52 B of scratch: 203 / 196 us against 198 / 193 at J20M20 / J10M10)
-#endif
-        struct NbRows { float4 r0[NA], r1[NA]; } nbA, nbB_;
-        NbRows &nbB = X6_NB_AHEAD == 2 ? nbB_ : nbA;
+        struct NbRows { float4 r0[NA], r1[NA]; } nbs;                 // (the one stage; `produce` takes it as an argument like the row stages)
         struct EllSlot { int ox, oy; float vx, vy, dg; } el[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) { el[i].ox = 0; el[i].oy = 0; el[i].vx = 0.f; el[i].vy = 0.f; el[i].dg = 1.f; }
@@ -951,10 +935,9 @@ __global__ __launch_bounds__(512) void k_gemm_x6(GemmArgs A)
         int cndA = -1, cndB = -1;
         request_rows(preA, CL(t0));
         if (PRO == PRO_BNRELU) request_cand(cndA, CL(t0));
-        if (PRO == PRO_AGG) request_nb(nbA, el[0], CL(t0));
+        if (PRO == PRO_AGG) request_nb(nbs, el[0], CL(t0));
         request_rows(preB, CL(t0 + 4));
         if (PRO == PRO_BNRELU) request_cand(cndB, CL(t0 + 4));
-        if (PRO == PRO_AGG && X6_NB_AHEAD == 2) request_nb(nbB, el[1], CL(t0 + 4));
         stage_scale_shift(std::false_type{});
         LDS_BARRIER();
         STAMP(0);
@@ -1003,21 +986,20 @@ __global__ __launch_bounds__(512) void k_gemm_x6(GemmArgs A)
                 }
             }
             // requests (vmcnt retires in order): the ELL entries of step s+3 first — step s+1 turns them into addresses and must not
-            // wait for the rows behind them —, then the rows and neighbour rows of step s+2 into the registers this tile just left
+            // wait for the rows behind them —, then the neighbour rows of step s+1 and the rows of step s+2 into the registers this tile just left
             if (PRO == PRO_AGG) fetch_ell(el[(K + 3) & 3], CL(tile + 12));
-            if (PRO == PRO_AGG && X6_NB_AHEAD == 1) request_nb(nb, el[(K + 1) & 3], CL(tile + 4));    // (needed first at the next step: ahead of the rows of s+2)
+            if (PRO == PRO_AGG) request_nb(nb, el[(K + 1) & 3], CL(tile + 4));    // (needed first at the next step: ahead of the rows of s+2)
             request_rows(pre, CL(tile + 8));
             if (PRO == PRO_BNRELU) request_cand(cv, CL(tile + 8));
-            if (PRO == PRO_AGG && X6_NB_AHEAD == 2) request_nb(nb, el[(K + 2) & 3], CL(tile + 8));
             STAMP(1);
             LDS_BARRIER();
             STAMP(4);
         };
         for (int s = 0; s < nsteps_c; s += 4) {
-            produce(preA, nbA, cndA, std::integral_constant<int, 0>{}, s);
-            produce(preB, nbB, cndB, std::integral_constant<int, 1>{}, s + 1);
-            produce(preA, nbA, cndA, std::integral_constant<int, 2>{}, s + 2);
-            produce(preB, nbB, cndB, std::integral_constant<int, 3>{}, s + 3);
+            produce(preA, nbs, cndA, std::integral_constant<int, 0>{}, s);
+            produce(preB, nbs, cndB, std::integral_constant<int, 1>{}, s + 1);
+            produce(preA, nbs, cndA, std::integral_constant<int, 2>{}, s + 2);
+            produce(preB, nbs, cndB, std::integral_constant<int, 3>{}, s + 3);
         }
         LDS_BARRIER();                                            // the consumers' last step
         }
@@ -1470,9 +1452,6 @@ __device__ __forceinline__ int gx_off(int row, int col) { return row * HD + ((((
 #define GAT_PRESTAGED 0
 #define BODY_TID threadIdx.x              // (k_headsx_gat3x_headsx gives each of its three parts an opaque copy: left alone, hipcc keeps the thread-index
                                           // expressions common to the parts alive across all of them — through scratch memory where registers run out)
-#ifndef GAT_PAIRED
-#define GAT_PAIRED 1                        // the three-in-one launch takes a wave's two GAT tiles together (mtfjsp_gat3x_body.h); 0: one after the other
-#endif
 struct XchgArgs {
     unsigned long long *words;       // this forward's words (zero on entry): [fine | wide][8 dispatch groups][sum | sumsq][128 columns]
     unsigned long long *words_next;  // the next forward's set: zeroed by this launch
@@ -1972,6 +1951,7 @@ __global__ __launch_bounds__(512) void k_headsx_gat3x(HeadArgs HA, GatArgs GA)
 #define GAT_F1_OFF (GAT_IMG_OFF + GAT_IMG_BYTES)                  // m_fea1 of the workgroup's 16 x M machines as f32 [16 M][6] (M <= 8), written by the job selection
 #define GAT_F2_OFF (GAT_F1_OFF + 16 * 8 * 6 * 4)                  // m_fea2 likewise [16 M][8], copied here
 #define GAT_PRE_END (GAT_F2_OFF + 16 * 8 * 8 * 4)
+static_assert(GAT_PRE_END <= 8 * 2 * 4 * 64 * 16 + 12 * 16 * HD * 4, "the staged images and rows lie inside the GAT part's LDS (fused3_lds_bytes)");
 // this workgroup's m_fea2 rows (written by the environment step a rollout step ago: the memory-side cache by now) are requested at the top of
 // the launch — the last of the first phase's requests, by every thread (waves 0-3 drop theirs) — and wait in four registers
 // (fx: every workgroup has 16 full instances of f32 observations — no clamp against the end of the array, no f64 form)
@@ -2025,14 +2005,11 @@ __device__ __forceinline__ void gat_prestage(const GatArgs &G, unsigned char *sm
 // own, and the machine part stages its rows by instance) — 12.6 MB per launch less written and 12.6 MB less read back.
 // SH (round 8): the shape the heads and GAT statements see.  H3ShapeAny: everything from the kernel arguments, as before.  H3ShapeFixed<J, M, 16>: the
 // shape as compile-time constants (mtfjsp_fused3_select.h states when the host may launch it; fused3_instantiation checks the arguments' half) — the statements
-// read it through the HX_FX / GAT_FX macros of the body headers, whose defaults are the run-time expressions, so no other kernel changes.  One item,
-// with a -D switch for A/B builds (0: the run-time code): H3_FX_DROP — the chunk loop and its reload path, the row-valid and group-size selects, the
+// read it through the HX_FX / GAT_FX macros of the body headers, whose defaults are the run-time expressions, so no other kernel changes.  What the
+// fixed shape drops: the chunk loop and its reload path, the row-valid and group-size selects, the
 // null-pointer alternatives, the non-row-wise selection, the f64 branches, the GAT part's tile bookkeeping and its one-tile-at-a-time loop.
 // (Measured and not kept, profiles/HISTORY.md round 8: the selection's straight-line forms — unrolled scan, total by a DPP row broadcast, the job
 // position by a multiply-high, m_fea1 without its loop.)
-#ifndef H3_FX_DROP
-#define H3_FX_DROP 1
-#endif
 struct H3ShapeAny { static constexpr bool fixed = false; static constexpr int J = 0, M = 0, T = 0, PER = 0; };
 template <int J_, int M_, int IPC_>
 struct H3ShapeFixed {
@@ -2046,7 +2023,7 @@ typedef H3ShapeFixed<FUSED3_FX_J, FUSED3_FX_M, FUSED3_FX_IPC> H3ShapeHeadline;
 template <int ENV, bool NLDS, class SH = H3ShapeAny>
 __global__ __launch_bounds__(512) void k_headsx_gat3x_headsx(HeadArgs HA, GatArgs GA, HeadArgs HM, XchgArgs XG, EnvParams EP)
 {
-    static_assert(!SH::fixed || (ENV == 0 && NLDS && GAT_PAIRED), "the fixed shape: no environment tail, node rows in LDS, paired GAT tiles");
+    static_assert(!SH::fixed || (ENV == 0 && NLDS), "the fixed shape: no environment tail, node rows in LDS, paired GAT tiles");
     extern __shared__ __align__(16) unsigned char smem[];
     const XchgArgs &XA = XG;
 #undef HX_FX
@@ -2054,14 +2031,14 @@ __global__ __launch_bounds__(512) void k_headsx_gat3x_headsx(HeadArgs HA, GatArg
 #undef HX_FX_R
 #undef HX_FX_T
 #undef HX_FX_M
-#define HX_FX (SH::fixed && H3_FX_DROP != 0)
+#define HX_FX (SH::fixed)
 #define HX_FX_JOB true
 #define HX_FX_R (SH::J)
 #define HX_FX_T (SH::T)
 #define HX_FX_M (SH::M)
 #undef GAT_FX
 #undef GAT_FX_PER
-#define GAT_FX (SH::fixed && H3_FX_DROP != 0)
+#define GAT_FX (SH::fixed)
 #define GAT_FX_PER (SH::PER)
     X3_RT(0);
     for (int i = blockIdx.x * 512 + threadIdx.x; i < XW_SET; i += (int)gridDim.x * 512) XA.words_next[i] = 0ull;
@@ -2076,12 +2053,8 @@ __global__ __launch_bounds__(512) void k_headsx_gat3x_headsx(HeadArgs HA, GatArg
 #endif
     {
         const HeadArgs &A = HA;
-#ifndef GAT_F2_LATE
 #define HX_TOP_HOOK float gf2[4]; gat_f2_load(GA, tid & 255, HX_FX ? HX_FX_M : A.mf.M, gf2, HX_FX);
 #define HX_IDLE_HOOK gat_prestage(GA, smem, tid - 256, gf2);
-#else                                                              // (diagnostic builds: the rows requested where they are stored, as before)
-#define HX_IDLE_HOOK float gf2[4]; gat_f2_load(GA, tid - 256, HX_FX ? HX_FX_M : A.mf.M, gf2, HX_FX); gat_prestage(GA, smem, tid - 256, gf2);
-#endif
 #define HX_MF1_LDS reinterpret_cast<float *>(smem + GAT_F1_OFF)
 #include "mtfjsp_headsx_body.h"
 #undef HX_IDLE_HOOK
@@ -2195,7 +2168,7 @@ __global__ __launch_bounds__(512) void k_headsx_envstep(HeadArgs HA, EnvParams E
     env_grp_body_dyn<OBS, 1, 8>(EP, smem);
 }
 static size_t headsx_lds_bytes() { return (size_t)(HCH + 3) * X2_TILE + (size_t)(16 * HX_CLDA + HG * HD + HX_NPART * HCH * 16 + HG * 64 + 2 * HD + 5 * HD) * 4 + HG * 64 + 2 * 512 * 4; }
-static size_t fused3_lds_bytes() { const size_t g = GAT_PAIRED ? (size_t)(8 * 2 * 4 * 64 * 16 + 12 * 16 * HD * 4) : (size_t)GAT_PRE_END; return headsx_lds_bytes() > g ? headsx_lds_bytes() : g; }   // k_headsx_gat3x_headsx: + the prestaged GAT images and feature rows (GAT_PRE_END)
+static size_t fused3_lds_bytes() { const size_t g = (size_t)(8 * 2 * 4 * 64 * 16 + 12 * 16 * HD * 4); return headsx_lds_bytes() > g ? headsx_lds_bytes() : g; }   // k_headsx_gat3x_headsx: the GAT fragments and 12 tile buffers (the prestaged images and feature rows, up to GAT_PRE_END, lie in buffers 8, 9)
 // The same kernel with TEN scorer tiles per chunk: a group of 16 instances with 7..10 candidates / machines each (J10M10: R = 10)
 // goes through the product phases once instead of twice (6 + 4 tiles, each chunk with its own staging, four barriers and latency chain)
 #undef HCH
@@ -2325,9 +2298,6 @@ __global__ __launch_bounds__(256) void k_gin0(int N, int T, const OBS *tfea, con
 // ---------------------------------------------------------------------------------------------
 // After the last GIN BatchNorm: h = relu(bn(z)); graph mean pool (gcn:192) and candidate gather (ac:197-207).
 // One 128-thread block per instance, thread = column.
-#ifndef POOL_INFLIGHT
-#define POOL_INFLIGHT 8                        // rows in flight per thread; 13 / 16 measured the same (114 / 108 us at J10M10 x 8192 / J20M20 x 2048), 25 slower (133 / 117)
-#endif
 // NT (non-temporal row loads) is a template parameter: as a run-time flag — `nt ? __builtin_nontemporal_load(p) : *p` — the two arms
 // were merged into ONE plain load (rounds 3 and 4 shipped that: no `nt` load in the kernel's ISA), and a just-written 419 MB matrix
 // reads at 3.6-3.8 TB/s with plain loads against 5.2-6.3 TB/s with non-temporal ones (tools/ubench/read_after_write.hip).
@@ -2338,9 +2308,7 @@ __global__ __launch_bounds__(256) void k_gin0(int N, int T, const OBS *tfea, con
 // through LDS (double-buffered: one barrier per instance).  The candidate rows (ac:197-207) are picked out of the stream — row v of
 // job v / M is written to cand_feat when cand[b][v / M] == v — instead of being read a second time behind a dependent index load.
 // The summation order per thread (rows rg, rg+8, ... ascending) and of the fold (row groups 0..7) is the earlier kernel's: same bits.
-#ifndef POOL_INFLIGHT
-#define POOL_INFLIGHT 8                        // rows per batch and thread (two batches in flight)
-#endif
+constexpr int POOL_INFLIGHT = 8;               // rows per batch and thread (two batches in flight); 13 / 16 measured the same (114 / 108 us at J10M10 x 8192 / J20M20 x 2048), 25 slower (133 / 117)
 // Pooling epilogue of the last streaming product (k_gemm_x6, GemmArgs::pooled): that launch takes candidate j of an instance from job j's block of rows
 // — where the environment's candidates always lie (ppo:306-309) — and its output is not stored.  A caller-made candidate outside its job's block is served
 // here, one thread per such slot, by forming that one row again with f32 instructions: h4 = relu(bn4(z4[row])), z5 = W5 h4 + b5, relu(bn5(z5)).  Never on the
@@ -3026,7 +2994,6 @@ struct mtfjsp_encoder {
     long long res_failures = 0, res_launches = 0;
     long long res_fail_at = getenv("MTFJSP_GIN_RES_FAIL_AT") ? atoll(getenv("MTFJSP_GIN_RES_FAIL_AT")) : 0;   // diagnostic: this launch's barriers time out
     long long range_fail_at = getenv("MTFJSP_RANGE_FAIL_AT") ? atoll(getenv("MTFJSP_RANGE_FAIL_AT")) : 0, job_forwards = 0;   // diagnostic: the n-th job-actor forward raises the range word (as a NaN output would)
-    float *res_zspill = nullptr;            // [grid][4][2][1024] f32: the two row tiles per workgroup that do not fit the registers
     unsigned long long res_epoch = 0;
     int gat_slot = 0;                       // the machine-path slot of the NEXT forward; the other one is zeroed by that forward's heads kernel
     struct { bool valid = false; const void *f1 = nullptr, *f2 = nullptr; int slot = 0;
@@ -3286,8 +3253,7 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
             const int ipc = pl.ipc, grid = pl.grid;
             if (hipFuncSetAttribute((const void *)k_gin_res, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess &&
                 hipFuncSetAttribute((const void *)k_gin_res_t36j6x16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess) {
-                int rc = dalloc(e, &e->res_stats, (size_t)2 * GR_STATS_SET) | dalloc(e, &e->res_bar, (size_t)17 * 16) |
-                         dalloc(e, &e->res_zspill, (size_t)grid * 4 * (GR_NT - GR_NRES) * 1024);
+                int rc = dalloc(e, &e->res_stats, (size_t)2 * GR_STATS_SET) | dalloc(e, &e->res_bar, (size_t)17 * 16);
                 if (!rc && hipMemset(e->res_stats, 0, (size_t)2 * GR_STATS_SET * 8) == hipSuccess &&
                     hipMemset(e->res_bar, 0, (size_t)17 * 16 * 8) == hipSuccess) {
                     e->res_ipc = ipc; e->res_grid = grid; e->res_eligible = true;
@@ -3829,7 +3795,7 @@ static int run_gin_resident(mtfjsp_encoder *e, const GinPlan &gp, const GinWeigh
     a.stats = reinterpret_cast<unsigned long long *>(e->res_stats) + (size_t)set * GR_STATS_SET;
     a.stats_next = reinterpret_cast<unsigned long long *>(e->res_stats) + (size_t)(set ^ 1) * GR_STATS_SET;
     a.bar = e->res_bar; a.epoch = e->res_epoch++; a.fail = e->res_fail; a.range_flag = e->range_flag;
-    a.candidate = candidate; a.pooled = h_pooled; a.cand_feat = cand_feat; a.h_nodes = h_nodes; a.zspill = e->res_zspill;
+    a.candidate = candidate; a.pooled = h_pooled; a.cand_feat = cand_feat; a.h_nodes = h_nodes; a.zspill = nullptr;
     a.inv_rows = 1.0 / ((double)B * (double)T);
     if (warm && e->warm_heads) {
         // what the heads launch behind this one reads first — the weight images of both actors' heads and of the GAT passes, last read a
@@ -4245,7 +4211,7 @@ static Fused3Kernel fused3_instantiation(const HeadsPlan &pl, const HeadArgs &ha
 {
     const int gtiles = (2 * ha.B * hm.R + 15) / 16, gper = (gtiles + pl.grid - 1) / pl.grid;
     *nlds = pl.three.nodes_lds && (fused3_lds_bytes() >= (size_t)(8 * 2 * 4 * 64 * 16 + gper * 16 * HD * 4));
-    const bool fx_args = GAT_PAIRED && *nlds && ha.hg == HG && hm.hg == HG && ga.R == ha.B * hm.R && !ga.feat_f64 &&
+    const bool fx_args = *nlds && ha.hg == HG && hm.hg == HG && ga.R == ha.B * hm.R && !ga.feat_f64 &&
                          !ha.xgather && !ha.xbn_stats && !ha.xrelu && !ha.zero_stats && !ha.zero_stats2 && ha.pooled && ha.sample_mode && ha.gather_from && ha.gathered_out &&
                          ha.logp_out && ha.mf_on && ha.mf.obs_f32 && ha.mf.M == hm.R &&
                          !hm.xgather && hm.xbn_stats && !hm.xrelu && !hm.zero_stats && !hm.zero_stats2 && hm.sample_mode && hm.logp_out && !hm.gather_from && !hm.mf_on;

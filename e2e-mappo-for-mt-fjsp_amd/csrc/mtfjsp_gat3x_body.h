@@ -189,7 +189,7 @@
     }
     };
     const unsigned char *wl = s_wf + lane * 16;                   // fragment (c, p, ks): wl + ((c*2 + p)*4 + ks) * 1024
-#if GAT_PRESTAGED && GAT_PAIRED
+#if GAT_PRESTAGED
     // PAIRED tiles (round 5, k_headsx_gat3x_headsx with 9..12 tiles per workgroup = M = 5, 6): every tile has its own buffer (12 x 8 KB + the 64 KB of
     // fragments = all of LDS), a wave with two tiles (w and w + 8) takes them TOGETHER — each weight fragment read from LDS feeds the matrix
     // instructions of both tiles (the tiles are bound by those reads: profiles/r05_ablate_gat.txt) and no wave is left alone with a second tile

@@ -53,40 +53,23 @@
                                           // 8 no plane writes, 16 no pooling, 32 no candidate gather
 #define GR_ABL 0
 #endif
-#ifndef GR_NRES
-#define GR_NRES 16                        // ... of which this many stay in registers; the others go through zspill (see below)
-#endif
-#ifndef GR_VRES
-#define GR_VRES 1                         // 1: row tiles GR_NRES.. stay on chip too — in the VECTOR registers that used to stage their round trip through global
-#endif                                    // memory (the matrix instructions on them are written out with vector-register accumulators); 0: the round trip
+#define GR_NRES 16                        // ... of which this many stay in the accumulation registers; the others (GR_NRES..) live in VECTOR registers, and the matrix
+                                          // instructions on them are written out with vector-register accumulators
 #define GR_RING 6                         // row tiles in the f32 ring of the aggregation layer
 #define GR_NBAR 6                         // grid barriers per launch
-#ifndef GR_GRP
 #define GR_GRP 2                          // row tiles per workgroup barrier in the layers without aggregation (2 * GR_GRP plane buffers; measured 1: 142, 2: 135, 3: 138 us per launch)
-#endif
-#ifndef GR_LOOK
-#define GR_LOOK 2                         // layers without aggregation: the planes of tile RT + GR_LOOK are produced while tile RT is multiplied; 2 * GR_LOOK
-#endif                                    // plane buffers.  GR_LOOK == GR_GRP: one workgroup barrier per group of tiles (4 buffers); GR_LOOK == 2 * GR_GRP: the four
-                                          // waves synchronise through one LDS counter per group with a whole group of slack, no barrier inside a layer —
-                                          // correct (same tests), measured SLOWER: 144 vs 135 us per launch (the four waves run in step anyway, and the
-                                          // deeper look-ahead costs 20 more spilled registers); kept as a build option
+#define GR_LOOK 2                         // layers without aggregation: the planes of tile RT + GR_LOOK are produced while tile RT is multiplied, in 2 * GR_LOOK plane
+                                          // buffers; GR_LOOK == GR_GRP: one workgroup barrier per group of tiles (two groups ahead, no barrier: measured 144 vs 135 us)
 #define GR_ROWB 272                       // plane row pitch in bytes (256 + 16: conflict-free 16-byte operand reads)
 #define GR_PLANE (32 * GR_ROWB)
 #define GR_TILE (2 * GR_PLANE)                // a tile buffer: the (high | low) f16 planes of 32 rows
 #define GR_MAXWARM 10
-// What the fixed-shape instantiation (GrShapeFixed below) drops or moves, one switch each for A/B builds (-DGR_FX_...=0 is the run-time code):
-#ifndef GR_FX_DROP
-#define GR_FX_DROP 1                      // row-valid selects and s_zero, the prologue's validity clamps, the divisions by J and T, the node-output test, the
-#endif                                    // run-time `left` of the pooling, candidate-store addresses from one base
-#ifndef GR_FX_TAIL
-#define GR_FX_TAIL 1                      // pooled tail with a constant trip count, every read issued before the first use
-#endif
-#ifndef GR_FX_SETUP
-#define GR_FX_SETUP 1                     // the final phase's set-up (s_wtab, slot[], the warm request) inside the last boundary, behind its atomic; needs
-#endif                                    // GR_FOLD_DPP (the boundary's LDS fold parks its sums in the ring area the table lives in)
 // The shape as compile-time parameters of the ONE kernel body.  GrShapeAny: everything read from GinResArgs (any 16 <= T <= 65, any
 // instances-per-workgroup count, a partly filled last workgroup, optional node output).  GrShapeFixed: T rows per instance, J candidates
-// per instance (A.candidate given), IPC instances in EVERY workgroup (B % IPC == 0, IPC * T == GR_ROWS), no node output.
+// per instance (A.candidate given), IPC instances in EVERY workgroup (B % IPC == 0, IPC * T == GR_ROWS), no node output.  What the fixed
+// shape drops or moves: the row-valid selects and s_zero, the prologue's validity clamps, the divisions by J and T, the node-output test, the
+// run-time `left` of the pooling, candidate-store addresses from one base; the pooled tail has a constant trip count with every read issued
+// before the first use; the final phase's set-up (s_wtab, slot[], the warm request) sits inside the last boundary, behind its atomic.
 struct GrShapeAny { static constexpr bool FIXED = false; static constexpr int T = 0, J = 0, IPC = 0; };
 template <int T_, int J_, int IPC_> struct GrShapeFixed {
     static constexpr bool FIXED = true; static constexpr int T = T_, J = J_, IPC = IPC_;
@@ -108,22 +91,6 @@ constexpr int gr_max_chunks(int T)
     return m;
 }
 
-#ifndef GR_MIX
-#define GR_MIX 2                          // 1: the low operand piece as fma(f16 high piece, -1, x) = v_fma_mix_f32 (no separate f16 -> f32 conversion); same bits
-#endif                                    // 2: ... and rounded to f16 by the same instruction (v_fma_mixlo_f16 / v_fma_mixhi_f16: the remainder is exact in f32,
-                                          //    so this is the one rounding the separate conversion performed): a packed conversion less per value pair; same bits
-#ifndef GR_SETTLE
-#define GR_SETTLE 1                       // two extra wait states between a tile's last matrix instruction and the first vector read of its result
-#endif
-#ifndef GR_FOLD_DPP
-#define GR_FOLD_DPP 1                     // 1: the per-lane column sums of a layer are folded over the 32 row lanes in registers (DPP reduce-scatter); 0: through LDS
-#endif
-#ifndef GR_STAT_ASM
-#define GR_STAT_ASM 0                     // (see stat2)
-#endif
-#ifndef GR_PK
-#define GR_PK 1                           // 1: two-wide f32 vector arithmetic (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32); 0: one instruction per element
-#endif
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 gr_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 gr_h2 __attribute__((ext_vector_type(2)));
@@ -149,7 +116,7 @@ struct GinResArgs {
     float *pooled;                        // [B,128] graph mean pool of h (gcn:192)
     float *cand_feat;                     // [B*J,128] h rows of the candidates (ac:197-207)
     float *h_nodes;                       // optional [B*T,128]
-    float *zspill;                        // [blocks][4 waves][2 tiles][4][64 lanes][4] f32: the pre-BatchNorm values of row tiles 16, 17
+    float *zspill;                        // unused (NULL): row tiles 16, 17 stay in vector registers; kept so that the argument offsets do not move
     double inv_rows;                      // 1 / (B*T)
     int barrier_only;                     // census launch: barriers only
     unsigned expect_extra;                // diagnostic (MTFJSP_GIN_RES_FAIL_AT): the barriers wait for this many workgroups that do not exist -> time-out path
@@ -180,43 +147,18 @@ struct GinResArgs {
 #define GR_OFF_CAND (GR_OFF_BN + 2 * HD * 4)                      // i32 [576]: candidate slot of a row (instance-local slot + J * local instance), -1 = none
 #define GR_OFF_ZERO (GR_OFF_CAND + GR_ROWS * 4)                   // f32 [256] zeros: the "scale | shift" of rows >= nrows
 #define GR_OFF_FLAG (GR_OFF_ZERO + 2 * HD * 4)
-#define GR_OFF_CNT (GR_OFF_FLAG + 64)                             // u32 [5 layers][GR_NT / GR_GRP]: waves that finished a group of tiles (GR_LOOK > GR_GRP)
+#define GR_OFF_CNT (GR_OFF_FLAG + 64)                             // u32 [5 layers][GR_NT / GR_GRP]: zeroed in the prologue and not read (the group counters of the retired look-ahead without barriers)
 #define GR_LDS_BYTES (GR_OFF_CNT + 5 * (GR_NT / GR_GRP) * 4 + 12)
 static size_t gin_res_lds_bytes() { return (size_t)GR_LDS_BYTES; }
 static_assert(GR_LDS_BYTES <= 160 * 1024, "resident GIN kernel: LDS budget");
 
-#if GR_PK == 1
+// two-wide f32 vector arithmetic (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32)
 __device__ __forceinline__ f32x2 gr_fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 gr_add2(f32x2 a, f32x2 b) { return a + b; }
-__device__ __forceinline__ f32x2 gr_sub2(f32x2 a, f32x2 b) { return a - b; }
 __device__ __forceinline__ f32x2 gr_mul2(f32x2 a, f32x2 b) { return a * b; }
-#else
-// (element by element, each result pinned so that no later pass pairs them up again)
-#if GR_PK == 2
-__device__ __forceinline__ float gr_pin(float x) { return x; }     // (with -fno-slp-vectorize)
-#else
-__device__ __forceinline__ float gr_pin(float x) { asm("" : "+v"(x)); return x; }
-#endif
-__device__ __forceinline__ f32x2 gr_fma2(f32x2 a, f32x2 b, f32x2 c) { return f32x2{gr_pin(__builtin_fmaf(a[0], b[0], c[0])), gr_pin(__builtin_fmaf(a[1], b[1], c[1]))}; }
-__device__ __forceinline__ f32x2 gr_add2(f32x2 a, f32x2 b) { return f32x2{gr_pin(a[0] + b[0]), gr_pin(a[1] + b[1])}; }
-__device__ __forceinline__ f32x2 gr_sub2(f32x2 a, f32x2 b) { return f32x2{gr_pin(a[0] - b[0]), gr_pin(a[1] - b[1])}; }
-__device__ __forceinline__ f32x2 gr_mul2(f32x2 a, f32x2 b) { return f32x2{gr_pin(a[0] * b[0]), gr_pin(a[1] * b[1])}; }
-#endif
-// x - (float)high piece, elementwise (exactly rounded either way: the product by -1 is exact)
-__device__ __forceinline__ f32x2 gr_rem2(f32x2 v, gr_h2 p)
-{
-#if GR_MIX
-    // (written as instructions: the optimiser turns fma(x, -1, v) back into a subtraction behind a conversion)
-    float r0, r1;
-    const unsigned pp = __builtin_bit_cast(unsigned, p);
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(pp), "v"(v[0]));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(pp), "v"(v[1]));
-    return f32x2{r0, r1};
-#else
-    return gr_sub2(v, __builtin_convertvector(p, f32x2));
-#endif
-}
-// f16(x - (float)high piece), both elements, packed
+// f16(x - (float)high piece), both elements, packed: the low operand piece as fma(f16 high piece, -1, x), rounded to f16 by the same
+// instruction (the product by -1 and the remainder are exact in f32, so this is the one rounding a separate conversion would perform).
+// (Written as instructions: the optimiser turns fma(x, -1, v) back into a subtraction behind a conversion.)
 __device__ __forceinline__ gr_h2 gr_rem16(f32x2 v, gr_h2 p)
 {
     unsigned r;
@@ -329,7 +271,6 @@ __global__ __launch_bounds__(256) void k_gin_res_t36j6x16(GinResArgs A);        
 __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
 {
     typedef GR_SHAPE SH;
-    constexpr bool FXD = SH::FIXED && GR_FX_DROP, FXT = SH::FIXED && GR_FX_TAIL, FXS = SH::FIXED && GR_FX_SETUP && GR_FOLD_DPP;
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char *s_planes = smem + GR_OFF_PLANES;
     float *s_ring = reinterpret_cast<float *>(smem + GR_OFF_RING);
@@ -349,10 +290,10 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         for (int k = 0; k < GR_NBAR; k++) gr_grid_barrier(A.bar, gen0 + k + 1, nblk, A.fail, s_flag);
         return;
     }
-    const int T = FXD ? SH::T : A.T, Jn = FXD ? SH::J : A.J;
-    const int inst0 = blockIdx.x * (FXD ? SH::IPC : A.ipc);
-    const int ninst = FXD ? SH::IPC : A.B - inst0 < A.ipc ? A.B - inst0 : A.ipc;
-    const bool have_cand = FXD || A.candidate;
+    const int T = SH::FIXED ? SH::T : A.T, Jn = SH::FIXED ? SH::J : A.J;
+    const int inst0 = blockIdx.x * (SH::FIXED ? SH::IPC : A.ipc);
+    const int ninst = SH::FIXED ? SH::IPC : A.B - inst0 < A.ipc ? A.B - inst0 : A.ipc;
+    const bool have_cand = SH::FIXED || A.candidate;
     const int nrows = ninst * T;
     const size_t grow0 = (size_t)inst0 * T;                       // first global row of this workgroup
     // (every workgroup computes all GR_NT tiles: rows >= nrows are zero inputs, masked out of the BatchNorm sums and never
@@ -431,7 +372,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
             __builtin_amdgcn_sched_barrier(0);
         }
         if (tid == 0) s_flag[1] = 0u;
-        if (tid < 5 * (GR_NT / GR_GRP)) s_cnt[tid] = 0u;
+        if (tid < 5 * (GR_NT / GR_GRP)) s_cnt[tid] = 0u;          // (nobody reads them any more: goes with the words themselves, a change of the device code)
         for (int i = tid; i < 2 * GR_TILE / 16; i += 256) reinterpret_cast<float4 *>(s_planes)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (have_cand) {                                          // row -> candidate slot (ac:197-207 gathers h of one row per job)
             LDS_BARRIER();                                        // (s_rowcand is LDS; __syncthreads() would also wait for the weight request above)
@@ -441,30 +382,14 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
                 if (i < ninst * Jn && c >= 0 && c < T && atomicExch(&s_rowcand[(i / Jn) * T + c], i) != -1) s_flag[1] = 1u;   // two slots on one row: fixed up at the end
             }
         }
-        if constexpr (!FXD) s_zero[tid] = 0.f;
+        if constexpr (!SH::FIXED) s_zero[tid] = 0.f;
     }
     // 18 tiles x 16 accumulators = 288 values per lane, but only 256 accumulation registers exist and the matrix instructions
     // need one 16-register tuple of them to work in: left to itself hipcc keeps two values per tile in scratch memory and the
-    // reloads stall the wave.  So tiles 0..15 are resident and tiles 16, 17 make an explicit round trip per layer through 32 KB
-    // of global memory per workgroup (L2-resident, each wave its own 8 KB, 16-byte coalesced, requested a tile ahead of use).
+    // reloads stall the wave.  So tiles 0..15 live in the accumulation file and tiles 16, 17 in 32 vector registers.
     f32x16 acc[GR_NRES];
-    f32x16 zs[2];                                                 // ring: spilled tile j uses zs[j & 1]
-    float *zsp = A.zspill + ((size_t)(blockIdx.x * 4 + wave) * (GR_NT - GR_NRES)) * 1024 + lane * 4;
-    auto zload = [&](auto Jc) __attribute__((always_inline)) {
-        constexpr int j = decltype(Jc)::value;
-        if constexpr (GR_VRES) return;
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const float4 v = *reinterpret_cast<const float4 *>(zsp + j * 1024 + g * 256);
-            zs[j & 1][4 * g] = v.x; zs[j & 1][4 * g + 1] = v.y; zs[j & 1][4 * g + 2] = v.z; zs[j & 1][4 * g + 3] = v.w;
-        }
-    };
-    auto zstore = [&](auto Jc, const f32x16 &a) __attribute__((always_inline)) {
-        constexpr int j = decltype(Jc)::value;
-        if constexpr (GR_VRES) return;
-#pragma unroll
-        for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(zsp + j * 1024 + g * 256) = make_float4(a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]);
-    };
+    f32x16 zs[2];                                                 // tile GR_NRES + j lives in zs[j & 1]
+    static_assert(GR_NT - GR_NRES <= 2, "row tiles beyond GR_NRES: one vector-register tile each");
 #define GR_TILEVAL(rt) ((rt) < GR_NRES ? acc[(rt) < GR_NRES ? (rt) : 0] : zs[(rt) >= GR_NRES ? ((rt) - GR_NRES) & 1 : 0])
     // v_mfma with its accumulator in VECTOR registers, written out: the compiler's intrinsic would allocate it in the accumulation
     // file (full) and move it back and forth.  ZERO: the first product of a tile (C = 0).
@@ -479,7 +404,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
     // (Fixed shape: every row of every workgroup is valid — no select, no s_zero.)
     int nrows_l = nrows, n_l = n;
     auto bn_of = [&](int rt) __attribute__((always_inline)) -> const float * {
-        if constexpr (FXD) return s_bn;
+        if constexpr (SH::FIXED) return s_bn;
         else return rt * 32 + n_l < nrows_l ? s_bn : s_zero;     // rows >= nrows: scale = shift = 0 -> zero planes
     };
     bool timed_out = false;                                       // a statistics wait of this launch gave up: everything after it is garbage
@@ -500,16 +425,8 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
     // the two statistics updates of a column pair, pinned where they are written (hipcc would sink a whole layer's sums to their use)
     auto stat2 = [&](int i, float x, float y) __attribute__((always_inline)) {
         const f32x2 v = {x, y};
-#if GR_STAT_ASM == 1                        // the two updates written out as packed instructions (hipcc splits about half of them into four scalar ones):
-        asm volatile("v_pk_add_f32 %0, %2, %0\n\tv_pk_fma_f32 %1, %2, %2, %1" : "+v"(ts[i]), "+v"(tq[i]) : "v"(v));      // measured SLOWER, 110.7 against 108.6 us per launch (A/B, one box)
-#elif GR_STAT_ASM == 2                      // ... all four as scalar instructions: 137.9 us (the pairs are taken apart and put together again)
-        float s0 = ts[i][0], s1 = ts[i][1], q0 = tq[i][0], q1 = tq[i][1];
-        asm volatile("v_add_f32 %0, %4, %0\n\tv_add_f32 %1, %5, %1\n\tv_fma_f32 %2, %4, %4, %2\n\tv_fma_f32 %3, %5, %5, %3" : "+v"(s0), "+v"(s1), "+v"(q0), "+v"(q1) : "v"(x), "v"(y));
-        ts[i] = f32x2{s0, s1}; tq[i] = f32x2{q0, q1};
-#else
         ts[i] = gr_add2(ts[i], v); tq[i] = gr_fma2(v, v, tq[i]);
         asm volatile("" : "+v"(ts[i]), "+v"(tq[i]));
-#endif
     };
     auto stats_all = [&](const f32x16 &a) __attribute__((always_inline)) {
         if (GR_ABL & 4) return;
@@ -519,12 +436,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
     // exact-to-2^-22 operand split of 4 values: high = f16(v), low = f16(v - high) (both round-to-nearest) -> packed pairs
     auto split2x4 = [&](f32x2 v01, f32x2 v23, uint2 &p0, uint2 &p1) __attribute__((always_inline)) {
         const gr_h2 a = __builtin_convertvector(v01, gr_h2), b = __builtin_convertvector(v23, gr_h2);
-#if GR_MIX == 2
         const gr_h2 c = gr_rem16(v01, a), d = gr_rem16(v23, b);
-#else
-        const f32x2 r01 = gr_rem2(v01, a), r23 = gr_rem2(v23, b);
-        const gr_h2 c = __builtin_convertvector(r01, gr_h2), d = __builtin_convertvector(r23, gr_h2);
-#endif
         p0 = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
         p1 = make_uint2(__builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d));
     };
@@ -535,29 +447,8 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         constexpr int RT = decltype(Tc)::value;
         stats_all(GR_TILEVAL(RT));
     };
-    // Once per layer: the per-lane sums -> this workgroup's (sum | sumsq) of column tid >> 1, one value per thread.  Every lane
-    // parks its 32 values in LDS (ring area, free at the boundaries; 144-byte lane pitch: conflict-free 16-byte writes) and
-    // thread (column, kind) adds up the 32 row-lanes of its column — 8 writes + 32 reads + 31 adds per thread instead of 32
-    // cross-lane reductions.
-    auto fold_stats = [&]() __attribute__((always_inline)) {
-        float *red = s_ring;
-        float *mine = red + (wave * 64 + lane) * 36;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            *reinterpret_cast<float4 *>(mine + 4 * j) = make_float4(ts[2 * j][0], ts[2 * j][1], ts[2 * j + 1][0], ts[2 * j + 1][1]);
-            *reinterpret_cast<float4 *>(mine + 16 + 4 * j) = make_float4(tq[2 * j][0], tq[2 * j][1], tq[2 * j + 1][0], tq[2 * j + 1][1]);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) { ts[i] = f32x2{0.f, 0.f}; tq[i] = f32x2{0.f, 0.f}; }
-        LDS_BARRIER();
-        const int col = tid >> 1, kind = tid & 1, cw = col & 31;
-        const float *src = red + ((col >> 5) * 64 + 32 * ((cw >> 2) & 1)) * 36 + 4 * (cw >> 3) + (cw & 3) + 16 * kind;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; i += 4) { s0 += src[i * 36]; s1 += src[(i + 1) * 36]; s2 += src[(i + 2) * 36]; s3 += src[(i + 3) * 36]; }
-        return (s0 + s1) + (s2 + s3);
-    };
-    // The same fold without LDS and without a workgroup barrier (round 4; GR_FOLD_DPP): a reduce-scatter over the 32 row lanes of a
+    // Once per layer: the per-lane sums -> this workgroup's (sum | sumsq) of every column, one value per thread, without LDS and
+    // without a workgroup barrier (round 4): a reduce-scatter over the 32 row lanes of a
     // half wave in five halving steps — partner = lane ^ 16 (ds_bpermute), ^ 15 (row mirror), ^ 7 (half-row mirror), ^ 2, ^ 1 (quad
     // permutes): at each step a lane keeps the half of its values selected by one of its own lane bits (bit 4, 3, 2, 1, 0), hands the
     // other half to its partner and adds what it receives, the exchange riding on the add as a DPP operand.  {16, 15, 7, 2, 1} span all
@@ -625,7 +516,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         constexpr int RT = decltype(Tc)::value;
         constexpr int PT = RT + GR_LOOK;                                  // the tile whose planes are produced here
         constexpr bool NEXT = (PT < GR_NT) && !(GR_ABL & 1);
-        constexpr bool STATS = RT > 0 && (GR_VRES || RT - 1 < GR_NRES) && !(GR_ABL & 4);     // (a spilled tile's sums are taken when it is stored)
+        constexpr bool STATS = RT > 0 && !(GR_ABL & 4);
         const unsigned char *xa = plane_buf(RT % (2 * GR_LOOK)) + n * GR_ROWB + 16 * h;
         unsigned char *pnext = plane_buf(PT % (2 * GR_LOOK));
         const float *bn = bn_of(PT);
@@ -637,16 +528,13 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
             s4 = *reinterpret_cast<const float4 *>(bn + 32 * wave + 4 * h);
             h4 = *reinterpret_cast<const float4 *>(bn + HD + 32 * wave + 4 * h);
         }
-        constexpr bool VT = GR_VRES && RT >= GR_NRES;                    // this tile lives in vector registers
-        f32x16 atmp;
-        f32x16 &a = RT < GR_NRES ? acc[RT < GR_NRES ? RT : 0] : VT ? zs[RT >= GR_NRES ? (RT - GR_NRES) & 1 : 0] : atmp;     // (its previous-layer values went into the planes one tile ago)
+        constexpr bool VT = RT >= GR_NRES;                               // this tile lives in vector registers
+        f32x16 &a = GR_TILEVAL(RT);                                      // (its previous-layer values went into the planes one tile ago)
         // (the tile's first matrix instruction takes a literal zero as its accumulator: no 16 writes into the accumulation file)
-        // the spilled tiles' old values: requested a tile before the slices that turn them into planes
-        if constexpr (RT + GR_LOOK + 1 >= GR_NRES && RT + GR_LOOK + 1 < GR_NT) zload(std::integral_constant<int, RT + GR_LOOK + 1 - GR_NRES>{});
         gr_static_for<4>([&](auto Pc) __attribute__((always_inline)) {
             constexpr int g = decltype(Pc)::value;                       // region = k-steps 2g, 2g+1 = column quarter g of the next tile
             const gr_h8 *x0 = xf[0], *x1 = xf[1];
-            f32x2 v01 = {0.f, 0.f}, v23 = {0.f, 0.f}, e01 = v01, e23 = v01;
+            f32x2 v01 = {0.f, 0.f}, v23 = {0.f, 0.f};
             gr_h2 p01 = {0, 0}, p23 = p01, q01 = p01, q23 = p01;
             unsigned char *dst = pnext + n * GR_ROWB + (32 * wave + 8 * g + 4 * h) * 2;
             const f32x16 &nx = GR_TILEVAL(PT < GR_NT ? PT : RT);
@@ -677,16 +565,13 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
             // slice 3: the k-step 2g operands are dead once its three instructions have issued
             M(2 * g + 1, 0, 1);
             if constexpr (g < 3) xf[0][0] = *reinterpret_cast<const gr_h8 *>(xa + 32 * (2 * g + 2));
-            if constexpr (NEXT && !GR_MIX) { e01 = __builtin_convertvector(p01, f32x2); e23 = __builtin_convertvector(p23, f32x2); }
             if constexpr (NEXT && g < 3) h4 = *reinterpret_cast<const float4 *>(bn + HD + 32 * wave + 8 * (g + 1) + 4 * h);
             GR_FENCE();
             // slice 4
             M(2 * g + 1, 1, 0);
             if constexpr (g < 3) xf[0][1] = *reinterpret_cast<const gr_h8 *>(xa + GR_PLANE + 32 * (2 * g + 2));
-            if constexpr (NEXT) { if constexpr (GR_MIX == 2) { q01 = gr_rem16(v01, p01); q23 = gr_rem16(v23, p23); }
-                                  else if constexpr (GR_MIX == 1) { v01 = gr_rem2(v01, p01); v23 = gr_rem2(v23, p23); } else { v01 = gr_sub2(v01, e01); v23 = gr_sub2(v23, e23); }
-                                  if (!(GR_ABL & 8)) *reinterpret_cast<uint2 *>(dst) = make_uint2(__builtin_bit_cast(unsigned, p01), __builtin_bit_cast(unsigned, p23));
-                                  if constexpr (GR_MIX != 2) { q01 = __builtin_convertvector(v01, gr_h2); q23 = __builtin_convertvector(v23, gr_h2); } }
+            if constexpr (NEXT) { q01 = gr_rem16(v01, p01); q23 = gr_rem16(v23, p23);
+                                  if (!(GR_ABL & 8)) *reinterpret_cast<uint2 *>(dst) = make_uint2(__builtin_bit_cast(unsigned, p01), __builtin_bit_cast(unsigned, p23)); }
             GR_FENCE();
             // slice 5
             M(2 * g + 1, 0, 0);
@@ -695,14 +580,9 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
             if constexpr (STATS) { stat2(2 * g, pv[4 * g], pv[4 * g + 1]); stat2(2 * g + 1, pv[4 * g + 2], pv[4 * g + 3]); }
             GR_FENCE();
         });
-        if constexpr (RT >= GR_NRES && !GR_VRES) {                    // not resident: BatchNorm sums now, then out to its spill slot
-            stats_all(a);
-            zstore(std::integral_constant<int, RT - GR_NRES>{}, a);
-            GR_FENCE();
-        }
-        // margin behind the matrix pipe's write-back (MFMA_SETTLE in mtfjsp_encoder.hip): hipcc copies the finished tile out of the
-        // accumulation file right here, at exactly the distance its hazard table asks for
-        if constexpr (!VT && GR_SETTLE) { asm volatile("s_nop 1"); GR_FENCE(); }          // (no operands: nothing for the register allocator to reconcile)
+        // two wait states of margin behind the matrix pipe's write-back (MFMA_SETTLE in mtfjsp_encoder.hip): hipcc copies the finished tile
+        // out of the accumulation file right here, at exactly the distance its hazard table asks for
+        if constexpr (!VT) { asm volatile("s_nop 1"); GR_FENCE(); }          // (no operands: nothing for the register allocator to reconcile)
     };
     // first Linear: tile RT's 16-wide operand sits at byte offset 32*(RT & 7) of buffer 0's rows
     auto consume_tile0 = [&](auto Tc) __attribute__((always_inline)) {
@@ -719,25 +599,21 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0f[1], x[0], a, 0, 0, 0);
         a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0f[0], x[0], a, 0, 0, 0);
         if constexpr (RT < GR_NRES) acc[RT] = a;
-        else if constexpr (GR_VRES) zs[(RT - GR_NRES) & 1] = a;
-        else {
-            stats_all(a);
-            zstore(std::integral_constant<int, RT - GR_NRES>{}, a);
-        }
-        if constexpr (RT > 0 && (GR_VRES || RT - 1 < GR_NRES)) stats_tile(std::integral_constant<int, RT - 1>{});
+        else zs[(RT - GR_NRES) & 1] = a;
+        if constexpr (RT > 0) stats_tile(std::integral_constant<int, RT - 1>{});
         __builtin_amdgcn_sched_barrier(0);
     };
     // Set-up of the final phase (pool + candidate gather): nothing here depends on the last boundary's statistics.  Run-time shape: behind
-    // that boundary.  Fixed shape (GR_FX_SETUP): inside it, behind its atomic — where the earlier boundaries request the next layer's weights
+    // that boundary.  Fixed shape: inside it, behind its atomic — where the earlier boundaries request the next layer's weights
     // — so that it runs while the boundary waits for the other workgroups; the boundary's own LDS barrier then also publishes s_wtab.
-    // The table's ring area (past the plane buffers 2, 3 of the layers without aggregation) is free there with GR_FOLD_DPP.
+    // The table's ring area (past the plane buffers 2, 3 of the layers without aggregation) is free there: the boundary folds its sums in registers.
     float *s_wtab = s_ring + 1024 + 4 * (2 * 32 * 36);            // [17][16]: row j = 1 for the first j of a chunk's 16 rows, 0 for the others (pool_tile)
-    static_assert(!(GR_FX_SETUP && GR_FOLD_DPP) || (1024 + 4 * (2 * 32 * 36)) * 4 >= (2 * GR_LOOK - 2) * GR_TILE, "s_wtab lies past the plane buffers in the ring area");
+    static_assert((1024 + 4 * (2 * 32 * 36)) * 4 >= (2 * GR_LOOK - 2) * GR_TILE, "s_wtab lies past the plane buffers in the ring area");
     unsigned warm_word = 0;
     int slot[GR_NT];                                              // candidate slot of this lane's row in every tile (-1: none)
     auto final_setup_a = [&]() __attribute__((always_inline)) {
         int tid_s = tid;
-        if constexpr (FXS) asm volatile("" : "+v"(tid_s));           // (inside the boundary: indices formed here, not kept from the prologue in scratch memory)
+        if constexpr (SH::FIXED) asm volatile("" : "+v"(tid_s));           // (inside the boundary: indices formed here, not kept from the prologue in scratch memory)
         for (int i = tid_s; i < 17 * 16; i += 256) s_wtab[i] = (i & 15) < (i >> 4) ? 1.0f : 0.0f;
         // ONE request per thread on behalf of the next launch (GinResArgs::warm): thread (blockIdx / 8) * 256 + tid of this XCD's workgroups
         // takes that line of the concatenated buffers (lines beyond the XCD's thread count are not requested); the word is dropped behind
@@ -755,9 +631,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         }
     };
     auto final_setup_b = [&]() __attribute__((always_inline)) {
-#ifndef GR_KEEP_MASKS
         asm volatile("" : "+v"(n_l));                                 // (the row indices of this phase are formed here, not kept from the layers)
-#endif
 #pragma unroll
         for (int rt = 0; rt < GR_NT; rt++) slot[rt] = (GR_ABL & 32) ? -1 : s_rowcand[rt * 32 + n_l];
     };
@@ -766,23 +640,16 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
     auto layer_boundary = [&](auto Kc) __attribute__((always_inline)) {
         constexpr int k = decltype(Kc)::value;
         GR_STAMP_AT(4 + 4 * k);
-        if constexpr (GR_VRES && GR_NT > GR_NRES) {               // the last tile's sums (it has no successor to take them beside)
+        if constexpr (GR_NT > GR_NRES) {                          // the last tile's sums (it has no successor to take them beside)
             asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");     // (its matrix instructions were written as text: no compiler-inserted wait before the reads)
             stats_all(zs[(GR_NT - 1 - GR_NRES) & 1]);
         }
-#if GR_FOLD_DPP
-        (void)fold_stats;
         const float colsum = fold_stats_dpp();                    // lane n of a half wave: value n of its 32 (see above)
         int lane_b = lane;
-        if constexpr (FXS && k == 5) asm volatile("" : "+v"(lane_b));   // (the boundary that holds the final phase's set-up forms its word index afresh: one register pair less across the layers)
+        if constexpr (SH::FIXED && k == 5) asm volatile("" : "+v"(lane_b));   // (the boundary that holds the final phase's set-up forms its word index afresh: one register pair less across the layers)
         const int n_b = lane_b & 31, h_b = lane_b >> 5;
         const int kind = n_b >> 4, scol = 32 * wave + 8 * ((n_b & 15) >> 2) + 4 * h_b + (n_b & 3);
         constexpr int PAIR = 16;                                  // the lane holding the other kind of the same column
-#else
-        const float colsum = fold_stats();                        // (GR_VRES 0: tile 17's sums were taken when it was stored)
-        const int kind = tid & 1, scol = tid >> 1;
-        constexpr int PAIR = 1;
-#endif
         const int sidx = 2 * scol + kind;                         // this thread's (column, sum | sumsq) word pair
         if (k == 1) GR_STAMP_AT(2);
         // one integer atomic, fire and forget
@@ -804,7 +671,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         // statistics' atomics queue behind 64 KB of loads in the in-order memory pipeline and every boundary gets 0.4 to 1.9 us longer.)
         const float ga = A.gamma[k][scol], be = A.beta[k][scol];
         if constexpr (k < 5) load_weights(k + 1);
-        else if constexpr (FXS) { final_setup_a(); final_setup_b(); }
+        else if constexpr (SH::FIXED) { final_setup_a(); final_setup_b(); }
         GR_STAMP_AT(5 + 4 * k);
         // every thread collects its own (column, kind) from the 8 dispatch groups: a word is complete when it carries its group's size
         // in the count field
@@ -872,7 +739,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
             const float2 y = *reinterpret_cast<const float2 *>(s_feat + n1 * 12 + fo);
             // gcn:125-153 (A_w @ h) / nnz_row on the raw features; small-integer weights, <= 3 terms: f32 FMA chain
             float v[4] = {__builtin_fmaf(w1, y.x, __builtin_fmaf(w0, x.x, o.x)) * inv, __builtin_fmaf(w1, y.y, __builtin_fmaf(w0, x.y, o.y)) * inv, 0.f, 0.f};
-            if (!FXD && row >= nrows) { v[0] = 0.f; v[1] = 0.f; }
+            if (!SH::FIXED && row >= nrows) { v[0] = 0.f; v[1] = 0.f; }
             uint2 p0, p1, p2;
             split3x4(v, p0, p1, p2);                              // elements 2, 3 are padding
             unsigned char *d = s_planes + r * GR_ROWB + 32 * (rt & 7) + 4 * fk;
@@ -906,37 +773,19 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
     // allocator resolves through scratch memory)
     gr_static_for<5>([&](auto Lc) __attribute__((always_inline)) {
         constexpr int layer = decltype(Lc)::value + 1;
-#ifndef GR_KEEP_MASKS                     // (A/B: -DGR_KEEP_MASKS is the code before this change)
-        if constexpr (FXD) asm volatile("" : "+v"(n_l));
+        if constexpr (SH::FIXED) asm volatile("" : "+v"(n_l));
         else asm volatile("" : "+s"(nrows_l), "+v"(n_l));
-#endif
         if constexpr (layer != 3) {
             gr_static_for<GR_LOOK>([&](auto Ic) __attribute__((always_inline)) { produce_tile(Ic, plane_buf(decltype(Ic)::value)); });
             LDS_BARRIER();
-            unsigned *cnt = s_cnt + (layer - 1) * (GR_NT / GR_GRP);
             gr_static_for<GR_NT>([&](auto Tc) __attribute__((always_inline)) {
                 constexpr int RT = decltype(Tc)::value;
-                constexpr int step = RT / GR_GRP, back = GR_LOOK / GR_GRP;
-                if constexpr (GR_LOOK > GR_GRP && RT % GR_GRP == 0 && step >= back) {
-                    // this group's planes were written during group step - back, by all four waves (each its 32 columns), after they had
-                    // finished reading the group that held these buffers before: one counter says both
-                    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&cnt[step - back], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < 4u)
-                        __builtin_amdgcn_s_sleep(1);
-                    asm volatile("" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                }
                 consume_tile(Tc);                                 // produces tile RT + GR_LOOK between its matrix instructions
                 GR_PIN_V();
-                if constexpr (RT % GR_GRP == GR_GRP - 1) {
-                    if constexpr (GR_LOOK > GR_GRP) {             // (LDS executes a wave's operations in issue order: the add lands after its plane writes and reads)
-                        asm volatile("" ::: "memory");
-                        if (lane == 0) __hip_atomic_fetch_add(&cnt[step], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    } else LDS_BARRIER();                         // one barrier per group of tiles
-                }
+                if constexpr (RT % GR_GRP == GR_GRP - 1) LDS_BARRIER();      // one barrier per group of tiles
                 __builtin_amdgcn_sched_barrier(0);
             });
-            if constexpr (GR_LOOK > GR_GRP) LDS_BARRIER();        // (the boundary parks its sums in the ring area, i.e. in plane buffers)
-            static_assert(GR_NT % GR_GRP == 0 && GR_GRP >= 1 && (GR_LOOK == GR_GRP || GR_LOOK == 2 * GR_GRP) && GR_LOOK <= GR_NRES, "tile groups");
+            static_assert(GR_NT % GR_GRP == 0 && GR_GRP >= 1 && GR_LOOK == GR_GRP && GR_LOOK <= GR_NRES, "tile groups");
         } else {
             // gcn:125-149: (A_w @ h) / nnz_row with h = relu(bn_outer0(z)), A_w incl. the self loop.  h tiles go through a ring of
             // GR_RING tiles in LDS; tile rt's rows and their in-edge sources (same instance, T <= 65 rows) lie in tiles rt-2..rt+2
@@ -995,8 +844,8 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
                 constexpr bool NEXT = RT + 1 < GR_NT && !(GR_ABL & 1);
                 constexpr bool WH = RT + 4 < GR_NT && !(GR_ABL & 1);
                 constexpr int WT = WH ? RT + 4 : RT;
-                constexpr bool STATS = RT > 0 && (GR_VRES || RT - 1 < GR_NRES) && !(GR_ABL & 4);
-                constexpr bool VT = GR_VRES && RT >= GR_NRES;
+                constexpr bool STATS = RT > 0 && !(GR_ABL & 4);
+                constexpr bool VT = RT >= GR_NRES;
                 const unsigned char *xa = xa0 + (RT & 1) * GR_TILE;
                 gr_h8 xf[2][2];
 #pragma unroll
@@ -1010,10 +859,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
                     s4 = *reinterpret_cast<const float4 *>(bnw + 32 * wave + 4 * h);
                     h4 = *reinterpret_cast<const float4 *>(bnw + HD + 32 * wave + 4 * h);
                 }
-                f32x16 atmp;
-                f32x16 &a = RT < GR_NRES ? acc[RT < GR_NRES ? RT : 0] : VT ? zs[RT >= GR_NRES ? (RT - GR_NRES) & 1 : 0] : atmp;
-                // the spilled tiles' old values: requested two tiles before they are turned into h
-                if constexpr (RT + 6 >= GR_NRES && RT + 6 < GR_NT) zload(std::integral_constant<int, RT + 6 - GR_NRES>{});
+                f32x16 &a = GR_TILEVAL(RT);
                 gr_static_for<4>([&](auto Pc) __attribute__((always_inline)) {
                     constexpr int g = decltype(Pc)::value;
                     const gr_h8 *x0 = xf[0], *x1 = xf[1];
@@ -1021,7 +867,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
                     const f32x16 &pv = GR_TILEVAL(RT > 0 ? RT - 1 : 0);
                     const int chl = 8 * wave + 2 * g + h;
                     float4 o = make_float4(0.f, 0.f, 0.f, 0.f), x = o, y = o;
-                    f32x2 v01 = {0.f, 0.f}, v23 = v01, e01 = v01, e23 = v01, u01 = v01, u23 = v01;
+                    f32x2 v01 = {0.f, 0.f}, v23 = v01, u01 = v01, u23 = v01;
                     gr_h2 p01 = {0, 0}, p23 = p01, q01 = p01, q23 = p01;
                     const f32x2 W0 = {r.w0, r.w0}, W1 = {r.w1, r.w1}, IV = {r.inv, r.inv};
                     auto M = [&](int ks, int wp, int xp) __attribute__((always_inline)) {
@@ -1060,23 +906,16 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
                     // slice 4
                     M(2 * g + 1, 1, 0);
                     if constexpr (g < 3) xf[0][1] = *reinterpret_cast<const gr_h8 *>(xa + GR_PLANE + 32 * (2 * g + 2));
-                    if constexpr (NEXT) { v01 = gr_mul2(v01, IV); v23 = gr_mul2(v23, IV); p01 = __builtin_convertvector(v01, gr_h2); p23 = __builtin_convertvector(v23, gr_h2);
-                                          if constexpr (!GR_MIX) { e01 = __builtin_convertvector(p01, f32x2); e23 = __builtin_convertvector(p23, f32x2); } }
+                    if constexpr (NEXT) { v01 = gr_mul2(v01, IV); v23 = gr_mul2(v23, IV); p01 = __builtin_convertvector(v01, gr_h2); p23 = __builtin_convertvector(v23, gr_h2); }
                     GR_FENCE();
                     // slice 5
                     M(2 * g + 1, 0, 0);
-                    if constexpr (NEXT) { if constexpr (GR_MIX == 2) { q01 = gr_rem16(v01, p01); q23 = gr_rem16(v23, p23); }
-                                          else { if constexpr (GR_MIX) { v01 = gr_rem2(v01, p01); v23 = gr_rem2(v23, p23); } else { v01 = gr_sub2(v01, e01); v23 = gr_sub2(v23, e23); } q01 = __builtin_convertvector(v01, gr_h2); q23 = __builtin_convertvector(v23, gr_h2); }
+                    if constexpr (NEXT) { q01 = gr_rem16(v01, p01); q23 = gr_rem16(v23, p23);
                                           *reinterpret_cast<uint2 *>(dst + 16 * g) = make_uint2(__builtin_bit_cast(unsigned, p01), __builtin_bit_cast(unsigned, p23));
                                           *reinterpret_cast<uint2 *>(dst + 16 * g + GR_PLANE) = make_uint2(__builtin_bit_cast(unsigned, q01), __builtin_bit_cast(unsigned, q23)); }
                     GR_FENCE();
                 });
-                if constexpr (RT >= GR_NRES && !GR_VRES) {
-                    stats_all(a);
-                    zstore(std::integral_constant<int, RT - GR_NRES>{}, a);
-                    GR_FENCE();
-                }
-                if constexpr (!VT && GR_SETTLE) { asm volatile("s_nop 1"); GR_FENCE(); }          // (no operands: nothing for the register allocator to reconcile)
+                if constexpr (!VT) { asm volatile("s_nop 1"); GR_FENCE(); }          // (no operands: nothing for the register allocator to reconcile)
             };
             write_h(std::integral_constant<int, 0>{}); write_h(std::integral_constant<int, 1>{}); write_h(std::integral_constant<int, 2>{});
             write_h(std::integral_constant<int, 3>{});
@@ -1113,25 +952,23 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         float *s_part = reinterpret_cast<float *>(s_planes);      // [2 * GR_NT chunks][2 segments][128] = 36 KB: the plane buffers and the first 2 KB of the ring area
         static_assert(2 * GR_NT * 2 * HD * 4 <= 2 * GR_TILE + 4096, "partial pool sums: plane buffers + 4 KB");
         float *tb = s_ring + 1024 + wave * (2 * 32 * 36);         // transposition buffers: ring area past those 4 KB
-        if constexpr (!FXS) final_setup_a();
+        if constexpr (!SH::FIXED) final_setup_a();
         float4 S[4], Hs[4];
 #pragma unroll
         for (int g = 0; g < 4; g++) {
             S[g] = *reinterpret_cast<const float4 *>(s_bn + 32 * wave + 8 * g + 4 * h_f);
             Hs[g] = *reinterpret_cast<const float4 *>(s_bn + HD + 32 * wave + 8 * g + 4 * h_f);
         }
-        if constexpr (GR_NT - GR_NRES >= 1) zload(std::integral_constant<int, 0>{});
-        if constexpr (GR_NT - GR_NRES >= 2) zload(std::integral_constant<int, 1>{});
         const int c = lane_f & 31;
         int left = ((16 * h_f) / T + 1) * T - 16 * h_f;                   // rows of the instance of this lane's first row (16h of tile 0) still ahead
         // (fixed shape: a constant per tile and half wave, gr_left_at)
         auto left_at = [&](auto Rc) __attribute__((always_inline)) {
             constexpr int rt = decltype(Rc)::value;
-            constexpr int FT = FXD ? SH::T : GR_MINT;
-            if constexpr (FXD) return h_f ? gr_left_at(FT, 1, rt) : gr_left_at(FT, 0, rt);
+            constexpr int FT = SH::FIXED ? SH::T : GR_MINT;
+            if constexpr (SH::FIXED) return h_f ? gr_left_at(FT, 1, rt) : gr_left_at(FT, 0, rt);
             else return left;
         };
-        if constexpr (!FXS) { final_setup_b(); LDS_BARRIER(); }       // the plane buffers are no longer read (fixed shape: the last boundary's barrier)
+        if constexpr (!SH::FIXED) { final_setup_b(); LDS_BARRIER(); }       // the plane buffers are no longer read (fixed shape: the last boundary's barrier)
         // candidate rows: one base for the workgroup, a 32-bit offset per row
         unsigned char *const cbase = reinterpret_cast<unsigned char *>(A.cand_feat + (size_t)inst0 * Jn * HD);
         const unsigned coff = (unsigned)(32 * wave + 4 * h_f) * 4u;
@@ -1170,7 +1007,7 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
             const float sa = sa2[0] + sa2[1];
             float *pp = s_part + ((2 * rt + h_f) * 2) * HD + 32 * wave + c;
             pp[0] = lf >= 16 ? tot : sa; pp[HD] = lf >= 16 ? 0.f : tot - sa;
-            if constexpr (!FXD) {
+            if constexpr (!SH::FIXED) {
                 left -= 32;                                           // on to this lane's rows of the next tile (T >= 16: at most two instances further)
                 if (left <= 0) left += T;
                 if (left <= 0) left += T;
@@ -1191,12 +1028,12 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
 #pragma unroll
             for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(wb + n_f * 36 + 8 * g + 4 * h_f) = v[g];
             if (slot[rt] >= 0) {
-                float *d = FXD ? reinterpret_cast<float *>(cbase + ((unsigned)slot[rt] * (unsigned)(HD * 4) + coff))
+                float *d = SH::FIXED ? reinterpret_cast<float *>(cbase + ((unsigned)slot[rt] * (unsigned)(HD * 4) + coff))
                                : A.cand_feat + ((size_t)inst0 * Jn + slot[rt]) * HD + 32 * wave + 4 * h_f;
 #pragma unroll
                 for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(d + 8 * g) = v[g];
             }
-            if (!FXD && A.h_nodes && rt * 32 + n_l < nrows) {
+            if (!SH::FIXED && A.h_nodes && rt * 32 + n_l < nrows) {
                 float *d = A.h_nodes + (grow0 + rt * 32 + n_l) * HD + 32 * wave + 4 * h_f;
 #pragma unroll
                 for (int g = 0; g < 4; g++) *reinterpret_cast<float4 *>(d + 8 * g) = v[g];
@@ -1213,13 +1050,13 @@ __global__ __launch_bounds__(256) void GR_KERNEL(GinResArgs A)
         // instance not added — instead of a loop with a run-time trip count whose reads each waited for the one before: 2.0 -> ~0.7 us of this phase's tail.
         // Same additions in the same order.)
         static_assert(GR_MAXT <= 65, "an instance spans at most five 16-row chunks");
-        if constexpr (FXT) {
+        if constexpr (SH::FIXED) {
             // (an opaque copy of the thread index: tid + 256 k is what the prologue's copies use too, and hipcc would keep those seven registers
             // for the whole kernel — through scratch memory)
             int tid_f = tid;
             asm volatile("" : "+v"(tid_f));
             // fixed shape: SH::IPC * HD / 256 items per thread and at most NCH chunks per instance, every read requested before the first sum
-            constexpr int FT = FXT ? SH::T : GR_MINT, NIT = FXT ? SH::IPC * HD / 256 : 1, NCH = gr_max_chunks(FT);     // (the other shape: placeholders, not compiled in)
+            constexpr int FT = SH::FIXED ? SH::T : GR_MINT, NIT = SH::FIXED ? SH::IPC * HD / 256 : 1, NCH = gr_max_chunks(FT);     // (the other shape: placeholders, not compiled in)
             float pv[NIT][NCH];
 #pragma unroll
             for (int it = 0; it < NIT; it++) {
