@@ -25,6 +25,7 @@
 #include <string.h>
 #include <algorithm>
 #include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -2952,7 +2953,8 @@ struct mtfjsp_encoder {
     std::map<std::string, float *> w;       // device copies, torch layout
     std::map<std::string, float *> wt;      // transposed [in,out] copies of the 128-wide Linear weights (split per 128-block of `in`)
     std::map<std::string, std::vector<float>> hostw;   // host copies of gat_layer.W / m_fea_*_fcl.weight (inputs of the fused projections)
-    std::map<std::string, float *> wfused;  // per prefix + "1"/"2": (m_fea_k_fcl.weight^T . gat_layer.W)^T, [128,6] / [128,8]
+    std::map<std::string, float *> wfused;  // per prefix + "1"/"2": (m_fea_k_fcl.weight^T . gat_layer.W)^T, [128,6] / [128,8]; + "q": both as k_gat3x's operand image
+    std::set<std::string> wfused_stale;     // keys of wfused whose buffer holds the projection of weights loaded over since: filled again, in place, by the next forward that needs it
     std::map<std::string, size_t> wx6_bytes;   // size of each wx6 image
     std::map<std::string, size_t> wx32_bytes;  // size of each wx32 image (a GIN Linear has both: one map keyed by name held whichever was uploaded last)
     std::map<std::string, void *> wx6;      // 128x128 Linear weights as 2 f16 planes (scaled) in k_gemm_x6's register-image order; GAT W / first Linear: 3 bf16 planes
@@ -2961,6 +2963,7 @@ struct mtfjsp_encoder {
     std::map<std::string, float> wx6_sinv;  // the same for the f16 images in wx6
     std::map<std::string, float *> wimg;    // the same blocks as per-wave register images for k_heads: [block][wave 8][g 8][lane 64][4]
     std::vector<void *> owned;
+    size_t owned_bytes = 0;                 // device bytes behind `owned` (mtfjsp_encoder_device_allocations)
     int num_cu = 256;
     // workspaces
     float *zA = nullptr, *zB = nullptr;     // [B*T,128] ping-pong
@@ -3064,6 +3067,7 @@ static int dalloc(mtfjsp_encoder *e, Tp **ptr, size_t n)
 {
     HIPCHK(e, hipMalloc((void **)ptr, n * sizeof(Tp)));
     e->owned.push_back(*ptr);
+    e->owned_bytes += n * sizeof(Tp);
     return 0;
 }
 
@@ -3262,6 +3266,10 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
             }
         }
     }
+    // The clears above are hipMemset calls on the null stream; HIP's interface does not promise that a fill of device memory has run when the
+    // call returns.  The caller's stream may be a non-blocking one, which the null stream does not order: the fills are waited for here, once,
+    // so that no first forward can overtake them (before, only the census of a shape eligible for the single-launch kernel did that)
+    if (hipDeviceSynchronize() != hipSuccess) { g_enc_err = "hipDeviceSynchronize failed"; mtfjsp_encoder_destroy(e); return MTFJSP_ERR_HIP; }
     *out = e;
     return MTFJSP_OK;
 }
@@ -3363,6 +3371,10 @@ extern "C" int mtfjsp_encoder_load_weight_host(mtfjsp_encoder_t e, const char *n
         }
     }
     HIPCHK(e, hipSetDevice(e->cfg.device_id));
+    // A tensor loaded again is written over the buffers the forwards read, by blocking copies that no stream orders: every forward
+    // enqueued on the handle's stream so far finishes first (it keeps the weights it was enqueued under), and every copy below has
+    // landed when this call returns (forwards enqueued afterwards see the new tensor).  Once per tensor and update: not a hot path.
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     float *d = nullptr;
     auto it = e->w.find(key);
     if (it != e->w.end()) d = it->second;
@@ -3373,7 +3385,8 @@ extern "C" int mtfjsp_encoder_load_weight_host(mtfjsp_encoder_t e, const char *n
         key.find("m_fea_2_fcl.weight") != std::string::npos) {
         e->hostw[key].assign(data, data + numel);
         const std::string prefix = key.substr(0, key.find('.') + 1);
-        e->wfused.erase(prefix + "1"); e->wfused.erase(prefix + "2"); e->wfused.erase(prefix + "q");   // rebuilt at the next forward (buffers stay owned)
+        for (const char *suffix : {"1", "2", "q"})                   // filled again at the next forward, into the same device buffers
+            if (e->wfused.count(prefix + suffix)) e->wfused_stale.insert(prefix + suffix);
     }
     if (numel == (int64_t)HD * 12 && key.find("mlps.0.linears.0.weight") != std::string::npos) {
         // k_gemm_x6<PRO_GIN0>: the 12 -> 128 first Linear as ONE k-step of 32 (k >= 12 zero), exact 3-way bf16 split:
@@ -3810,7 +3823,7 @@ static int run_gin_resident(mtfjsp_encoder *e, const GinPlan &gp, const GinWeigh
             a.warm[a.nwarm] = it->second; a.warm_lines[a.nwarm] = (unsigned)(bt->second / 128); a.nwarm++;
         }
         auto q = e->wfused.find("machine_actor.q");               // the GAT projection's operand image (8 KB), once it has been formed
-        if (q != e->wfused.end() && a.nwarm < GR_MAXWARM) { a.warm[a.nwarm] = q->second; a.warm_lines[a.nwarm] = 64; a.nwarm++; }
+        if (q != e->wfused.end() && !e->wfused_stale.count("machine_actor.q") && a.nwarm < GR_MAXWARM) { a.warm[a.nwarm] = q->second; a.warm_lines[a.nwarm] = 64; a.nwarm++; }
     }
     if (++e->res_launches == e->res_fail_at) a.expect_extra = 1u;      // (diagnostic) this launch's barriers never complete
 #ifdef GR_STAMP
@@ -3878,25 +3891,34 @@ static std::vector<float> fused_projection_host(mtfjsp_encoder *e, const std::st
         }
     return f;
 }
+// wfused[key] := f.  The device buffer is allocated the first time and written over afterwards (its size never changes): a blocking
+// copy that no stream orders, so what is enqueued on the handle's stream — an earlier forward may still read the buffer — finishes first
+static int fused_upload(mtfjsp_encoder *e, const std::string &key, const std::vector<float> &f, const float **out)
+{
+    float *d = nullptr;
+    auto it = e->wfused.find(key);
+    if (it != e->wfused.end()) { d = it->second; HIPCHK(e, hipStreamSynchronize(e->stream)); }
+    else if (dalloc(e, &d, f.size())) return MTFJSP_ERR_HIP;
+    HIPCHK(e, hipMemcpy(d, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+    e->wfused[key] = d;
+    e->wfused_stale.erase(key);
+    *out = d;
+    return MTFJSP_OK;
+}
 static int fused_projection(mtfjsp_encoder *e, const std::string &pre, int which, const float **out)
 {
     const std::string key = pre + (which == 1 ? "1" : "2");
     auto it = e->wfused.find(key);
-    if (it != e->wfused.end()) { *out = it->second; return MTFJSP_OK; }
+    if (it != e->wfused.end() && !e->wfused_stale.count(key)) { *out = it->second; return MTFJSP_OK; }
     const std::vector<float> f = fused_projection_host(e, pre, which);
-    float *d = nullptr;
-    if (dalloc(e, &d, f.size())) return MTFJSP_ERR_HIP;
-    HIPCHK(e, hipMemcpy(d, f.data(), f.size() * 4, hipMemcpyHostToDevice));
-    e->wfused[key] = d;
-    *out = d;
-    return MTFJSP_OK;
+    return fused_upload(e, key, f, out);
 }
 // both fused projections as the B operands of v_mfma_f32_16x16x4_f32 (GatArgs::Wq), cached like them
 static int fused_projection_image(mtfjsp_encoder *e, const std::string &pre, const float **out)
 {
     const std::string key = pre + "q";
     auto it = e->wfused.find(key);
-    if (it != e->wfused.end()) { *out = it->second; return MTFJSP_OK; }
+    if (it != e->wfused.end() && !e->wfused_stale.count(key)) { *out = it->second; return MTFJSP_OK; }
     const std::vector<float> f1 = fused_projection_host(e, pre, 1), f2 = fused_projection_host(e, pre, 2);
     std::vector<float> img((size_t)8 * 64 * 4);
     for (int c = 0; c < 8; c++)
@@ -3905,12 +3927,7 @@ static int fused_projection_image(mtfjsp_encoder *e, const std::string &pre, con
                 const int kk = 4 * ks + (lane >> 4), col = 16 * c + (lane & 15);
                 img[((size_t)c * 64 + lane) * 4 + ks] = kk < 6 ? f1[(size_t)col * 6 + kk] : kk < 8 ? 0.f : f2[(size_t)col * 8 + (kk - 8)];
             }
-    float *d = nullptr;
-    if (dalloc(e, &d, img.size())) return MTFJSP_ERR_HIP;
-    HIPCHK(e, hipMemcpy(d, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-    e->wfused[key] = d;
-    *out = d;
-    return MTFJSP_OK;
+    return fused_upload(e, key, img, out);
 }
 // h_pooled == nullptr: leave `node` pre-BatchNorm for a consumer that normalises and pools it itself (k_heads); *slot_out = the
 // accumulator slot holding the column sums.
@@ -4728,6 +4745,14 @@ extern "C" int mtfjsp_encoder_peek_nodes_host(mtfjsp_encoder_t e, float *out_hos
     HIPCHK(e, hipSetDevice(e->cfg.device_id));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipMemcpy(out_host, e->node, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    return MTFJSP_OK;
+}
+// diagnostic: device buffers the handle owns and their total size (every one of them is freed by mtfjsp_encoder_destroy only)
+extern "C" int mtfjsp_encoder_device_allocations(mtfjsp_encoder_t e, int64_t *buffers_out, int64_t *bytes_out)
+{
+    if (!e) return MTFJSP_ERR_ARG;
+    if (buffers_out) *buffers_out = (int64_t)e->owned.size();
+    if (bytes_out) *bytes_out = (int64_t)e->owned_bytes;
     return MTFJSP_OK;
 }
 extern "C" int mtfjsp_encoder_peek_gin_res_host(mtfjsp_encoder_t e, float *cand_feat_host, int64_t count, uint64_t *stats_host, uint32_t *flags_host)

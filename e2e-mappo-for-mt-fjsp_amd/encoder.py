@@ -210,6 +210,12 @@ class Encoder:
         capi.check(self.L.mtfjsp_encoder_peek_nodes_host(self.h, out.ctypes.data, out.size), self.h, enc=True)
         return out
 
+    def device_allocations(self):
+        """diagnostic: (device buffers this handle owns, their total bytes); constant across weight reloads once every forward has run"""
+        n, nbytes = C.c_int64(0), C.c_int64(0)
+        capi.check(self.L.mtfjsp_encoder_device_allocations(self.h, C.byref(n), C.byref(nbytes)), self.h, enc=True)
+        return int(n.value), int(nbytes.value)
+
     def gin_res_kernel_name(self):
         """the instantiation of the single-launch GIN kernel this handle's last forward ran (None: none yet)"""
         name = self.L.mtfjsp_encoder_gin_res_kernel_name(self.h)

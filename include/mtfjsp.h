@@ -616,7 +616,14 @@ int mtfjsp_encoder_destroy(mtfjsp_encoder_t e);
 const char *mtfjsp_encoder_last_error(mtfjsp_encoder_t e);
 int mtfjsp_encoder_set_stream(mtfjsp_encoder_t e, void *hip_stream);
 /* Weights by the reference's state_dict key, prefixed "job_actor." or "machine_actor."
- * (e.g. "job_actor.encoder.feature_extract.mlps.0.linears.0.weight"); f32, row-major as in torch. */
+ * (e.g. "job_actor.encoder.feature_extract.mlps.0.linears.0.weight"); f32, row-major as in torch.
+ * Loading a tensor again on a used handle (rollout, update on the host, load, rollout) writes over the same device buffers — the plain
+ * copy and every image derived from it; nothing is allocated after the first load and the first forward of each kind.
+ * Ordering: the call first waits for everything enqueued on the handle's stream (mtfjsp_encoder_set_stream), so a forward enqueued
+ * BEFORE it computes with the weights it was enqueued under, and returns when its copies have landed, so a forward enqueued AFTER
+ * it computes with the new tensor (the fused GAT projections, which depend on three tensors, are formed by the next forward that
+ * needs them, after the same wait).  data_host may be freed on return.  Work on OTHER streams that reads this handle's outputs is
+ * not waited for; loading between the two forwards of one decision mixes two policies, as it would anywhere. */
 int mtfjsp_encoder_load_weight_host(mtfjsp_encoder_t e, const char *name, const float *data_host, int64_t numel);
 int mtfjsp_encoder_weights_ready(mtfjsp_encoder_t e);     /* 0 when every required tensor has been loaded */
 
@@ -769,6 +776,11 @@ int mtfjsp_encoder_range_fallbacks(mtfjsp_encoder_t e, int64_t *count_out, int32
  * written by the separate GAT launches (k_gat3x, k_headsx_gat3x) and by the global critic; the three-in-one launch keeps its node
  * rows in LDS (round 6) and leaves the buffer alone unless MTFJSP_FUSED3_NODES_HBM=1. */
 int mtfjsp_encoder_peek_nodes_host(mtfjsp_encoder_t e, float *out_host, int64_t count);
+/* diagnostic (tests/test_weight_reload_gpu.py): the device buffers this handle has allocated so far and their total size in bytes
+ * (either pointer may be NULL).  Workspaces are allocated by mtfjsp_encoder_create, weight buffers and their derived images the first
+ * time a tensor is loaded or a forward needs them; loading a tensor again reuses them, so both figures stay constant once every
+ * tensor has been loaded and every kind of forward has run once.  Nothing is freed before mtfjsp_encoder_destroy.  No GPU work. */
+int mtfjsp_encoder_device_allocations(mtfjsp_encoder_t e, int64_t *buffers_out, int64_t *bytes_out);
 /* Which instantiation of the single-launch GIN kernel serves a forward — the library's one statement of the rule (csrc/mtfjsp_gin_res_select.h; every
  * launch goes through it).  No GPU involved.  batch instances of rows_per_instance (= n_job * n_machine) node rows on num_cu compute units; n_job bounds
  * the candidate table; candidates = candidates per instance of the forward (n_job for the job actor, 0 for the global critic); node_output != 0 when

@@ -146,10 +146,10 @@ def critic_weights(npz):
     return {k[len("w_gc."):]: npz[k] for k in npz.files if k.startswith("w_gc.")}
 
 
-def _gat_machine_nodes(w, mfea1, mfea2, B, M):
+def _gat_machine_nodes(w, mfea1, mfea2, B, M, dtype=torch.float32):
     """shared by the machine actor and the global critic: input projections, 3x the same GATLayer, node mean, BN"""
-    f1 = torch.as_tensor(np.asarray(mfea1), dtype=torch.float64).float().reshape(B * M, 6)
-    f2 = torch.as_tensor(np.asarray(mfea2), dtype=torch.float64).float().reshape(B * M, 8)
+    f1 = torch.as_tensor(np.asarray(mfea1), dtype=torch.float64).float().reshape(B * M, 6).to(dtype)
+    f2 = torch.as_tensor(np.asarray(mfea2), dtype=torch.float64).float().reshape(B * M, 8).to(dtype)
     n0 = f1 @ w["m_fea_1_fcl.weight"].t()
     n1 = f2 @ w["m_fea_2_fcl.weight"].t()
     W = w["gat_layer.W"]
@@ -169,10 +169,11 @@ def _gat_machine_nodes(w, mfea1, mfea2, B, M):
     return _bn((n0 + n1) / 2, w["bn.weight"], w["bn.bias"]).reshape(B, M, Hd)
 
 
-def global_critic_forward(w, tfea, ell_col, ell_val, mfea1, mfea2, B, T, M):
+def global_critic_forward(w, tfea, ell_col, ell_val, mfea1, mfea2, B, T, M, dtype=torch.float32):
     """Global_Critic_JointAction_GAT.forward (ac:587-750): its own GIN encoder -> graph pool, its own GAT
-    machine path -> pool, MLPCritic(256 -> 128 -> 128 -> 4) on [pooled_m, pooled_o]."""
-    w = {k: torch.as_tensor(v) for k, v in w.items()}
-    _, h_o = gin_encoder(w, tfea, ell_col, ell_val, B, T)
-    h_m = _gat_machine_nodes(w, mfea1, mfea2, B, M).mean(1)
+    machine path -> pool, MLPCritic(256 -> 128 -> 128 -> 4) on [pooled_m, pooled_o].
+    dtype=torch.float64: the same network in binary64 on the f32-rounded inputs and weights (yardstick, not the reference)."""
+    w = {k: torch.as_tensor(v).to(dtype) for k, v in w.items()}
+    _, h_o = gin_encoder(w, tfea, ell_col, ell_val, B, T, dtype=dtype)
+    h_m = _gat_machine_nodes(w, mfea1, mfea2, B, M, dtype=dtype).mean(1)
     return _mlp_tanh(torch.cat([h_m, h_o], -1), w, "critic").numpy()
