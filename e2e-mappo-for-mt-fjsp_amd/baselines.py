@@ -463,6 +463,97 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
     return out
 
 
+# ---- a walk on plans (csrc/mtfjsp_walk.hip): the local search's round with an acceptance rule that can leave a local optimum
+def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_MOVES, tabu=0, slack=None, late=8, left_shift=False,
+                chunk=None, device=0, obs_dtype="f32", name="WS"):
+    """`local_search` that may step sideways and uphill: start, the instances, args, K, seed, moves (CRIT_MOVES included), left_shift and
+    chunk are `local_search`'s, and so are the neighbours of a round (`DeviceBatchEnv.plan_neighbours`, draws keyed by (seed, instance,
+    copy, round)) and their replay.  What differs is the acceptance (`DeviceBatchEnv.walk_accept`; include/mtfjsp.h has the rule): of the
+    neighbours whose SCHEDULE (`state_signature`) is neither the incumbent's own nor one of the last `tabu` schedules the walk left
+    (0..1024; 0: no ring) the best becomes the incumbent if it is strictly better, or within `slack` of the incumbent (None: off; one
+    number; or a sequence of `rounds` numbers, a threshold schedule: 0.0 admits sideways steps, inf always moves — with a ring that is
+    tabu search), or not above the incumbent's objective `late` rounds ago (0..4096; 0: off — late-acceptance hill climbing).  The
+    incumbent can get worse, so the best plan met is kept on the device beside it and is what the result holds.
+    A round: plan_neighbours, reset, T steps, final_costs, state_signature, walk_accept — T + 5 launches (T + 6 with directed moves:
+    critical_path of the next incumbent), no torch kernel, nothing read back before the last round.  The state is per pass and the
+    draws are keyed by the instance's number in the whole set: the results do not depend on `chunk`.  After the last round the best
+    plans are replayed as `local_search` replays its plans.  rounds = 0 is a plain replay of `start`; K = 1 never moves.  With tabu = 0,
+    slack = None, late = 0 the walk is `local_search`: a copy of the incumbent's schedule is never strictly better.
+    The defaults are late acceptance alone: at J6M6E2 x 4096 it ends below the ring with slack = inf under both weightings.
+    -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout for the best plans, under PLANS {name: (task[N,T],
+       mach[N,T])}, and "start_obj" [N];  "history" [rounds, N]: the best Objective so far after every round (never rising);  "current"
+       [rounds, N]: the incumbent's;  "accepted" [rounds, N] int8: the kind of the move taken (MOVE_*), -1 where the walk stayed;  "why"
+       [rounds, N] int8: 0 no candidate, 1 refused, 2 better, 3 within the slack, 4 by the late ring, + 8 for a new best;  "barred"
+       [rounds, N] int32: neighbours with an objective that were the incumbent's schedule again or in the ring."""
+    N, T = CopyGroups.sizes(t, args)
+    K, R, moves, tabu, late = int(K), int(rounds), int(moves), int(tabu), int(late)
+    if not 1 <= K <= 4096:
+        raise ValueError("K must be 1..4096")
+    if R < 0 or not 1 <= moves <= (ALL_MOVES | CRIT_MOVES):
+        raise ValueError("rounds must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN | MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN")
+    if not 0 <= tabu <= 1024 or not 0 <= late <= 4096:
+        raise ValueError("tabu must be 0..1024 and late 0..4096")
+    if slack is None or np.ndim(slack) == 0:
+        slacks = [None if slack is None else float(slack)] * R
+    else:
+        slacks = [float(x) for x in slack]
+        if len(slacks) != R:
+            raise ValueError("slack must be None, one number or a sequence of `rounds` numbers")
+    _rule_names([(name,), ("start_obj",), ("history",), ("current",), ("accepted",), ("why",), ("barred",)])
+    st_task, st_mach = np.ascontiguousarray(start[0], np.int32), np.ascontiguousarray(start[1], np.int32)
+    if st_task.shape != (N, T) or st_mach.shape != (N, T):
+        raise ValueError("start must be (task [N,T], mach [N,T])")
+    with CopyGroups(t, p, tt, edge, args, K, chunk, copies=R > 0, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
+        n, dev, env, top = g.n, g.dev, g.env, g.top
+        path = None
+        if R:
+            obj0 = torch.empty(n * K, dtype=torch.float64, device=dev)
+            sig = torch.empty(n * K, dtype=torch.int64, device=dev)
+            col = torch.empty(R, n, dtype=torch.int32, device=dev)
+            hist, cur = torch.empty(R, n, dtype=torch.float64, device=dev), torch.empty(R, n, dtype=torch.float64, device=dev)
+            kind = torch.empty(R, n * K, dtype=torch.int8, device=dev)
+            why, barred = torch.empty(R, n, dtype=torch.int8, device=dev), torch.empty(R, n, dtype=torch.int32, device=dev)
+            state = env.walk_state(n, late, tabu)
+            if moves & CRIT_MOVES:                                      # every group's critical path: tasks, arcs, length
+                path = (torch.empty(n, T, dtype=torch.int32, device=dev), torch.empty(n, T, dtype=torch.int8, device=dev),
+                        torch.empty(n, dtype=torch.int32, device=dev))
+        for lo, m in g.passes():
+            cur_t = torch.as_tensor(np.ascontiguousarray(g.pad(st_task).T), device=dev)     # [T,n]: row s = the actions of step s
+            cur_m = torch.as_tensor(np.ascontiguousarray(g.pad(st_mach).T), device=dev)
+            src = None
+            if path is not None:                                        # the start plans' schedules, for round 0's directed moves
+                top.scaler_init()
+                top.reset(g.w3_top)
+                for s in range(T):
+                    top.step(cur_t[s], cur_m[s])
+                top.critical_path(None, None, *path)
+            for r in range(R):
+                out_t, out_m = g.plan_bufs(r)
+                env.plan_neighbours(K, cur_t, cur_m, src, seed, r, lo, moves, out_t, out_m, kind[r], critical=path)
+                g.replay(out_t, out_m, g.cost4, g.done)
+                env.state_signature(sig)
+                env.walk_accept(n, K, g.cost4, g.done, g.w, out_t, out_m, state, sig, r, r == 0, slacks[r], col[r], cur[r], hist[r], False,
+                                why[r], barred[r], obj0 if r == 0 else False)
+                if path is not None:                                    # of the next incumbents, while their state is still there (-1: an empty path)
+                    env.critical_path(col[r], None, *path)
+                cur_t, cur_m, src = out_t, out_m, col[r]
+            if R:
+                acc = torch.where((why & 7) < 2, torch.full_like(col, -1), kind.gather(1, col.clamp(min=0).long()).to(torch.int32)).to(torch.int8)
+                g.finish(state["best_task"], state["best_mach"], None, f"{name} walk", start_obj=obj0.view(n, K)[:, 0], history=hist, current=cur,
+                         accepted=acc, why=why, barred=barred)
+            else:
+                g.finish(cur_t, cur_m, None, f"{name} walk")
+    extra = ("history", "current", "accepted", "why", "barred")
+    r = g.collect(last_axis=extra)
+    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
+    if R:
+        out.update(start_obj=r["start_obj"], **{k: r[k] for k in extra})
+    else:
+        out.update(start_obj=out[name][2].copy(), history=np.zeros((0, N)), current=np.zeros((0, N)), accepted=np.zeros((0, N), np.int8),
+                   why=np.zeros((0, N), np.int8), barred=np.zeros((0, N), np.int32))
+    return out
+
+
 # ---- evolutionary search on plans (csrc/mtfjsp_evolve.hip): a population of P plans per instance, recombined generation by generation
 def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.8, p_mut=0.3, moves=ALL_MOVES, left_shift=False, chunk=None,
            device=0, obs_dtype="f32", name="GA"):

@@ -365,6 +365,59 @@ class DeviceBatchEnv:
                                                arc_out.data_ptr(), len_out.data_ptr()), self.h)
         return task_out, arc_out, len_out
 
+    # ---- a walk on plans (csrc/mtfjsp_walk.hip): acceptance with a tabu ring, a slack and a late ring in the local search's round
+    def walk_state(self, N, late_len=0, tabu_len=0):
+        """-> the state `walk_accept` keeps for N groups: dict(late [N,late_len] f64 or None, tabu [N,tabu_len] int64 (the unsigned words)
+        or None, tabu_n [N] int32 or None, best_obj [N] f64, best_task, best_mach [T,N] int32), uninitialised device tensors: the first
+        call (first=True) fills them"""
+        N, L, U, dev = int(N), int(late_len), int(tabu_len), self.device
+        return dict(late=torch.empty(N, L, dtype=torch.float64, device=dev) if L > 0 else None,
+                    tabu=torch.empty(N, U, dtype=torch.int64, device=dev) if U > 0 else None,
+                    tabu_n=torch.empty(N, dtype=torch.int32, device=dev) if U > 0 else None,
+                    best_obj=torch.empty(N, dtype=torch.float64, device=dev),
+                    best_task=torch.empty(self.T, N, dtype=torch.int32, device=dev), best_mach=torch.empty(self.T, N, dtype=torch.int32, device=dev))
+
+    def walk_accept(self, N, K, cost4, done, w_cfg, task, mach, state, sig=None, round=0, first=False, slack=None, next_col=None,
+                    cur_obj=True, best_obj=True, pick=True, why=True, barred=True, obj=True):
+        """N groups of K copies (copy c of group n = element n*K + c; copy 0 the incumbent) after the replay of the plans task, mach
+        [T, N*K] int32: cost4 [N*K,4] f64 and done [N*K] uint8 as `final_costs` gives them, sig [N*K] int64 as `state_signature` gives
+        it (or None), w_cfg = (w_mk, w_ec, w_tt).  This handle gives T, the device and the stream only.  state: the dict of
+        `walk_state` — its shapes give late_len and tabu_len; first=True fills it.  The rule (include/mtfjsp.h): the candidates are the
+        copies c >= 1 with an objective whose schedule is neither the incumbent's nor in the tabu ring; the best of them (lowest c
+        among equals) is taken if strictly better (why 2), else if within `slack` of the incumbent (why 3; None: off, 0.0: sideways
+        steps, inf: always), else if not above the late ring's entry of this round (why 4), else refused (why 1; 0: no candidate); a
+        move into a new best adds 8 and stores the plan in state.
+        -> (next_col [N] int32: the next incumbent's column, for `plan_neighbours`' src_col; cur_obj [N] f64: its objective; best_obj
+            [N] f64: the best so far; pick [N] int32: the local index taken or refused, -1 without one; why [N] int8; barred [N] int32:
+            candidates the two schedule tests removed; obj [N*K] f64 as `group_reduce` gives it)
+        device tensors; next_col may be a tensor to write into; the others True, a tensor, or None / False.  A tabu ring needs sig.
+        One launch (mtfjsp_walk_accept), nothing read back."""
+        N, K, T, dev = int(N), int(K), self.T, self.device
+        assert cost4.is_cuda and cost4.dtype == torch.float64 and cost4.is_contiguous() and cost4.numel() == N * K * 4
+        assert done.is_cuda and done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == N * K
+        assert sig is None or (sig.is_cuda and sig.dtype == torch.int64 and sig.is_contiguous() and sig.numel() == N * K)
+        for x in (task, mach):
+            assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and tuple(x.shape) == (T, N * K)
+        late, tabu, tabu_n = state["late"], state["tabu"], state["tabu_n"]
+        late_len, tabu_len = (0 if late is None else late.shape[1]), (0 if tabu is None else tabu.shape[1])
+        for x, dt, shape in ((late, torch.float64, (N, late_len)), (tabu, torch.int64, (N, tabu_len)), (tabu_n, torch.int32, (N,)),
+                             (state["best_obj"], torch.float64, (N,)), (state["best_task"], torch.int32, (T, N)), (state["best_mach"], torch.int32, (T, N))):
+            assert x is None or (x.is_cuda and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape)
+        assert (tabu is None) == (tabu_n is None)
+        # (an out-of-range N or K is the library's MTFJSP_ERR_ARG; the buffers below are then never written)
+        next_col = _out(True if next_col is None else next_col, max(N, 0), torch.int32, dev)
+        cur_obj, best_obj = _out(cur_obj, max(N, 0), torch.float64, dev), _out(best_obj, max(N, 0), torch.float64, dev)
+        pick, why, barred = _out(pick, max(N, 0), torch.int32, dev), _out(why, max(N, 0), torch.int8, dev), _out(barred, max(N, 0), torch.int32, dev)
+        obj = _out(obj, max(N * K, 0), torch.float64, dev)
+        w = (C.c_double * 3)(*[float(x) for x in w_cfg])
+        self._plan_keep = (cost4, done, sig, task, mach, state)         # alive until the launch has run
+        capi.check(self.L.mtfjsp_walk_accept(self.h, N, K, cost4.data_ptr(), done.data_ptr(), w, _ptr(sig), task.data_ptr(), mach.data_ptr(),
+                                             int(round), int(bool(first)), -1.0 if slack is None else float(slack), late_len, tabu_len,
+                                             _ptr(late), _ptr(tabu), _ptr(tabu_n), state["best_obj"].data_ptr(), state["best_task"].data_ptr(),
+                                             state["best_mach"].data_ptr(), next_col.data_ptr(), _ptr(cur_obj), _ptr(best_obj), _ptr(pick),
+                                             _ptr(why), _ptr(barred), _ptr(obj)), self.h)
+        return next_col, cur_obj, best_obj, pick, why, barred, obj
+
     def scaler_init(self):
         capi.check(self.L.mtfjsp_scaler_init(self.h), self.h)
 

@@ -88,6 +88,8 @@ PROTOTYPES = {
     "mtfjsp_plan_neighbours": (_I, [_VP, C.c_int32, _VP, _VP, C.c_int64, _VP, _U64, _U64, _U64, C.c_uint32, _VP, _VP, _VP]),
     "mtfjsp_plan_neighbours_critical": (_I, [_VP, C.c_int32, _VP, _VP, C.c_int64, _VP, _U64, _U64, _U64, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_critical_path": (_I, [_VP, C.c_int32, _VP, _VP, _VP, _VP]),
+    "mtfjsp_walk_accept": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _U64, C.c_int32, C.c_double, C.c_int32, C.c_int32]
+                           + [_VP] * 13),
     "mtfjsp_plan_offspring": (_I, [_VP, C.c_int32, _VP, _VP, _VP, _VP, _U64, _U64, _U64, _U64, _U64, C.c_uint32, _VP, _VP, _VP, _VP]),
     "mtfjsp_front_rank": (_I, [_VP, C.c_int32, C.c_int32, C.c_int32] + [_VP] * 10),
     "mtfjsp_plan_survivors": (_I, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_VP] * 17),

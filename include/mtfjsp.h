@@ -417,6 +417,62 @@ int mtfjsp_plan_neighbours_critical(mtfjsp_handle_t h, int32_t K, const int32_t 
                                     int32_t *task_out, int32_t *mach_out, int8_t *kind_out, const int32_t *path_task, const int8_t *path_arc,
                                     const int32_t *path_len);
 
+/* ------------------------------------------------------------------ a walk on plans: tabu ring, threshold and late acceptance */
+/* The local search above never takes a step that is not strictly better, and ends in the first local optimum of its neighbourhood.
+ * mtfjsp_walk_accept takes mtfjsp_group_reduce's place in its round and may step sideways or uphill; the incumbent is then no longer
+ * the best plan met, so the best is kept beside it.  A round: mtfjsp_plan_neighbours, mtfjsp_reset, T x mtfjsp_step,
+ * mtfjsp_final_costs, mtfjsp_state_signature, mtfjsp_walk_accept — T + 5 launches, nothing read back; next_col is the next round's
+ * src_col.  The reference has no improvement step.
+ *
+ * mtfjsp_walk_accept: h gives T, the device and the stream only.  N groups of K copies, copy c of group n = element g = n*K + c; copy 0
+ * is the incumbent.  cost4 [N*K,4], done [N*K], w3cfg_host: as for mtfjsp_group_reduce.  sig: device u64 [N*K], what
+ * mtfjsp_state_signature wrote for the copies after their replay, or NULL.  task, mach: device int32 [T, N*K], the plans this round
+ * replayed (history layout).  STATE, device arrays the caller keeps from call to call and never has to look into: late binary64
+ * [N, late_len], tabu u64 [N, tabu_len], tabu_n int32 [N], best_obj binary64 [N], best_task, best_mach int32 [T, N] (history layout,
+ * column n = group n).  With late_len == 0 late, with tabu_len == 0 tabu and tabu_n are neither read nor written and may be NULL.
+ * The rule for group n:
+ *   1 objectives   obj[c] and eligibility exactly as mtfjsp_group_reduce forms them — mk = cost4[0], ec = cost4[1] + cost4[3], tt =
+ *                  cost4[2], obj = (w_mk*mk + w_ec*ec) + w_tt*tt, uncontracted; eligible iff done != 0 and none of mk, ec, tt is NaN;
+ *                  obj[c] = NaN for an ineligible copy.  cur = obj[0]
+ *   2 first call   first != 0: late[n][0 .. late_len) = cur, tabu_n[n] = 0, best_obj[n] = cur, and column n of best_task / best_mach =
+ *                  column n*K of task / mach, word for word, whatever it holds; nothing of the state is read
+ *   3 candidates   c = 1 .. K-1 with obj[c] not NaN; where sig is given also sig[g] != sig[n*K] (the incumbent's own schedule again is
+ *                  no move) and sig[g] none of the valid ring entries tabu[n][0 .. min(tabu_n[n], tabu_len)).  barred = the number of
+ *                  copies c >= 1 with a non-NaN obj that these two tests removed.  The ring holds signatures of SCHEDULES the walk has
+ *                  left: a plan that decodes to one of them is barred however its job string looks.  No aspiration rule: a barred
+ *                  schedule was an incumbent, so best_obj is not above its objective
+ *   4 pick         the candidate with the smallest obj, the lowest c among equal ones (comparisons only); -1 if there is none
+ *   5 why          0 if there is no pick; else 2 if cur is NaN or obj[pick] < cur; else 3 if slack >= 0 and obj[pick] <= cur + slack
+ *                  (one binary64 addition; a negative or NaN slack switches this off, 0.0 admits sideways steps, +inf always moves to
+ *                  the best candidate); else 4 if late_len > 0 and obj[pick] <= late[n][round % late_len] (its value before this call
+ *                  writes it, after a first call's fill); else 1: refused
+ *   6 move         iff why >= 2: with tabu_len > 0, tabu[n][tabu_n[n] mod tabu_len] = sig[n*K] — the schedule being left — and
+ *                  tabu_n[n] += 1 (mod: the non-negative remainder); next_col[n] = n*K + pick, new cur = obj[pick].  Otherwise
+ *                  next_col[n] = n*K where cur is not NaN, else -1 (what best_out of mtfjsp_group_reduce gives: a group without a
+ *                  plan stays without one), new cur = cur
+ *   7 late ring    late_len > 0: late[n][round % late_len] = new cur (late-acceptance hill climbing in Burke and Bykov's form: the
+ *                  entry is overwritten every round, moved or not)
+ *   8 best so far  on a move with best_obj[n] NaN or new cur < best_obj[n]: best_obj[n] = new cur, column n of best_task / best_mach
+ *                  = column n*K + pick of task / mach, and 8 is added to why
+ *   9 outputs      device, [N] each, all but next_col may be NULL: next_col int32; cur_obj_out = new cur; best_obj_out = best_obj[n]
+ *                  after the call; pick_out int32 = pick (the local index c); why_out int8; barred_out int32; obj_out [N*K] = obj as
+ *                  mtfjsp_group_reduce writes it.  Every value reported is the copy's own word: of -0.0 and +0.0, which are equal,
+ *                  the one the copy holds
+ * Signatures are compared, never computed with: two different schedules share one with probability about 2^-64, and the copy is
+ * then barred without cause for as long as the entry stays in the ring — a lost candidate, never a wrong plan.
+ * MTFJSP_ERR_ARG, nothing written: N < 1, K < 1 or K > 4096, N*K >= 2^31; late_len outside 0..4096; tabu_len outside 0..1024; a null
+ * cost4, done, w3cfg_host, task, mach, best_obj, best_task, best_mach or next_col; late_len > 0 without late; tabu_len > 0 without tabu,
+ * tabu_n or sig; a state or output array that overlaps an input array or another state or output array.
+ * One launch (k_walk_accept), one workgroup per group, on h's stream, no read-back, no synchronisation: every thread keeps its own
+ * copies in registers as k_group_reduce does, the ring's valid entries sit in LDS and are read by broadcast, one thread decides and
+ * the workgroup copies the plan, rows over threads, only where there is a new best; every write of the state comes after every read
+ * of it. */
+int mtfjsp_walk_accept(mtfjsp_handle_t h, int32_t N, int32_t K, const double *cost4, const uint8_t *done, const double *w3cfg_host,
+                       const uint64_t *sig, const int32_t *task, const int32_t *mach, uint64_t round, int32_t first, double slack,
+                       int32_t late_len, int32_t tabu_len, double *late, uint64_t *tabu, int32_t *tabu_n, double *best_obj,
+                       int32_t *best_task, int32_t *best_mach, int32_t *next_col, double *cur_obj_out, double *best_obj_out,
+                       int32_t *pick_out, int8_t *why_out, int32_t *barred_out, double *obj_out);
+
 /* ------------------------------------------------------------------ evolutionary search on plans: offspring of a population */
 /* Recombination over the same machinery: a population of P plans per instance lives in one handle of N*P (member c of group n =
  * element g = n*P + c), one launch turns it into its offspring, the P copies replay them (mtfjsp_reset, T x mtfjsp_step), and
