@@ -390,7 +390,7 @@ CRIT_MOVES = MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN
 
 
 def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL_MOVES, left_shift=False, chunk=None, device=0,
-                 obs_dtype="f32", name="LS"):
+                 obs_dtype="f32", name="LS", replay="steps"):
     """Hill climbing from the plans `start` = (task [N,T], mach [N,T]) — any plan the library returns: PLANS of `pdr_baselines`,
     `lookahead_baselines`, `beam_baselines`, `random_baselines`, or `plans` of `evaluate.sample_best_of_k` — on the N instances t, p
     [N,T,M], tt [N,M,M], edge [N,E,M/E] (args as for `pdr_baselines`).  Per round every instance's incumbent becomes K neighbours
@@ -408,11 +408,15 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
     path between two jobs and turn it round, or put one task of the path on another machine.  The path is read off the device
     state (`DeviceBatchEnv.critical_path`): of `start` after one replay on the n-instance handle before round 0, of every group's
     best copy after its `group_reduce`, while that state is still there — T + 5 launches a round, still nothing read back.
+    replay="launch": the copies' replay of a round is `DeviceBatchEnv.replay_plans` — one launch instead of reset, T steps and
+    final_costs, the same bits; it writes the copies' schedules only where the round reads a critical path.  The start plans' replay
+    for the paths and the last replay stay step by step.  Any other value: ValueError.
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS {name: (task[N,T], mach[N,T])}, and
        "start_obj" [N]: the Objective of `start`;  "history" [rounds, N]: the best Objective after every round;
        "accepted" [rounds, N] int8: the move that gave the round's best copy (MOVE_*, 8 and 16 included), -1 where the incumbent stayed."""
     N, T = CopyGroups.sizes(t, args)
     K, R, moves = int(K), int(rounds), int(moves)
+    CopyGroups.check_mode(replay)
     if not 1 <= K <= 4096:
         raise ValueError("K must be 1..4096")
     if R < 0 or not 1 <= moves <= (ALL_MOVES | CRIT_MOVES):
@@ -445,7 +449,7 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
             for r in range(R):
                 out_t, out_m = g.plan_bufs(r)
                 env.plan_neighbours(K, cur_t, cur_m, col, seed, r, lo, moves, out_t, out_m, kind[r], critical=path)
-                g.round(out_t, out_m, obj0 if r == 0 else False, best[r], hist[r])
+                g.round(out_t, out_m, obj0 if r == 0 else False, best[r], hist[r], replay, path is not None)
                 if path is not None:                                    # of the best copies, while their state is still there (-1: an empty path)
                     env.critical_path(best[r], None, *path)
                 cur_t, cur_m, col = out_t, out_m, best[r]
@@ -465,7 +469,7 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
 
 # ---- a walk on plans (csrc/mtfjsp_walk.hip): the local search's round with an acceptance rule that can leave a local optimum
 def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_MOVES, tabu=0, slack=None, late=8, left_shift=False,
-                chunk=None, device=0, obs_dtype="f32", name="WS"):
+                chunk=None, device=0, obs_dtype="f32", name="WS", replay="steps"):
     """`local_search` that may step sideways and uphill: start, the instances, args, K, seed, moves (CRIT_MOVES included), left_shift and
     chunk are `local_search`'s, and so are the neighbours of a round (`DeviceBatchEnv.plan_neighbours`, draws keyed by (seed, instance,
     copy, round)) and their replay.  What differs is the acceptance (`DeviceBatchEnv.walk_accept`; include/mtfjsp.h has the rule): of the
@@ -480,6 +484,7 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
     plans are replayed as `local_search` replays its plans.  rounds = 0 is a plain replay of `start`; K = 1 never moves.  With tabu = 0,
     slack = None, late = 0 the walk is `local_search`: a copy of the incumbent's schedule is never strictly better.
     The defaults are late acceptance alone: at J6M6E2 x 4096 it ends below the ring with slack = inf under both weightings.
+    replay: `local_search`'s ("launch": one launch per round's replay, with the copies' schedules written: every round reads their signatures).
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout for the best plans, under PLANS {name: (task[N,T],
        mach[N,T])}, and "start_obj" [N];  "history" [rounds, N]: the best Objective so far after every round (never rising);  "current"
        [rounds, N]: the incumbent's;  "accepted" [rounds, N] int8: the kind of the move taken (MOVE_*), -1 where the walk stayed;  "why"
@@ -487,6 +492,7 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
        [rounds, N] int32: neighbours with an objective that were the incumbent's schedule again or in the ring."""
     N, T = CopyGroups.sizes(t, args)
     K, R, moves, tabu, late = int(K), int(rounds), int(moves), int(tabu), int(late)
+    CopyGroups.check_mode(replay)
     if not 1 <= K <= 4096:
         raise ValueError("K must be 1..4096")
     if R < 0 or not 1 <= moves <= (ALL_MOVES | CRIT_MOVES):
@@ -530,7 +536,7 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
             for r in range(R):
                 out_t, out_m = g.plan_bufs(r)
                 env.plan_neighbours(K, cur_t, cur_m, src, seed, r, lo, moves, out_t, out_m, kind[r], critical=path)
-                g.replay(out_t, out_m, g.cost4, g.done)
+                g.replay(out_t, out_m, g.cost4, g.done, replay, True)
                 env.state_signature(sig)
                 env.walk_accept(n, K, g.cost4, g.done, g.w, out_t, out_m, state, sig, r, r == 0, slacks[r], col[r], cur[r], hist[r], False,
                                 why[r], barred[r], obj0 if r == 0 else False)
@@ -556,7 +562,7 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
 
 # ---- evolutionary search on plans (csrc/mtfjsp_evolve.hip): a population of P plans per instance, recombined generation by generation
 def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.8, p_mut=0.3, moves=ALL_MOVES, left_shift=False, chunk=None,
-           device=0, obs_dtype="f32", name="GA"):
+           device=0, obs_dtype="f32", name="GA", replay="steps"):
     """A genetic algorithm on the (job string, machine per task) encoding, seeded with plans the library already has: `start` = one
     (task [N,T], mach [N,T]) or a list of S <= P of them — any PLANS entry of `pdr_baselines`, `lookahead_baselines`, `beam_baselines`,
     `random_baselines`, `local_search`, or `plans` of `evaluate.sample_best_of_k` — on the N instances t, p [N,T,M], tt [N,M,M], edge
@@ -570,10 +576,12 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
     depend on `chunk` (instances per pass; None: all N).  After the last generation the best plans are replayed on an n-instance
     handle step by step, as `local_search` replays its plans (`evaluate.CopyGroups`, which also holds the handles and the round);
     where no member is a valid plan the replay of member 0 ends there (RuntimeError).  generations = 0 is a replay of the best start.
+    replay: `local_search`'s ("launch": every generation's replay is one launch; no schedule is read, none is written).
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS {name: (task[N,T], mach[N,T])}, and
        "start_obj" [N]: the best start's Objective;  "history" [generations, N]: the best Objective after every generation."""
     N, T = CopyGroups.sizes(t, args)
     P, G, moves = int(P), int(generations), int(moves)
+    CopyGroups.check_mode(replay)
     if not 1 <= P <= 4096:
         raise ValueError("P must be 1..4096")
     if G < 0 or not 1 <= moves <= ALL_MOVES:
@@ -603,7 +611,7 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
                     out_t, out_m = g.plan_bufs(gen)
                     env.plan_offspring(P, cur_t, cur_m, obj, best[gen - 1], seed, gen, lo, cross_thr, mut_thr, moves, out_t, out_m, False, False)
                     cur_t, cur_m = out_t, out_m
-                g.round(cur_t, cur_m, obj, best[gen], hist[gen])
+                g.round(cur_t, cur_m, obj, best[gen], hist[gen], replay)
             g.finish(cur_t, cur_m, best[G], f"{name} evolve", start_obj=hist[0], history=hist[1:])
     r = g.collect(last_axis=("history",))
     out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
@@ -613,7 +621,7 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
 
 # ---- Pareto-front evolutionary search (csrc/mtfjsp_nsga.hip): parents and children ranked into fronts, the first P survive
 def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.8, p_mut=0.3, moves=ALL_MOVES, left_shift=False,
-                  chunk=None, device=0, obs_dtype="f32", name="NSGA"):
+                  chunk=None, device=0, obs_dtype="f32", name="NSGA", replay="steps"):
     """`evolve` without collapsing the three objectives before it selects: an NSGA-II style search that returns one Pareto front of
     schedules in (makespan, energy + idle, transport) per instance.  `start`, the P-member generation 0 (member c = start[c % S]), the
     thresholds round(p * 2**32) and the draws keyed by (seed, instance, child, g) are `evolve`'s; 8 <= P <= 1024.
@@ -629,7 +637,7 @@ def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_c
     index keeps its front and the others fall to later ones; there is no archive across generations.  The results do not depend on
     `chunk`.  After the last generation one `group_reduce` over the survivors gives the best-Objective member, which is replayed on
     an n-instance handle as `evolve` replays its best plan (RuntimeError where no member is a valid plan), and the population's
-    plans, costs and ranks are read back once.
+    plans, costs and ranks are read back once.  replay: `evolve`'s.
     -> {name: (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout and PLANS {name: (task[N,T], mach[N,T])} for the
        best-Objective member; "start_obj" [N]: the best start's Objective; "history" [generations, N]: the best Objective among
        parents and children of every generation; "front_size" [generations + 1, N] int32: the members of front 0 among the ranked
@@ -637,6 +645,7 @@ def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_c
        [F,4], "obj" [F], "task" [F,T], "mach" [F,T]}: the front-0 survivors in selection order."""
     N, T = CopyGroups.sizes(t, args)
     P, G, moves = int(P), int(generations), int(moves)
+    CopyGroups.check_mode(replay)
     if not 8 <= P <= 1024:
         raise ValueError("P must be 8..1024 (the best Objective is only sure to survive among 8 or more)")
     if G < 0 or not 1 <= moves <= ALL_MOVES:
@@ -668,13 +677,13 @@ def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_c
             pop, child, spare = slots
             pop[0].copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_task).reshape(B, T).T)))      # [T,n*P]: row s = the actions of step s
             pop[1].copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_mach).reshape(B, T).T)))
-            g.replay(*pop)
+            g.replay(*pop, replay)
             env.front_rank(n, pop[2], pop[3], None, None, g.w, rank[:B], False, order[:B], size[0], hist[0])
             env.plan_survivors(P, order[:B], rank[:B], pop, None, child[0], child[1], child[2], child[3], pop_rank, False, fit)
             pop, child = child, pop
             for gen in range(1, G + 1):
                 env.plan_offspring(P, pop[0], pop[1], fit, None, seed, gen, lo, cross_thr, mut_thr, moves, child[0], child[1], False, False)
-                g.replay(*child)
+                g.replay(*child, replay)
                 env.front_rank(n, pop[2], pop[3], child[2], child[3], g.w, rank, False, order, size[gen], hist[gen])
                 env.plan_survivors(P, order, rank, pop, child, spare[0], spare[1], spare[2], spare[3], pop_rank, False, fit)
                 pop, child, spare = spare, pop, child

@@ -171,6 +171,30 @@ class DeviceBatchEnv:
         capi.check(self.L.mtfjsp_final_costs(self.h, out.data_ptr(), done.data_ptr()), self.h)
         return out, done
 
+    def replay_plans(self, task, mach, cost4=None, done=None, state=False):
+        """The plans task, mach — int32 device tensors [T, stride >= B] in history layout (row s = the actions of step s, copy b = column
+        b; a column-offset view of a wider buffer is fine: rows contiguous, one row stride) — replayed from scratch in ONE launch
+        (mtfjsp_replay_plans): -> (cost4 [B,4] f64, done [B] uint8) device tensors, bit for bit what `reset`, T times `step` and
+        `final_costs` give, except that a copy that is not done holds four NaNs.  The handle needs instances and no reset.
+        state=True also writes every copy's schedule, so that `critical_path`, `state_signature` and `read_state` of STATE_MACHINE,
+        _START, _FINISH, _ROUTES see it.  Until the next `reset` everything else that needs a state raises (MtfjspError, ERR_STATE):
+        `step`, `final_costs`, a fork of state or observation out of this handle, the masks, the snapshots.  Nothing is read back."""
+        T, B = self.T, self.B
+        for x in (task, mach):
+            assert x.is_cuda and x.dtype == torch.int32 and x.dim() == 2 and x.shape[0] == T and x.shape[1] >= B and x.stride(1) == 1
+        assert T == 1 or task.stride(0) == mach.stride(0)
+        stride = task.stride(0) if T > 1 else max(task.shape[1], B)
+        if cost4 is None:
+            cost4 = torch.empty(B, 4, dtype=torch.float64, device=self.device)
+        if done is None:
+            done = torch.empty(B, dtype=torch.uint8, device=self.device)
+        assert cost4.is_cuda and cost4.dtype == torch.float64 and cost4.is_contiguous() and cost4.shape == (B, 4)
+        assert done.is_cuda and done.dtype == torch.uint8 and done.is_contiguous() and done.shape == (B,)
+        self._plan_keep = (task, mach)                                  # alive until the launch has run
+        capi.check(self.L.mtfjsp_replay_plans(self.h, task.data_ptr(), mach.data_ptr(), stride, cost4.data_ptr(), done.data_ptr(),
+                                              capi.REPLAY_STATE if state else 0), self.h)
+        return cost4, done
+
     def group_reduce(self, N, K, cost4, done, w_cfg, obj=True, best=True, best_obj=True, front=True):
         """N groups of K copies (copy c of group n = element n*K + c of cost4 [N*K,4] f64 and done [N*K] uint8, device tensors
         from any source; this handle gives the device and the stream only).  w_cfg = (w_mk, w_ec, w_tt).  A copy is eligible iff

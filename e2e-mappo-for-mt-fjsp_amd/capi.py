@@ -13,6 +13,7 @@ OBS_F64, OBS_F32 = 0, 1
 OK, ERR_ARG, ERR_STATE, ERR_HIP, ERR_ACTION, ERR_RETRY = 0, -1, -2, -3, -4, -5
 PATH_MASK, ST_INVALID, ST_INFEASIBLE = 0x7, 0x100, 0x200
 FORK_INSTANCE, FORK_STATE, FORK_OBS = 1, 2, 4
+REPLAY_STATE = 1
 STATE_MACHINE, STATE_START, STATE_FINISH, STATE_ROUTES, STATE_PREV_COSTS, STATE_SCALER, STATE_W3 = range(7)
 
 
@@ -85,6 +86,8 @@ PROTOTYPES = {
     "mtfjsp_beam_backtrack": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_final_costs": (_I, [_VP, _VP, _VP]),
     "mtfjsp_group_reduce": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mtfjsp_replay_plans": (_I, [_VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int32]),
+    "mtfjsp_replay_launch_info_for": (_I, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "mtfjsp_plan_neighbours": (_I, [_VP, C.c_int32, _VP, _VP, C.c_int64, _VP, _U64, _U64, _U64, C.c_uint32, _VP, _VP, _VP]),
     "mtfjsp_plan_neighbours_critical": (_I, [_VP, C.c_int32, _VP, _VP, C.c_int64, _VP, _U64, _U64, _U64, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_critical_path": (_I, [_VP, C.c_int32, _VP, _VP, _VP, _VP]),
@@ -179,6 +182,16 @@ def check(rc, handle=None, enc=False):
         L = lib()
         msg = (L.mtfjsp_encoder_last_error(handle) if enc else L.mtfjsp_last_error(handle)) or b""
         raise MtfjspError(rc, msg.decode())
+
+
+def replay_launch_info_for(n_job, n_machine, batch, lds_max=160 * 1024):
+    """(copies per workgroup, dynamic LDS bytes) of the launch `DeviceBatchEnv.replay_plans` makes for a handle of this shape where a
+    workgroup may use `lds_max` bytes of LDS (gfx950: 160 KiB) — the library's own rule (csrc/mtfjsp_replay.hip), no GPU needed.
+    ValueError for a shape mtfjsp_create refuses or whose single copy does not fit `lds_max`."""
+    g, nb = C.c_int32(0), C.c_int64(0)
+    if lib().mtfjsp_replay_launch_info_for(n_job, n_machine, batch, lds_max, C.byref(g), C.byref(nb)) != OK:
+        raise ValueError(f"no plan replay in one launch for J{n_job}M{n_machine} B={batch} with {lds_max} bytes of LDS per workgroup")
+    return g.value, nb.value
 
 
 def gin_res_kernel_for(batch, n_job, n_machine, num_cu=256, candidates=None, node_output=False):

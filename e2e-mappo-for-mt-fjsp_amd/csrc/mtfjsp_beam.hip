@@ -65,7 +65,7 @@ extern "C" int mtfjsp_state_signature(mtfjsp_handle_t h, uint64_t *sig_out)
     if (!sig_out) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_state_signature: null argument");
     EnvHostView v;
     mtfjsp_env_host_view(h, &v);
-    if (!v.was_reset) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_state_signature: the handle has never been reset");
+    if (!v.has_schedule()) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_state_signature: the handle holds no schedule (never reset, or plans replayed without MTFJSP_REPLAY_STATE)");
     if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_state_signature")) return rc;
     SigArgs A{};
     A.B = v.B; A.T = v.T; A.sd = v.sd; A.pl = v.pl; A.out = (u64 *)sig_out;

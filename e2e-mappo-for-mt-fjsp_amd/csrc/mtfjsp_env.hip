@@ -1593,6 +1593,7 @@ struct mtfjsp_env {
     hipStream_t stream = nullptr;
     std::string err;
     bool loaded = false, was_reset = false;
+    int replayed = 0;                  // mtfjsp_replay_plans since the last reset: 1, or 2 with the sd / pl records (was_reset is then false)
     // device memory
     double *t = nullptr, *p = nullptr, *tt = nullptr, *mean3 = nullptr;
     double2 *cst = nullptr;
@@ -1627,6 +1628,16 @@ void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v)
     v->loaded = h->loaded; v->t = h->t; v->p = h->p; v->stream = h->stream;
     v->was_reset = h->was_reset; v->obs_bound = h->obs_bound; v->mj = h->mj; v->MJ = h->MJ; v->sd = h->sd; v->pl = h->pl; v->obs = h->obs;
     v->scal = h->scal; v->tt = h->tt;
+    v->replayed = h->replayed; v->left_shift = h->cfg.left_shift; v->lds_max = h->lds_max; v->cst = h->cst; v->pw_tab = h->pw_tab; v->pw_nleaf = h->pw_nleaf;
+}
+void mtfjsp_env_set_replayed(mtfjsp_handle_t h, int how)
+{
+    h->was_reset = false; h->replayed = how;
+}
+// what an entry point that needs a reset answers on a handle that has none
+static const char *no_reset_msg(const mtfjsp_env *h)
+{
+    return h->replayed ? "the handle holds replayed plans (mtfjsp_replay_plans), not a state: reset first" : "reset has not been called";
 }
 int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg)
 {
@@ -1786,6 +1797,7 @@ extern "C" int mtfjsp_bind_obs(mtfjsp_handle_t h, const mtfjsp_obs_t *o)
 static int snapshot_impl(mtfjsp_env *h, const mtfjsp_obs_t *dst, const mtfjsp_obs_t *dst2, float *reward_out)
 {
     if (!h->obs_bound) { h->err = "no observation buffers bound (mtfjsp_alloc_obs / mtfjsp_bind_obs)"; return MTFJSP_ERR_STATE; }
+    if (h->replayed) { h->err = no_reset_msg(h); return MTFJSP_ERR_STATE; }      // (the bound observation is the last reset's or step's, not the replay's)
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t B = h->cfg.batch, T = h->T, M = h->cfg.n_machine, J = h->cfg.n_job;
     const size_t es = h->cfg.obs_dtype == MTFJSP_OBS_F32 ? 4 : 8;
@@ -1843,7 +1855,7 @@ static int load_common(mtfjsp_env *h, const double *t, const double *p, const do
     hipLaunchKernelGGL(k_transpose_tt, dim3((unsigned)((B * M * M + 127) / 128)), dim3(128), 0, h->stream, (int)B, (int)M, h->tt, h->ttT);
     HIPCHK(h, hipGetLastError());
     if (kind == hipMemcpyHostToDevice) HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->loaded = true; h->was_reset = false;
+    h->loaded = true; h->was_reset = false; h->replayed = 0;
     return MTFJSP_OK;
 }
 extern "C" int mtfjsp_load_instances(mtfjsp_handle_t h, const double *t, const double *p, const double *tt, const int32_t *shop)
@@ -1872,7 +1884,7 @@ extern "C" int mtfjsp_generate_instances(mtfjsp_handle_t h, uint64_t seed, uint6
     hipLaunchKernelGGL(k_prepare, dim3((B * T + 127) / 128), dim3(128), 0, h->stream, B, T, M, h->t, h->p, h->cst, h->mean3);
     hipLaunchKernelGGL(k_transpose_tt, dim3((B * M * M + 127) / 128), dim3(128), 0, h->stream, B, M, h->tt, h->ttT);
     HIPCHK(h, hipGetLastError());
-    h->loaded = true; h->was_reset = false;
+    h->loaded = true; h->was_reset = false; h->replayed = 0;
     return MTFJSP_OK;
 }
 // instance arrays back to the host (t, p [B,T,M] f64; tt [B,M,M] f64; shop [B,M] i32) — e.g. to export a generated set in
@@ -1929,7 +1941,7 @@ static int check_ready(mtfjsp_env *h, bool need_reset)
 {
     if (!h->loaded) { h->err = "load_instances has not been called"; return MTFJSP_ERR_STATE; }
     if (!h->obs_bound) { h->err = "no observation buffers bound (mtfjsp_alloc_obs / mtfjsp_bind_obs)"; return MTFJSP_ERR_STATE; }
-    if (need_reset && !h->was_reset) { h->err = "reset has not been called"; return MTFJSP_ERR_STATE; }
+    if (need_reset && !h->was_reset) { h->err = no_reset_msg(h); return MTFJSP_ERR_STATE; }
     return MTFJSP_OK;
 }
 
@@ -1942,7 +1954,7 @@ static int reset_launch(mtfjsp_env *h, const EnvParams &P)
     static void (*const fn[2])(EnvParams) = {k_env_reset<float>, k_env_reset<double>};
     hipLaunchKernelGGL(fn[!P.obs_f32], dim3(P.B), dim3(WAVE), env_reset_lds_bytes(P.T, P.obs_f32), h->stream, P);
     HIPCHK(h, hipGetLastError());
-    h->was_reset = true;
+    h->was_reset = true; h->replayed = 0;
     return MTFJSP_OK;
 }
 extern "C" int mtfjsp_reset(mtfjsp_handle_t h, const double *w3)
@@ -2237,7 +2249,9 @@ extern "C" int mtfjsp_copy_to_host(mtfjsp_handle_t h, void *dst, const void *src
 extern "C" int mtfjsp_read_state_host(mtfjsp_handle_t h, int which, void *out)
 {
     if (!h || !out) return MTFJSP_ERR_ARG;
-    int rc = check_ready(h, true);
+    // a replay with MTFJSP_REPLAY_STATE leaves the schedule fields (machine, start, finish, routes) and nothing else
+    const bool schedule = which == MTFJSP_STATE_MACHINE || which == MTFJSP_STATE_START || which == MTFJSP_STATE_FINISH || which == MTFJSP_STATE_ROUTES;
+    int rc = check_ready(h, !(h->replayed == 2 && schedule));
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t B = h->cfg.batch, T = h->T, M = h->cfg.n_machine;
@@ -2633,7 +2647,8 @@ int mtfjsp_env_fork_launch(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32
         (a.left_shift != 0) != (b.left_shift != 0) || a.device_id != b.device_id)
         return fail(MTFJSP_ERR_ARG, "handles differ in n_job, n_machine, n_edge, obs_dtype, left_shift or device");
     if (!src->loaded) return fail(MTFJSP_ERR_STATE, "the source has no instances loaded or generated");
-    if ((flags & (MTFJSP_FORK_STATE | MTFJSP_FORK_OBS)) && !src->was_reset) return fail(MTFJSP_ERR_STATE, "the source has never been reset");
+    if ((flags & (MTFJSP_FORK_STATE | MTFJSP_FORK_OBS)) && !src->was_reset)
+        return fail(MTFJSP_ERR_STATE, src->replayed ? "the source holds replayed plans (mtfjsp_replay_plans), not a state: reset it first" : "the source has never been reset");
     if ((flags & MTFJSP_FORK_OBS) && (!src->obs_bound || !dst->obs_bound)) return fail(MTFJSP_ERR_STATE, "MTFJSP_FORK_OBS needs observation buffers bound on both handles");
     if (!(flags & MTFJSP_FORK_INSTANCE) && !dst->loaded) return fail(MTFJSP_ERR_STATE, "the destination has no instances: fork with MTFJSP_FORK_INSTANCE first");
     const size_t Bd = a.batch, T = dst->T, M = a.n_machine, J = a.n_job, MJ = dst->MJ, es = a.obs_dtype == MTFJSP_OBS_F32 ? 4 : 8;
@@ -2676,8 +2691,8 @@ int mtfjsp_env_fork_launch(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32
     if (src_index) hipLaunchKernelGGL(k_env_fork<false>, dim3(blocks), dim3(256), 0, dst->stream, A);
     else hipLaunchKernelGGL(k_env_fork<true>, dim3(blocks), dim3(256), 0, dst->stream, A);
     if (hipGetLastError() != hipSuccess) return fail(MTFJSP_ERR_HIP, "launch failed");
-    if (flags & MTFJSP_FORK_INSTANCE) { dst->loaded = true; dst->was_reset = false; }
-    if (flags & MTFJSP_FORK_STATE) dst->was_reset = true;
+    if (flags & MTFJSP_FORK_INSTANCE) { dst->loaded = true; dst->was_reset = false; dst->replayed = 0; }
+    if (flags & MTFJSP_FORK_STATE) { dst->was_reset = true; dst->replayed = 0; }
     return MTFJSP_OK;
 }
 extern "C" int mtfjsp_fork(mtfjsp_handle_t dst, mtfjsp_handle_t src, const int32_t *src_index, int32_t flags)

@@ -115,7 +115,7 @@ __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t 
     }
 }
 
-// host side: what the library's other translation units (mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip, mtfjsp_plan.hip) see of a handle; defined in mtfjsp_env.hip
+// host side: what the library's other translation units (mtfjsp_pdr.hip, mtfjsp_lookahead.hip, mtfjsp_beam.hip, mtfjsp_group.hip, mtfjsp_plan.hip, mtfjsp_replay.hip) see of a handle; defined in mtfjsp_env.hip
 struct EnvHostView {
     int B, J, M, T, device_id;
     bool loaded;
@@ -129,8 +129,20 @@ struct EnvHostView {
     mtfjsp_obs_t obs;                  // the bound observation (valid with obs_bound)
     const double *scal;                // [B,SCAL_N] per-instance scalar state (slots above)
     const double *tt;                  // [B,M,M] device transport times (mtfjsp_critical_path: the tightness of a job arc)
+    // mtfjsp_replay_plans (mtfjsp_replay.hip)
+    int replayed;                      // 0, or since the last reset: 1 = replayed, 2 = replayed with the sd / pl records written
+    int left_shift;
+    size_t lds_max;                    // LDS bytes a workgroup may use on the handle's device
+    const double2 *cst;                // [B,T] {min_dur, min_pt}
+    const short *pw_tab;               // numpy's pairwise sum over T elements (pw_table)
+    int pw_nleaf;
+    // sd and pl hold a schedule: after a reset, or after a replay that wrote them
+    bool has_schedule() const { return was_reset || replayed == 2; }
 };
 __attribute__((visibility("hidden"))) void mtfjsp_env_host_view(mtfjsp_handle_t h, EnvHostView *v);
+// after mtfjsp_replay_plans: the handle is no longer reset (everything that needs a reset refuses with MTFJSP_ERR_STATE) until the next reset;
+// how = 2: sd and pl hold the replayed schedules
+__attribute__((visibility("hidden"))) void mtfjsp_env_set_replayed(mtfjsp_handle_t h, int how);
 __attribute__((visibility("hidden"))) int mtfjsp_env_fail(mtfjsp_handle_t h, int code, const char *msg);   // sets mtfjsp_last_error, returns code
 // the check behind every HIP call of an entry point `who`: e != hipSuccess sets "<who>: <msg>" and returns MTFJSP_ERR_HIP, else MTFJSP_OK
 __attribute__((visibility("hidden"))) int mtfjsp_env_hip_check(mtfjsp_handle_t h, hipError_t e, const char *who, const char *msg);

@@ -47,7 +47,9 @@ extern "C" int mtfjsp_final_costs(mtfjsp_handle_t h, double *cost4_out, uint8_t 
     if (!cost4_out) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_final_costs: null argument");
     EnvHostView v;
     mtfjsp_env_host_view(h, &v);
-    if (!v.was_reset) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_final_costs: the handle has never been reset");
+    if (!v.was_reset)
+        return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, v.replayed ? "mtfjsp_final_costs: the handle holds replayed plans (mtfjsp_replay_plans wrote their costs), not a state: reset first"
+                                                               : "mtfjsp_final_costs: the handle has never been reset");
     if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_final_costs")) return rc;
     FinalArgs A{};
     A.B = v.B; A.T = v.T; A.scal = v.scal; A.cost4 = cost4_out; A.done = done_out;

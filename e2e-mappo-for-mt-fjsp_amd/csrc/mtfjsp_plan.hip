@@ -333,7 +333,7 @@ extern "C" int mtfjsp_critical_path(mtfjsp_handle_t h, int32_t n, const int32_t 
     EnvHostView v;
     mtfjsp_env_host_view(h, &v);
     if (n < 1 || (!col && n != v.B)) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_critical_path: n >= 1, and n = the handle's batch without col");
-    if (!v.was_reset) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_critical_path: the handle has never been reset");
+    if (!v.has_schedule()) return mtfjsp_env_fail(h, MTFJSP_ERR_STATE, "mtfjsp_critical_path: the handle holds no schedule (never reset, or plans replayed without MTFJSP_REPLAY_STATE)");
     const size_t lds = crit_lds_bytes(v.T);
     if (lds > PLAN_LDS_HARD) return mtfjsp_env_fail(h, MTFJSP_ERR_ARG, "mtfjsp_critical_path: n_job * n_machine is too large for four paths in LDS");
     if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_critical_path")) return rc;

@@ -201,16 +201,29 @@ class CopyGroups:
     def plan_bufs(self, i):
         return self.bufs[i & 1]
 
-    def round(self, task, mach, obj, best, best_obj):
+    REPLAY_MODES = ("steps", "launch")
+
+    @classmethod
+    def check_mode(cls, mode):
+        if mode not in cls.REPLAY_MODES:
+            raise ValueError('replay must be "steps" or "launch"')
+        return mode
+
+    def round(self, task, mach, obj, best, best_obj, mode="steps", state=False):
         """the copies replay the plans (task, mach) and every group is reduced into the tensors given (obj may be False): reset, T steps,
-        final_costs, group_reduce — T + 3 launches, no torch kernel, nothing read back"""
-        self.replay(task, mach, self.cost4, self.done)
+        final_costs, group_reduce — T + 3 launches (mode "launch": 2), no torch kernel, nothing read back; mode, state: `replay`'s"""
+        self.replay(task, mach, self.cost4, self.done, mode, state)
         self.env.group_reduce(self.n, self.K, self.cost4, self.done, self.w, obj=obj, best=best, best_obj=best_obj, front=False)
 
-    def replay(self, task, mach, cost4, done):
-        """the copies replay the plans (task, mach), their final costs into the tensors given: reset, T steps, final_costs — T + 2
-        launches, no torch kernel, nothing read back"""
+    def replay(self, task, mach, cost4, done, mode="steps", state=False):
+        """the copies replay the plans (task, mach), their final costs into the tensors given.  mode "steps": reset, T steps, final_costs
+        — T + 2 launches; mode "launch": `DeviceBatchEnv.replay_plans`, one launch, the same costs (NaN for a copy that is not done),
+        and the copies' schedules are there afterwards (`critical_path`, `state_signature`) only with state=True.  No torch kernel,
+        nothing read back"""
         env = self.env
+        if self.check_mode(mode) == "launch":
+            env.replay_plans(task, mach, cost4, done, state=state)
+            return
         env.reset(self.w3_all)
         for s in range(self.T):
             env.step(task[s], mach[s])

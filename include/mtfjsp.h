@@ -274,7 +274,8 @@ int mtfjsp_lookahead_select(mtfjsp_handle_t scratch, mtfjsp_handle_t src, int32_
  * NOT covered, deliberately: the words that remember the previous step (the merged-edge node and its transport time), the 17
  * RewardScaling words and the previous-step costs — two states that agree in the schedule but differ there count as equal.
  * Merging by signature is therefore a search heuristic: a false merge costs one beam slot and never corrupts a state.
- * One launch on h's stream (one wavefront per instance, lanes over tasks), nothing read back.  MTFJSP_ERR_STATE: h never reset.
+ * One launch on h's stream (one wavefront per instance, lanes over tasks), nothing read back.  MTFJSP_ERR_STATE: h never reset
+ * (a handle replayed with MTFJSP_REPLAY_STATE holds schedules and is accepted).
  *
  * mtfjsp_beam_select: candidate c = w*T + r of source n (r = j*n_machine + m: slot w tries job j's next task on machine m) is
  * scratch instance g = (n*W + w)*T + r.  It is eligible iff score_in[n*W + w] != -inf (-inf marks an empty slot) and status[g]
@@ -331,6 +332,45 @@ int mtfjsp_final_costs(mtfjsp_handle_t h, double *cost4_out, uint8_t *done_out);
 int mtfjsp_group_reduce(mtfjsp_handle_t h, int32_t N, int32_t K, const double *cost4, const uint8_t *done, const double *w3cfg_host,
                         double *obj_out, int32_t *best_out, double *best_obj_out, uint8_t *front_out);
 
+/* ------------------------------------------------------------------ plans evaluated in one launch */
+/* mtfjsp_replay_plans: what mtfjsp_reset, T x mtfjsp_step and mtfjsp_final_costs give for known plans — the replay every search on
+ * plans below pays per round or generation — in ONE launch, bit for bit: cost4_out [batch,4] and done_out [batch] (device) as
+ * mtfjsp_final_costs writes them after the T steps.  The reference replays a plan step by step on the host (pdrs:465-540).
+ * task, mach: device int32 [T, stride] in history layout, row s = the actions of step s, copy b = column b (stride >= batch: the
+ * buffers of mtfjsp_plan_neighbours and mtfjsp_plan_offspring, or a column-offset view of larger ones).  The handle needs loaded
+ * instances and no prior reset; left_shift and the shape are its configuration's.
+ * Per step only the scheduling part of the step (env:1476-1685): the validity tests (index range, already scheduled, job
+ * predecessor unscheduled), the empty route, the front of the route, the gap search, the append, and the route links; a rejected
+ * action changes nothing and the following actions are still tried, exactly as mtfjsp_step does; t[a][m] < 0 is scheduled like any
+ * duration (MTFJSP_ST_INFEASIBLE today).  Of the cost part only what the final costs depend on: the transport time accumulated in
+ * step order (env:872-876), and after the last step the per-job chain of estimated finishes (env:1920-1999; an operation whose finish
+ * is 0.0 counts as having no real finish) for the makespan, numpy's pairwise sum of the processing energies (env:896), the idle
+ * terms in (machine, position) order summed left to right (dg:144-170), and the one binary64 division of mtfjsp_final_costs.
+ * done = all T operations scheduled; a copy that is not done gets four NaNs in cost4_out (mtfjsp_step leaves estimates of a partial
+ * schedule there): mtfjsp_group_reduce, mtfjsp_walk_accept and mtfjsp_front_rank make such a copy ineligible from done alone.
+ * No observation, reward, RewardScaling word, mask or machine feature is read or written.
+ * flags: 0, or MTFJSP_REPLAY_STATE: every copy's per-task records (machine, start, duration, energy, route links) are written as the T
+ * step launches would leave them, copies with rejected actions included.
+ * After the call the handle is REPLAYED until the next mtfjsp_reset / mtfjsp_reset_episode (or a fork of a state into it) clears it:
+ *   with MTFJSP_REPLAY_STATE   mtfjsp_critical_path, mtfjsp_state_signature and mtfjsp_read_state_host of MTFJSP_STATE_MACHINE, _START,
+ *                              _FINISH, _ROUTES work on the replayed schedules; without it they return MTFJSP_ERR_STATE
+ *   either way                 everything that reads other dynamic state or the observation returns MTFJSP_ERR_STATE with a message:
+ *                              mtfjsp_step*, mtfjsp_final_costs, mtfjsp_fork from it with MTFJSP_FORK_STATE or _OBS, the masks, the
+ *                              snapshots, the other selectors of mtfjsp_read_state_host
+ * MTFJSP_ERR_ARG, nothing written: a null pointer, stride < batch, flags with another bit, an output that overlaps the plans or
+ * the other output, a shape whose single copy does not fit a workgroup's LDS.  MTFJSP_ERR_STATE: no instances loaded.
+ * One launch (k_replay_plans) on h's stream, nothing read back: one wavefront per copy, G copies per workgroup, each copy's
+ * schedule and its per-step operands (duration, power, transport time from the job predecessor's planned machine, gathered from
+ * the plan before the first step) in its own LDS region, 62 bytes per task plus 8 n_machine^2 for the transport times.
+ *
+ * mtfjsp_replay_launch_info_for: that launch's G and dynamic LDS bytes for a shape where a workgroup may use lds_max bytes (gfx950:
+ * 160 KiB), no GPU needed: G = the largest of 4, 2, 1 whose regions stay within min(64 KiB, lds_max) and with G < 2 * batch; a
+ * single region may take up to lds_max.  MTFJSP_ERR_ARG: a shape mtfjsp_create refuses, or one copy does not fit. */
+enum { MTFJSP_REPLAY_STATE = 1 };
+int mtfjsp_replay_plans(mtfjsp_handle_t h, const int32_t *task, const int32_t *mach, int64_t stride, double *cost4_out, uint8_t *done_out,
+                        int32_t flags);
+int mtfjsp_replay_launch_info_for(int32_t n_job, int32_t n_machine, int32_t batch, int64_t lds_max, int32_t *group_out, int64_t *lds_bytes_out);
+
 /* ------------------------------------------------------------------ local search on plans: neighbourhood moves */
 /* Improvement of a schedule the library already has, over the best-of-K machinery above: every group's incumbent plan becomes K
  * neighbouring plans in one launch, the K copies replay them (mtfjsp_reset, T x mtfjsp_step), mtfjsp_final_costs and
@@ -375,7 +415,7 @@ int mtfjsp_plan_neighbours(mtfjsp_handle_t h, int32_t K, const int32_t *src_task
                            int32_t *task_out, int32_t *mach_out, int8_t *kind_out);
 
 /* mtfjsp_critical_path: one critical path per row out of the scheduling state of h as it stands — which operations and which
- * machine hand-overs make the schedule as long as it is.  h: any handle that has been reset (MTFJSP_ERR_STATE otherwise).  col:
+ * machine hand-overs make the schedule as long as it is.  h: any handle that has been reset, or replayed with MTFJSP_REPLAY_STATE (MTFJSP_ERR_STATE otherwise).  col:
  * device int32 [n], row i describes instance col[i] of h (any order, repeats allowed); NULL = the identity, and n must then be the
  * batch.  Outputs (device): path_task int32 [n,T], path_arc int8 [n,T], path_len int32 [n].  The rule uses only what
  * mtfjsp_read_state_host exports (machine, start, finish = start + duration: the addition the step performs, routes) and tt:
