@@ -14,7 +14,7 @@ import torch
 
 from . import capi
 from .batch_env import DeviceBatchEnv
-from .evaluate import COST_KEYS, CopyGroups, best_of_k_rollout, episode_results, parse_args, replay_episode
+from .evaluate import COST_KEYS, CopyGroups, best_of_k_rollout, episode_results, config_w3, eval_reset, parse_args, replay_episode
 
 M_RULE_NAMES = ["SPT", "SEC"]                                                        # pdrs:729
 O_RULE_NAMES = ["FIFO", "MOR", "LWKR_T_o", "LWKR_PT_o", "MWKR_T_o", "MWKR_PT_o"]     # pdrs:730
@@ -96,7 +96,7 @@ def pdr_baselines(t, p, tt, edge, args, rules=RULES, mor_order=None, seed=0, dev
         rep = lambda x: np.tile(np.asarray(x), (R,) + (1,) * (np.asarray(x).ndim - 1))      # noqa: E731
         big.load_instances(rep(t), rep(np.asarray(p, np.float64)), rep(np.asarray(tt, np.float64)), edge=rep(edge))
         big.scaler_init()                                               # the scaled components are produced but not used here
-        w3 = torch.tensor([w], dtype=torch.float64, device=big.device).repeat(R * N, 1)
+        w3 = config_w3(big, w)
         o = np.repeat(np.array([r[1] for r in rules], np.int32), N)
         m = np.repeat(np.array([r[2] for r in rules], np.int32), N)
         mor = None
@@ -112,7 +112,7 @@ def pdr_baselines(t, p, tt, edge, args, rules=RULES, mor_order=None, seed=0, dev
             raise ValueError("env does not have the size args describes")
         if env.left_shift:
             raise ValueError("the dispatch rules run with left shift off (pdrs:669): create the env with left_shift=False")
-        w3 = torch.tensor([w], dtype=torch.float64, device=env.device).repeat(env.B, 1)
+        w3 = config_w3(env, w)
         env.scaler_init()
         parts = [_rollout(env, w3, r[1], r[2], mor_order, seed) for r in rules]
     return _results(names, dict(zip(names, parts)), T, w)
@@ -131,8 +131,7 @@ class Lookahead:
 
     def __init__(self, src):
         self.src, B, T, dev = src, src.B, src.T, src.device
-        self.scratch = DeviceBatchEnv(src.J, src.M, src.E, B * T, left_shift=src.left_shift, obs_dtype="f32" if src.obs_f32 else "f64",
-                                      device=dev.index or 0, gamma=src.gamma, w_cfg=src.w_cfg, scaling_divisor=src.scaling_divisor)
+        self.scratch = DeviceBatchEnv.like(src, B * T)
         self.scratch.fork_from(src, torch.arange(B * T, dtype=torch.int32, device=dev) // T, instance=True, state=False, obs=False)
         self.task_c = torch.empty(B * T, dtype=torch.int32, device=dev)
         self.mach_c = torch.empty(B * T, dtype=torch.int32, device=dev)
@@ -178,10 +177,9 @@ def lookahead_baselines(t, p, tt, edge, args, rules=LOOKAHEAD_RULES, device=0, o
         env.load_instances(t, np.asarray(p, np.float64), np.asarray(tt, np.float64), edge=edge)
         la = Lookahead(env)
         dev = env.device
-        w3 = torch.tensor([w], dtype=torch.float64, device=dev).repeat(N, 1)
+        w3 = config_w3(env, w)
         for name, column in rules:
-            env.scaler_init()                                           # the scaled components are produced but not used here
-            env.reset(w3)                                               # pdrs:675 reset(Random_weight_type="eval")
+            eval_reset(env, w3)
             task = torch.empty(T, N, dtype=torch.int32, device=dev)
             mach = torch.empty(T, N, dtype=torch.int32, device=dev)
 
@@ -221,10 +219,8 @@ class BeamSearch:
         self.src, self.W, self.dedupe = src, W, bool(dedupe)
         N, T, dev = src.B, src.T, src.device
         self.N, self.T = N, T
-        kw = dict(left_shift=src.left_shift, obs_dtype="f32" if src.obs_f32 else "f64", device=dev.index or 0, gamma=src.gamma,
-                  w_cfg=src.w_cfg, scaling_divisor=src.scaling_divisor)
-        self.beam = DeviceBatchEnv(src.J, src.M, src.E, N * W, **kw)
-        self.scratch = DeviceBatchEnv(src.J, src.M, src.E, N * W * T, **kw)
+        self.beam = DeviceBatchEnv.like(src, N * W)
+        self.scratch = DeviceBatchEnv.like(src, N * W * T)
         self._beam_index = torch.arange(N * W, dtype=torch.int32, device=dev) // W
         self.scratch.fork_from(src, torch.arange(N * W * T, dtype=torch.int32, device=dev) // (W * T), instance=True, state=False, obs=False)
         self.task_c = torch.empty(N * W * T, dtype=torch.int32, device=dev)
@@ -323,11 +319,9 @@ def beam_baselines(t, p, tt, edge, args, rules=BEAM_RULES, width=8, dedupe=True,
         bs = None
         try:
             env.load_instances(t[lo:hi], p[lo:hi], tt[lo:hi], edge=edge[lo:hi])
-            dev = env.device
-            w3 = torch.tensor([w], dtype=torch.float64, device=dev).repeat(n, 1)
+            w3 = config_w3(env, w)
             for name, column in rules:
-                env.scaler_init()                                       # the scaled components are produced but not used here
-                env.reset(w3)                                           # pdrs:675 reset(Random_weight_type="eval")
+                eval_reset(env, w3)
                 if bs is None:
                     bs = BeamSearch(env, W, dedupe)
                 else:
@@ -389,6 +383,67 @@ MOVE_CRIT_SWAP, MOVE_CRIT_REASSIGN = 8, 16               # moves a critical path
 CRIT_MOVES = MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN
 
 
+MOVE_NAMES = ("MOVE_SWAP", "MOVE_INSERT", "MOVE_REASSIGN", "MOVE_CRIT_SWAP", "MOVE_CRIT_REASSIGN")                  # bit i = MOVE_NAMES[i]
+# what a plan search returns beside (name, PLANS): (key, dtype, rows) — rows None: per instance [N]; else per round [rounds + rows, N]
+EVOLVE_RESULT = (("start_obj", np.float64, None), ("history", np.float64, 0))
+LOCAL_RESULT = EVOLVE_RESULT + (("accepted", np.int8, 0),)
+WALK_RESULT = EVOLVE_RESULT + (("current", np.float64, 0), ("accepted", np.int8, 0), ("why", np.int8, 0), ("barred", np.int32, 0))
+PARETO_RESULT = EVOLVE_RESULT + (("front_size", np.int32, 1),)
+
+
+def _check_copies(what, n):
+    if not 1 <= n <= 4096:
+        raise ValueError(f"{what} must be 1..4096")
+
+
+def _check_rounds_moves(what, count, moves, allowed):
+    if count < 0 or not 1 <= moves <= allowed:
+        raise ValueError(f"{what} must be >= 0 and moves a non-empty mask of " + " | ".join(x for i, x in enumerate(MOVE_NAMES) if allowed >> i & 1))
+
+
+def _check_name(name, table, *more):                                   # the entry `name` is none of the result's other keys
+    _rule_names([(name,)] + [(key,) for key, _, _ in table] + [(key,) for key in more])
+
+
+def _thresholds(p_cross, p_mut):
+    """the probabilities of `evolve`, checked -> the thresholds round(p * 2**32) the device compares its draws with"""
+    if not (0.0 <= float(p_cross) <= 1.0 and 0.0 <= float(p_mut) <= 1.0):
+        raise ValueError("p_cross and p_mut must be probabilities")
+    return int(round(float(p_cross) * 2 ** 32)), int(round(float(p_mut) * 2 ** 32))
+
+
+def _start_plans(start, N, T):
+    """`start` -> (task [N,T], mach [N,T]) int32, checked"""
+    task, mach = np.ascontiguousarray(start[0], np.int32), np.ascontiguousarray(start[1], np.int32)
+    if task.shape != (N, T) or mach.shape != (N, T):
+        raise ValueError("start must be (task [N,T], mach [N,T])")
+    return task, mach
+
+
+def _start_population(start, P, N, T):
+    """`start`: one (task [N,T], mach [N,T]) or a list of S <= P, checked -> the population (task, mach [N,P,T]): member c = start c % S"""
+    starts = [start] if len(start) == 2 and np.ndim(start[0]) == 2 else list(start)
+    starts = [(np.ascontiguousarray(s[0], np.int32), np.ascontiguousarray(s[1], np.int32)) for s in starts]
+    if not 1 <= len(starts) <= P or any(s[0].shape != (N, T) or s[1].shape != (N, T) for s in starts):
+        raise ValueError("start must be (task [N,T], mach [N,T]) or a list of 1..P of them")
+    member = np.arange(P) % len(starts)
+    return np.stack([s[0] for s in starts], 1)[:, member], np.stack([s[1] for s in starts], 1)[:, member]
+
+
+def _search_result(g, name, table, rounds, **more):
+    """`g.finish`'s parts -> a plan search's result: the entry `name`, its plans, `more`, and every key of `table` in its shape — where no
+    pass recorded it (no rounds: a plain replay), start_obj is the replay's Objective and a per-round entry has no rows"""
+    r = g.collect(last_axis=[key for key, _, rows in table if rows is not None])
+    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, g.T, g.w)
+    for key, dt, rows in table:
+        if rows is None:
+            out[key] = r[key] if key in r else out[name][2].copy()
+        else:
+            out[key] = r[key].reshape(rounds + rows, g.N) if key in r else np.zeros((rounds + rows, g.N), dt)
+    out.update(more)
+    return out
+
+
 def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL_MOVES, left_shift=False, chunk=None, device=0,
                  obs_dtype="f32", name="LS", replay="steps"):
     """Hill climbing from the plans `start` = (task [N,T], mach [N,T]) — any plan the library returns: PLANS of `pdr_baselines`,
@@ -417,35 +472,25 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
     N, T = CopyGroups.sizes(t, args)
     K, R, moves = int(K), int(rounds), int(moves)
     CopyGroups.check_mode(replay)
-    if not 1 <= K <= 4096:
-        raise ValueError("K must be 1..4096")
-    if R < 0 or not 1 <= moves <= (ALL_MOVES | CRIT_MOVES):
-        raise ValueError("rounds must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN | MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN")
-    _rule_names([(name,), ("start_obj",), ("history",), ("accepted",)])
-    st_task, st_mach = np.ascontiguousarray(start[0], np.int32), np.ascontiguousarray(start[1], np.int32)
-    if st_task.shape != (N, T) or st_mach.shape != (N, T):
-        raise ValueError("start must be (task [N,T], mach [N,T])")
+    _check_copies("K", K)
+    _check_rounds_moves("rounds", R, moves, ALL_MOVES | CRIT_MOVES)
+    _check_name(name, LOCAL_RESULT)
+    st_task, st_mach = _start_plans(start, N, T)
     with CopyGroups(t, p, tt, edge, args, K, chunk, copies=R > 0, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
-        n, dev, env, top = g.n, g.dev, g.env, g.top
+        n, dev, env = g.n, g.dev, g.env
         path = None
         if R:
             obj0 = torch.empty(n * K, dtype=torch.float64, device=dev)
             best = torch.empty(R, n, dtype=torch.int32, device=dev)
             hist = torch.empty(R, n, dtype=torch.float64, device=dev)
             kind = torch.empty(R, n * K, dtype=torch.int8, device=dev)
-            if moves & CRIT_MOVES:                                      # every group's critical path: tasks, arcs, length
-                path = (torch.empty(n, T, dtype=torch.int32, device=dev), torch.empty(n, T, dtype=torch.int8, device=dev),
-                        torch.empty(n, dtype=torch.int32, device=dev))
+            if moves & CRIT_MOVES:
+                path = g.path_bufs()
         for lo, m in g.passes():
-            cur_t = torch.as_tensor(np.ascontiguousarray(g.pad(st_task).T), device=dev)     # [T,n]: row s = the actions of step s
-            cur_m = torch.as_tensor(np.ascontiguousarray(g.pad(st_mach).T), device=dev)
+            cur_t, cur_m = g.upload(st_task), g.upload(st_mach)
             col = None
             if path is not None:                                        # the start plans' schedules, for round 0's directed moves
-                top.scaler_init()
-                top.reset(g.w3_top)
-                for s in range(T):
-                    top.step(cur_t[s], cur_m[s])
-                top.critical_path(None, None, *path)
+                g.prime_paths(cur_t, cur_m, path)
             for r in range(R):
                 out_t, out_m = g.plan_bufs(r)
                 env.plan_neighbours(K, cur_t, cur_m, col, seed, r, lo, moves, out_t, out_m, kind[r], critical=path)
@@ -458,13 +503,7 @@ def local_search(t, p, tt, edge, args, start, K=16, rounds=32, seed=0, moves=ALL
                 g.finish(cur_t, cur_m, col, f"{name} local-search", start_obj=obj0.view(n, K)[:, 0], history=hist, accepted=acc)
             else:
                 g.finish(cur_t, cur_m, None, f"{name} local-search")
-    r = g.collect(last_axis=("history", "accepted"))
-    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
-    if R:
-        out.update(start_obj=r["start_obj"], history=r["history"], accepted=r["accepted"])
-    else:
-        out.update(start_obj=out[name][2].copy(), history=np.zeros((0, N)), accepted=np.zeros((0, N), np.int8))
-    return out
+    return _search_result(g, name, LOCAL_RESULT, R)
 
 
 # ---- a walk on plans (csrc/mtfjsp_walk.hip): the local search's round with an acceptance rule that can leave a local optimum
@@ -493,10 +532,8 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
     N, T = CopyGroups.sizes(t, args)
     K, R, moves, tabu, late = int(K), int(rounds), int(moves), int(tabu), int(late)
     CopyGroups.check_mode(replay)
-    if not 1 <= K <= 4096:
-        raise ValueError("K must be 1..4096")
-    if R < 0 or not 1 <= moves <= (ALL_MOVES | CRIT_MOVES):
-        raise ValueError("rounds must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN | MOVE_CRIT_SWAP | MOVE_CRIT_REASSIGN")
+    _check_copies("K", K)
+    _check_rounds_moves("rounds", R, moves, ALL_MOVES | CRIT_MOVES)
     if not 0 <= tabu <= 1024 or not 0 <= late <= 4096:
         raise ValueError("tabu must be 0..1024 and late 0..4096")
     if slack is None or np.ndim(slack) == 0:
@@ -505,12 +542,10 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
         slacks = [float(x) for x in slack]
         if len(slacks) != R:
             raise ValueError("slack must be None, one number or a sequence of `rounds` numbers")
-    _rule_names([(name,), ("start_obj",), ("history",), ("current",), ("accepted",), ("why",), ("barred",)])
-    st_task, st_mach = np.ascontiguousarray(start[0], np.int32), np.ascontiguousarray(start[1], np.int32)
-    if st_task.shape != (N, T) or st_mach.shape != (N, T):
-        raise ValueError("start must be (task [N,T], mach [N,T])")
+    _check_name(name, WALK_RESULT)
+    st_task, st_mach = _start_plans(start, N, T)
     with CopyGroups(t, p, tt, edge, args, K, chunk, copies=R > 0, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
-        n, dev, env, top = g.n, g.dev, g.env, g.top
+        n, dev, env = g.n, g.dev, g.env
         path = None
         if R:
             obj0 = torch.empty(n * K, dtype=torch.float64, device=dev)
@@ -520,19 +555,13 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
             kind = torch.empty(R, n * K, dtype=torch.int8, device=dev)
             why, barred = torch.empty(R, n, dtype=torch.int8, device=dev), torch.empty(R, n, dtype=torch.int32, device=dev)
             state = env.walk_state(n, late, tabu)
-            if moves & CRIT_MOVES:                                      # every group's critical path: tasks, arcs, length
-                path = (torch.empty(n, T, dtype=torch.int32, device=dev), torch.empty(n, T, dtype=torch.int8, device=dev),
-                        torch.empty(n, dtype=torch.int32, device=dev))
+            if moves & CRIT_MOVES:
+                path = g.path_bufs()
         for lo, m in g.passes():
-            cur_t = torch.as_tensor(np.ascontiguousarray(g.pad(st_task).T), device=dev)     # [T,n]: row s = the actions of step s
-            cur_m = torch.as_tensor(np.ascontiguousarray(g.pad(st_mach).T), device=dev)
+            cur_t, cur_m = g.upload(st_task), g.upload(st_mach)
             src = None
             if path is not None:                                        # the start plans' schedules, for round 0's directed moves
-                top.scaler_init()
-                top.reset(g.w3_top)
-                for s in range(T):
-                    top.step(cur_t[s], cur_m[s])
-                top.critical_path(None, None, *path)
+                g.prime_paths(cur_t, cur_m, path)
             for r in range(R):
                 out_t, out_m = g.plan_bufs(r)
                 env.plan_neighbours(K, cur_t, cur_m, src, seed, r, lo, moves, out_t, out_m, kind[r], critical=path)
@@ -549,15 +578,7 @@ def walk_search(t, p, tt, edge, args, start, K=16, rounds=64, seed=0, moves=ALL_
                          accepted=acc, why=why, barred=barred)
             else:
                 g.finish(cur_t, cur_m, None, f"{name} walk")
-    extra = ("history", "current", "accepted", "why", "barred")
-    r = g.collect(last_axis=extra)
-    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
-    if R:
-        out.update(start_obj=r["start_obj"], **{k: r[k] for k in extra})
-    else:
-        out.update(start_obj=out[name][2].copy(), history=np.zeros((0, N)), current=np.zeros((0, N)), accepted=np.zeros((0, N), np.int8),
-                   why=np.zeros((0, N), np.int8), barred=np.zeros((0, N), np.int32))
-    return out
+    return _search_result(g, name, WALK_RESULT, R)
 
 
 # ---- evolutionary search on plans (csrc/mtfjsp_evolve.hip): a population of P plans per instance, recombined generation by generation
@@ -582,21 +603,11 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
     N, T = CopyGroups.sizes(t, args)
     P, G, moves = int(P), int(generations), int(moves)
     CopyGroups.check_mode(replay)
-    if not 1 <= P <= 4096:
-        raise ValueError("P must be 1..4096")
-    if G < 0 or not 1 <= moves <= ALL_MOVES:
-        raise ValueError("generations must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN")
-    if not (0.0 <= float(p_cross) <= 1.0 and 0.0 <= float(p_mut) <= 1.0):
-        raise ValueError("p_cross and p_mut must be probabilities")
-    cross_thr, mut_thr = int(round(float(p_cross) * 2 ** 32)), int(round(float(p_mut) * 2 ** 32))
-    _rule_names([(name,), ("start_obj",), ("history",)])
-    starts = [start] if len(start) == 2 and np.ndim(start[0]) == 2 else list(start)
-    starts = [(np.ascontiguousarray(s[0], np.int32), np.ascontiguousarray(s[1], np.int32)) for s in starts]
-    if not 1 <= len(starts) <= P or any(s[0].shape != (N, T) or s[1].shape != (N, T) for s in starts):
-        raise ValueError("start must be (task [N,T], mach [N,T]) or a list of 1..P of them")
-    member = np.arange(P) % len(starts)
-    pop_task = np.stack([s[0] for s in starts], 1)[:, member]          # [N,P,T]: member c = start c % S
-    pop_mach = np.stack([s[1] for s in starts], 1)[:, member]
+    _check_copies("P", P)
+    _check_rounds_moves("generations", G, moves, ALL_MOVES)
+    cross_thr, mut_thr = _thresholds(p_cross, p_mut)
+    _check_name(name, EVOLVE_RESULT)
+    pop_task, pop_mach = _start_population(start, P, N, T)
     with CopyGroups(t, p, tt, edge, args, P, chunk, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
         n, dev, env = g.n, g.dev, g.env
         obj = torch.empty(n * P, dtype=torch.float64, device=dev)
@@ -604,8 +615,7 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
         hist = torch.empty(G + 1, n, dtype=torch.float64, device=dev)
         for lo, m in g.passes():
             cur_t, cur_m = g.plan_bufs(0)
-            cur_t.copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_task).reshape(n * P, T).T)))    # [T,n*P]: row s = the actions of step s
-            cur_m.copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_mach).reshape(n * P, T).T)))
+            g.upload(pop_task, cur_t); g.upload(pop_mach, cur_m)
             for gen in range(G + 1):
                 if gen:
                     out_t, out_m = g.plan_bufs(gen)
@@ -613,10 +623,7 @@ def evolve(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_cross=0.
                     cur_t, cur_m = out_t, out_m
                 g.round(cur_t, cur_m, obj, best[gen], hist[gen], replay)
             g.finish(cur_t, cur_m, best[G], f"{name} evolve", start_obj=hist[0], history=hist[1:])
-    r = g.collect(last_axis=("history",))
-    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
-    out.update(start_obj=r["start_obj"], history=r["history"].reshape(G, N))
-    return out
+    return _search_result(g, name, EVOLVE_RESULT, G)
 
 
 # ---- Pareto-front evolutionary search (csrc/mtfjsp_nsga.hip): parents and children ranked into fronts, the first P survive
@@ -648,19 +655,10 @@ def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_c
     CopyGroups.check_mode(replay)
     if not 8 <= P <= 1024:
         raise ValueError("P must be 8..1024 (the best Objective is only sure to survive among 8 or more)")
-    if G < 0 or not 1 <= moves <= ALL_MOVES:
-        raise ValueError("generations must be >= 0 and moves a non-empty mask of MOVE_SWAP | MOVE_INSERT | MOVE_REASSIGN")
-    if not (0.0 <= float(p_cross) <= 1.0 and 0.0 <= float(p_mut) <= 1.0):
-        raise ValueError("p_cross and p_mut must be probabilities")
-    cross_thr, mut_thr = int(round(float(p_cross) * 2 ** 32)), int(round(float(p_mut) * 2 ** 32))
-    _rule_names([(name,), ("start_obj",), ("history",), ("front_size",), ("fronts",)])
-    starts = [start] if len(start) == 2 and np.ndim(start[0]) == 2 else list(start)
-    starts = [(np.ascontiguousarray(s[0], np.int32), np.ascontiguousarray(s[1], np.int32)) for s in starts]
-    if not 1 <= len(starts) <= P or any(s[0].shape != (N, T) or s[1].shape != (N, T) for s in starts):
-        raise ValueError("start must be (task [N,T], mach [N,T]) or a list of 1..P of them")
-    member = np.arange(P) % len(starts)
-    pop_task = np.stack([s[0] for s in starts], 1)[:, member]          # [N,P,T]: member c = start c % S
-    pop_mach = np.stack([s[1] for s in starts], 1)[:, member]
+    _check_rounds_moves("generations", G, moves, ALL_MOVES)
+    cross_thr, mut_thr = _thresholds(p_cross, p_mut)
+    _check_name(name, PARETO_RESULT, "fronts")
+    pop_task, pop_mach = _start_population(start, P, N, T)
     fronts = []
     with CopyGroups(t, p, tt, edge, args, P, chunk, plans=True, left_shift=left_shift, obs_dtype=obs_dtype, device=device) as g:
         n, dev, env = g.n, g.dev, g.env
@@ -675,8 +673,7 @@ def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_c
         obj, best = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
         for lo, m in g.passes():
             pop, child, spare = slots
-            pop[0].copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_task).reshape(B, T).T)))      # [T,n*P]: row s = the actions of step s
-            pop[1].copy_(torch.as_tensor(np.ascontiguousarray(g.pad(pop_mach).reshape(B, T).T)))
+            g.upload(pop_task, pop[0]); g.upload(pop_mach, pop[1])
             g.replay(*pop, replay)
             env.front_rank(n, pop[2], pop[3], None, None, g.w, rank[:B], False, order[:B], size[0], hist[0])
             env.plan_survivors(P, order[:B], rank[:B], pop, None, child[0], child[1], child[2], child[3], pop_rank, False, fit)
@@ -696,10 +693,7 @@ def evolve_pareto(t, p, tt, edge, args, start, P=32, generations=32, seed=0, p_c
                 f4 = h_c4[sel]
                 fronts.append({"cost": np.stack([f4[:, 0], f4[:, 1] + f4[:, 3], f4[:, 2]], 1), "final4": f4, "obj": h_obj[sel],
                                "task": np.ascontiguousarray(h_task[sel]), "mach": np.ascontiguousarray(h_mach[sel])})
-    r = g.collect(last_axis=("history", "front_size"))
-    out = _results([name], {name: (r["cum"], r["prev"], r["task"], r["mach"])}, T, g.w)
-    out.update(start_obj=r["start_obj"], history=r["history"].reshape(G, N), front_size=r["front_size"].reshape(G + 1, N), fronts=fronts)
-    return out
+    return _search_result(g, name, PARETO_RESULT, G, fronts=fronts)
 
 
 def hypervolume(points, ref):

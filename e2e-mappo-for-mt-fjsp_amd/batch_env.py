@@ -85,6 +85,12 @@ class DeviceBatchEnv:
         self._sp_buf = None
         self.use_current_stream()
 
+    @classmethod
+    def like(cls, src, batch):
+        """a handle of `batch` instances like `src`: its sizes, left-shift setting, observation type, device, gamma, w_cfg and scaling divisor"""
+        return cls(src.J, src.M, src.E, batch, left_shift=src.left_shift, obs_dtype="f32" if src.obs_f32 else "f64", device=src.device.index or 0,
+                   gamma=src.gamma, w_cfg=src.w_cfg, scaling_divisor=src.scaling_divisor)
+
     def use_current_stream(self):
         s = torch.cuda.current_stream(self.device).cuda_stream
         capi.check(self.L.mtfjsp_set_stream(self.h, C.c_void_p(s)), self.h)

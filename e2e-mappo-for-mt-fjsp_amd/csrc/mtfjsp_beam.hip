@@ -172,9 +172,7 @@ extern "C" int mtfjsp_beam_select(mtfjsp_handle_t scratch, mtfjsp_handle_t beam,
     if (!sc.obs_bound || !sc.obs.raw) return mtfjsp_env_fail(scratch, MTFJSP_ERR_STATE, "mtfjsp_beam_select: the scratch handle needs bound observations with raw");
     if ((rc = mtfjsp_env_set_device(scratch, bm.device_id, "mtfjsp_beam_select"))) return rc;
     const size_t lds = (size_t)W * bm.T * (sig ? 16 : 8);
-    if (lds > 48 * 1024 && (rc = mtfjsp_env_hip_check(scratch, hipFuncSetAttribute((const void *)k_beam_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                                                      "mtfjsp_beam_select", "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed")))
-        return rc;
+    if ((rc = mtfjsp_env_dyn_lds(scratch, (const void *)k_beam_select, lds, "mtfjsp_beam_select"))) return rc;
     BeamArgs A{};
     A.W = W; A.T = bm.T; A.M = bm.M; A.MJ = bm.MJ; A.column = column; A.mj = bm.mj; A.status = sc.obs.status; A.raw = sc.obs.raw;
     A.score_in = score_in; A.sig = (const u64 *)sig; A.parent = parent_out; A.from_slot = from_slot_out; A.task = task_out; A.mach = mach_out;

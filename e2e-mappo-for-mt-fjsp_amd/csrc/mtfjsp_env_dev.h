@@ -148,6 +148,12 @@ __attribute__((visibility("hidden"))) int mtfjsp_env_fail(mtfjsp_handle_t h, int
 __attribute__((visibility("hidden"))) int mtfjsp_env_hip_check(mtfjsp_handle_t h, hipError_t e, const char *who, const char *msg);
 static inline int mtfjsp_env_set_device(mtfjsp_handle_t h, int device_id, const char *who) { return mtfjsp_env_hip_check(h, hipSetDevice(device_id), who, "hipSetDevice failed"); }
 static inline int mtfjsp_env_launched(mtfjsp_handle_t h, const char *who) { return mtfjsp_env_hip_check(h, hipGetLastError(), who, "launch failed"); }
+// before the launch of a kernel `fn` with `lds` bytes of dynamic LDS: above the 48 KiB every kernel may have, the attribute that allows them
+static inline int mtfjsp_env_dyn_lds(mtfjsp_handle_t h, const void *fn, size_t lds, const char *who)
+{
+    return lds <= 48 * 1024 ? MTFJSP_OK : mtfjsp_env_hip_check(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), who,
+                                                               "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+}
 // both views of a (scratch, source) pair of the look-ahead's shape — another handle of the same size on the same device, scratch batch =
 // source batch * T — or MTFJSP_ERR_ARG on the scratch handle; noun: what the message calls the source ("source", "beam")
 __attribute__((visibility("hidden"))) int mtfjsp_env_pair_views(const char *who, const char *noun, mtfjsp_handle_t scratch, mtfjsp_handle_t src, EnvHostView *sc,

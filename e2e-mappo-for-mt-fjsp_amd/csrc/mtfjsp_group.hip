@@ -5,9 +5,8 @@
 //                         evaluate.py's Final_4cost): makespan, processing energy / T, transport time, idle time
 //   mtfjsp_group_reduce   k_group_reduce: one workgroup per group — every copy's objective (test_all.py:536-538, evaluate.py's
 //                         Objective), the copy with the smallest one and the non-dominated copies in (makespan, energy, transport)
-// Arithmetic: ONE binary64 division in k_final_costs; in k_group_reduce one addition for the energy and the two products and two
-// additions of the objective, in numpy's order, never contracted.  Everything else is comparisons: both must equal a host model bit
-// for bit.
+// Arithmetic: ONE binary64 division in k_final_costs; in k_group_reduce the objective's (the rule: mtfjsp_copy_costs.h), never contracted.
+// Everything else is comparisons: both must equal a host model bit for bit.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -15,6 +14,7 @@
 
 #include "../../include/mtfjsp.h"
 
+#include "mtfjsp_copy_costs.h"
 #include "mtfjsp_env_dev.h"
 #include "mtfjsp_wave_select.h"
 
@@ -60,7 +60,7 @@ extern "C" int mtfjsp_final_costs(mtfjsp_handle_t h, double *cost4_out, uint8_t 
 // ---------------------------------------------------------------- group reduction
 struct GroupArgs {
     int K;
-    double w_mk, w_ec, w_tt;
+    CopyWeights w;
     const double *cost4;               // [N*K,4]
     const uint8_t *done;               // [N*K]
     double *obj;                       // [N*K] or null
@@ -69,12 +69,8 @@ struct GroupArgs {
     uint8_t *front;                    // [N*K] or null
 };
 
-// Copy c of group n lives in LDS as (mk, ec, tt, obj), 32 bytes; an ineligible copy (not done, or a NaN among mk, ec, tt) has NaN for
-// mk and obj there: every comparison with it is false, so it neither dominates nor is picked.  Thread tid owns copies tid, tid + 256,
-// ... (OWN of them at most: 1, 4 or 16 by K) and keeps them in registers: it alone writes their flags, and pass i of wave w over the
-// minimum — copies w*64 + 256*i + lane — is exactly its i-th owned copy, so the minimum reads no LDS.  A wave's later pass wins only
-// with a strictly smaller value and the four partial results are combined by (value, then lower c): the lowest index of the minimum
-// (WaveBest, mtfjsp_wave_select.h).
+// Copy c of group n lives in LDS as its record; thread tid owns copies tid, tid + 256, ... (OWN of them at most: 1, 4 or 16 by K), keeps them
+// in registers and alone writes their flags; the minimum runs over the owned copies (all of it: mtfjsp_copy_costs.h).
 // The dominance loop reads copy c' at one address for the whole workgroup (a broadcast read: no bank conflict at any pitch).
 template <int OWN>
 __global__ __launch_bounds__(GRP_THREADS) void k_group_reduce(GroupArgs A)
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(GRP_THREADS) void k_group_reduce(GroupArgs A)
     for (int i = 0; i < OWN; i++) {
         const int c = tid + i * GRP_THREADS;
         const double m = c0[i], e = c1[i] + c3[i], t = c2[i];
-        const double o = (A.w_mk * m + A.w_ec * e) + A.w_tt * t;
+        const double o = (A.w.mk * m + A.w.ec * e) + A.w.tt * t;
         el[i] = c < K && dn[i] != 0 && m == m && e == e && t == t;
         mk[i] = el[i] ? m : (double)NAN; ec[i] = e; tt[i] = t; ob[i] = el[i] ? o : (double)NAN;
         if (c < K) {
@@ -124,7 +120,8 @@ __global__ __launch_bounds__(GRP_THREADS) void k_group_reduce(GroupArgs A)
         if (A.best) A.best[blockIdx.x] = gi < 0 ? -1 : (int)(g0 + gi);
         if (A.best_obj) A.best_obj[blockIdx.x] = gi < 0 ? (double)NAN : cp[gi].w;   // the copy's own word (the minimum may be a zero of the other sign)
     }
-    // ---- the front: copy c is dominated by c' iff c' is nowhere worse and somewhere better, or equal throughout with c' < c
+    // ---- the front: copy c is dominated by c' iff c' is nowhere worse and somewhere better, or equal throughout with c' < c (copy_dominates,
+    // written out: through the function the loop's code changes and K > 256 is slower, profiles/HISTORY.md)
     if (!A.front) return;
     bool dom[OWN];
 #pragma unroll
@@ -150,10 +147,7 @@ template <int OWN>
 static int group_launch(mtfjsp_handle_t h, const EnvHostView &v, int N, const GroupArgs &A)
 {
     const size_t lds = (size_t)A.K * 32;
-    if (lds > 48 * 1024)
-        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)k_group_reduce<OWN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                                          "mtfjsp_group_reduce", "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
-            return rc;
+    if (int rc = mtfjsp_env_dyn_lds(h, (const void *)k_group_reduce<OWN>, lds, "mtfjsp_group_reduce")) return rc;
     hipLaunchKernelGGL(k_group_reduce<OWN>, dim3((unsigned)N), dim3(GRP_THREADS), lds, v.stream, A);
     return mtfjsp_env_launched(h, "mtfjsp_group_reduce");
 }
@@ -169,7 +163,7 @@ extern "C" int mtfjsp_group_reduce(mtfjsp_handle_t h, int32_t N, int32_t K, cons
     mtfjsp_env_host_view(h, &v);
     if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_group_reduce")) return rc;
     GroupArgs A{};
-    A.K = K; A.w_mk = w3cfg_host[0]; A.w_ec = w3cfg_host[1]; A.w_tt = w3cfg_host[2]; A.cost4 = cost4; A.done = done;
+    A.K = K; A.w = copy_weights(w3cfg_host); A.cost4 = cost4; A.done = done;
     A.obj = obj_out; A.best = best_out; A.best_obj = best_obj_out; A.front = front_out;
     if (K <= GRP_THREADS) return group_launch<1>(h, v, N, A);
     if (K <= 4 * GRP_THREADS) return group_launch<4>(h, v, N, A);

@@ -6,7 +6,7 @@
 //                           the group's selection order, the size of front 0 and the smallest objective
 //   mtfjsp_plan_survivors   k_plan_survivors: the first P candidates of every group's order, gathered into a population in history
 //                           layout with their costs, ranks and the position as the fitness the next tournaments compare
-// Arithmetic: the additions and products of k_group_reduce's objectives, and per candidate and axis one subtraction, one subtraction
+// Arithmetic: the additions and products of the objective (the rule: mtfjsp_copy_costs.h), and per candidate and axis one subtraction, one subtraction
 // and one division of the crowding distance and two additions of the three axes, never contracted.  Everything else is comparisons:
 // both must equal a host model bit for bit.
 // Cost of the peeling: 2 K dominance tests per candidate whatever the number of fronts (one pass counts every candidate's dominators,
@@ -19,6 +19,7 @@
 
 #include "../../include/mtfjsp.h"
 
+#include "mtfjsp_copy_costs.h"
 #include "mtfjsp_env_dev.h"
 #include "mtfjsp_plan_dev.h"
 #include "mtfjsp_wave_select.h"
@@ -31,7 +32,7 @@
 // ---------------------------------------------------------------- front ranks, crowding distance, selection order
 struct FrontArgs {
     int Ka, Kb;
-    double w_mk, w_ec, w_tt;
+    CopyWeights w;
     const double *cost4_a, *cost4_b;   // [N*Ka,4], [N*Kb,4] or null
     const uint8_t *done_a, *done_b;    // [N*Ka], [N*Kb] or null
     int *rank;                         // [N*K] or null
@@ -45,16 +46,7 @@ struct FrontArgs {
 // the lower index among equal ones or two NaNs
 __device__ __forceinline__ bool nsga_crowd_first(double dq, double dc) { return dq > dc || (dq == dq && dc != dc); }
 
-// candidate q with o = (mk, ec, tt, .) dominates candidate c (an ineligible one has NaN for mk on either side: false)
-__device__ __forceinline__ bool nsga_dominates(const double4 &o, int q, double mk, double ec, double tt, int c)
-{
-    const bool le = o.x <= mk && o.y <= ec && o.z <= tt;
-    const bool lt = o.x < mk || o.y < ec || o.z < tt;
-    return le && (lt || q < c);
-}
-
-// Candidate c of group n lives in LDS as k_group_reduce keeps it — (mk, ec, tt, obj), an ineligible one with NaN for mk and obj: every
-// comparison with it is false — with its rank (NSGA_UNRANKED while the peeling has not reached it, -1 for an ineligible one) and its
+// Candidate c of group n lives in LDS as its record (mtfjsp_copy_costs.h) with its rank (NSGA_UNRANKED while the peeling has not reached it, -1 for an ineligible one) and its
 // crowding distance beside it.  A workgroup has WAVES waves (one for K <= 64: four times as many groups per compute unit; else four);
 // thread tid owns candidates tid, tid + 64*WAVES, ... (OWN at most: 1, 4 or 8 by K): it alone writes their rank and distance.  Every loop over q reads one LDS address for the whole workgroup (a broadcast).
 template <int OWN, int WAVES>
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void k_front_rank(FrontArgs A)
     for (int i = 0; i < OWN; i++) {
         const int c = tid + i * THREADS;
         const double m = c0[i], e = c1[i] + c3[i], t = c2[i];
-        const double o = (A.w_mk * m + A.w_ec * e) + A.w_tt * t;
+        const double o = (A.w.mk * m + A.w.ec * e) + A.w.tt * t;
         const bool el = c < K && dn[i] != 0 && m == m && e == e && t == t;
         mk[i] = el ? m : (double)NAN; ec[i] = e; tt[i] = t; ob[i] = el ? o : (double)NAN;
         my[i] = el ? NSGA_UNRANKED : -1;
@@ -104,8 +96,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void k_front_rank(FrontArgs A)
         const int cw = wave * WAVE + i * THREADS;                      // (wave-uniform)
         if (cw < K) mine.pass(ob[i] == ob[i], ob[i], cw);
     }
-    // ---- phase 1, the peeling: rank r holds the unranked candidates that no unranked candidate dominates — c' dominates c iff it is
-    // nowhere worse and somewhere better, or equal throughout with c' < c.  One pass over q counts the dominators of every owned
+    // ---- phase 1, the peeling: rank r holds the unranked candidates that no unranked candidate dominates.  One pass over q counts the dominators of every owned
     // candidate; round r ranks the unranked candidates whose count is zero (a strict partial order: there is one while any is left),
     // and every wave then takes them off the counts of its own candidates: it scans the ranks 64 at a time and tests only the new
     // members.  Every candidate is tested against every other twice in all, however many fronts there are; a round costs K / 64 steps
@@ -116,7 +107,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void k_front_rank(FrontArgs A)
     for (int q = 0; q < K; q++) {
         const double4 o = cp[q];
 #pragma unroll
-        for (int i = 0; i < OWN; i++) cnt[i] += nsga_dominates(o, q, mk[i], ec[i], tt[i], tid + i * THREADS) ? 1 : 0;
+        for (int i = 0; i < OWN; i++) cnt[i] += copy_dominates(o, q, mk[i], ec[i], tt[i], tid + i * THREADS) ? 1 : 0;
     }
     for (int r = 0; r < K; r++) {
         bool left = false;
@@ -136,7 +127,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void k_front_rank(FrontArgs A)
                 m &= m - 1;
                 const double4 o = cp[q];
 #pragma unroll
-                for (int i = 0; i < OWN; i++) cnt[i] -= nsga_dominates(o, q, mk[i], ec[i], tt[i], tid + i * THREADS) ? 1 : 0;
+                for (int i = 0; i < OWN; i++) cnt[i] -= copy_dominates(o, q, mk[i], ec[i], tt[i], tid + i * THREADS) ? 1 : 0;
             }
         }
     }
@@ -228,10 +219,7 @@ static int front_launch(mtfjsp_handle_t h, const EnvHostView &v, int N, const Fr
 {
     void (*fn)(FrontArgs) = k_front_rank<OWN, WAVES>;
     const size_t lds = (size_t)(A.Ka + A.Kb) * NSGA_BYTES;
-    if (lds > 48 * 1024)
-        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                                          "mtfjsp_front_rank", "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
-            return rc;
+    if (int rc = mtfjsp_env_dyn_lds(h, (const void *)fn, lds, "mtfjsp_front_rank")) return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)N), dim3(WAVES * WAVE), lds, v.stream, A);
     return mtfjsp_env_launched(h, "mtfjsp_front_rank");
 }
@@ -249,7 +237,7 @@ extern "C" int mtfjsp_front_rank(mtfjsp_handle_t h, int32_t N, int32_t Ka, int32
     mtfjsp_env_host_view(h, &v);
     if (int rc = mtfjsp_env_set_device(h, v.device_id, "mtfjsp_front_rank")) return rc;
     FrontArgs A{};
-    A.Ka = Ka; A.Kb = Kb; A.w_mk = w3cfg_host[0]; A.w_ec = w3cfg_host[1]; A.w_tt = w3cfg_host[2];
+    A.Ka = Ka; A.Kb = Kb; A.w = copy_weights(w3cfg_host);
     A.cost4_a = cost4_a; A.done_a = done_a; A.cost4_b = cost4_b; A.done_b = done_b;
     A.rank = rank_out; A.crowd = crowd_out; A.order = order_out; A.front_size = front_size_out; A.best_obj = best_obj_out;
     const int K = Ka + Kb;

@@ -342,10 +342,7 @@ extern "C" int mtfjsp_critical_path(mtfjsp_handle_t h, int32_t n, const int32_t 
     A.inv_M = (unsigned)((0x100000000ull + (unsigned)v.M - 1) / (unsigned)v.M);
     A.sd = v.sd; A.pl = v.pl; A.tt = v.tt; A.col = col;
     A.path_task = path_task; A.path_arc = path_arc; A.path_len = path_len;
-    if (lds > 48 * 1024)
-        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)k_critical_path, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                                          "mtfjsp_critical_path", "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
-            return rc;
+    if (int rc = mtfjsp_env_dyn_lds(h, (const void *)k_critical_path, lds, "mtfjsp_critical_path")) return rc;
     hipLaunchKernelGGL(k_critical_path, dim3((unsigned)(((size_t)n + PLAN_WAVES - 1) / PLAN_WAVES)), dim3(PLAN_THREADS), lds, v.stream, A);
     return mtfjsp_env_launched(h, "mtfjsp_critical_path");
 }

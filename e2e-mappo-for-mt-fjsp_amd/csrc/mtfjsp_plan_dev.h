@@ -162,10 +162,7 @@ static inline int plan_launch_tiles(mtfjsp_handle_t h, const char *who, const En
     A.inv_M = (unsigned)((0x100000000ull + (unsigned)v.M - 1) / (unsigned)v.M); A.t = v.t;
     A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32); A.ctr_lo = (uint32_t)counter; A.first_lo = (uint32_t)first_instance;
     A.moves = moves; A.n_moves = (uint32_t)__builtin_popcount(moves); A.task_out = task_out; A.mach_out = mach_out; A.kind_out = kind_out;
-    if (lds > 48 * 1024)
-        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), who,
-                                          "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
-            return rc;
+    if (int rc = mtfjsp_env_dyn_lds(h, (const void *)fn, lds, who)) return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)(((size_t)v.B + tile - 1) / tile)), dim3(PLAN_THREADS), lds, v.stream, A);
     return mtfjsp_env_launched(h, who);
 }

@@ -354,10 +354,7 @@ extern "C" int mtfjsp_replay_plans(mtfjsp_handle_t h, const int32_t *task, const
     A.task = task; A.mach = mach; A.stride = stride; A.cost4 = cost4_out; A.done = done_out;
     const bool state = (flags & MTFJSP_REPLAY_STATE) != 0;
     A.sd = state ? const_cast<TaskSD *>(v.sd) : nullptr; A.pl = state ? const_cast<TaskPL *>(v.pl) : nullptr;
-    if (lds > 48 * 1024)
-        if (int rc = mtfjsp_env_hip_check(h, hipFuncSetAttribute((const void *)k_replay_plans, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), who,
-                                          "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"))
-            return rc;
+    if (int rc = mtfjsp_env_dyn_lds(h, (const void *)k_replay_plans, lds, who)) return rc;
     hipLaunchKernelGGL(k_replay_plans, dim3((unsigned)(((size_t)v.B + G - 1) / G)), dim3(G * WAVE), lds, v.stream, A);
     if (int rc = mtfjsp_env_launched(h, who)) return rc;
     mtfjsp_env_set_replayed(h, state ? 2 : 1);

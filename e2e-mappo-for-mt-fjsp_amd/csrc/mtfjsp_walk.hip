@@ -1,12 +1,11 @@
 // mtfjsp_walk.hip — the acceptance step of a search on plans that may leave a local optimum: in the round of the local search
 // (mtfjsp_plan_neighbours, replay, mtfjsp_final_costs) it takes the place of mtfjsp_group_reduce.
-//   mtfjsp_walk_accept    k_walk_accept: one workgroup per group — every copy's objective as k_group_reduce forms it, the candidates
+//   mtfjsp_walk_accept    k_walk_accept: one workgroup per group — every copy's objective (mtfjsp_copy_costs.h has the rule), the candidates
 //                         (not the incumbent's own schedule again, not a schedule of the tabu ring), the best of them, whether the walk
 //                         moves there (strictly better | within the slack | not above the late ring's entry), both rings' updates and
 //                         the best plan seen so far: the incumbent may get worse, so the best is kept beside it
-// Arithmetic: the objective's one addition, two products and two additions, in k_group_reduce's order, never contracted, and ONE addition
-// cur + slack.  Everything else is comparisons of binary64 and of 64-bit signatures: the kernel must equal a host model bit for bit
-// (tests/walk_ref.py).
+// Arithmetic: the objective's (the rule: mtfjsp_copy_costs.h), never contracted, and ONE addition cur + slack. Everything else is comparisons of
+// binary64 and of 64-bit signatures: the kernel must equal a host model bit for bit (tests/walk_ref.py).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -14,6 +13,7 @@
 
 #include "../../include/mtfjsp.h"
 
+#include "mtfjsp_copy_costs.h"
 #include "mtfjsp_env_dev.h"
 #include "mtfjsp_plan_dev.h"
 #include "mtfjsp_wave_select.h"
@@ -26,7 +26,8 @@
 
 struct WalkArgs {
     int N, K, T, first, late_len, tabu_len, late_slot;
-    double w_mk, w_ec, w_tt, slack;
+    CopyWeights w;
+    double slack;
     const double *cost4;               // [N*K,4]
     const uint8_t *done;               // [N*K]
     const uint64_t *sig;               // [N*K] or null
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(WALK_THREADS) void k_walk_accept(WalkArgs A)
     for (int i = 0; i < OWN; i++) {
         const int c = tid + i * WALK_THREADS;
         const double m = c0[i], e = c1[i] + c3[i], t = c2[i];
-        const double o = (A.w_mk * m + A.w_ec * e) + A.w_tt * t;
+        const double o = (A.w.mk * m + A.w.ec * e) + A.w.tt * t;
         const bool el = c < K && dn[i] != 0 && m == m && e == e && t == t;
         ob[i] = el ? o : (double)NAN;
         if (c < K && A.obj_out) A.obj_out[g0 + c] = ob[i];
@@ -206,7 +207,7 @@ extern "C" int mtfjsp_walk_accept(mtfjsp_handle_t h, int32_t N, int32_t K, const
     WalkArgs A{};
     A.N = N; A.K = K; A.T = v.T; A.first = first != 0; A.late_len = late_len; A.tabu_len = tabu_len;
     A.late_slot = late_len > 0 ? (int)(round % (uint64_t)late_len) : 0;
-    A.w_mk = w3cfg_host[0]; A.w_ec = w3cfg_host[1]; A.w_tt = w3cfg_host[2]; A.slack = slack;
+    A.w = copy_weights(w3cfg_host); A.slack = slack;
     A.cost4 = cost4; A.done = done; A.sig = sig; A.task = task; A.mach = mach;
     A.late = late; A.tabu = tabu; A.tabu_n = tabu_n; A.best_obj = best_obj; A.best_task = best_task; A.best_mach = best_mach;
     A.next_col = next_col; A.cur_out = cur_obj_out; A.best_out = best_obj_out; A.pick_out = pick_out; A.why_out = why_out;

@@ -37,6 +37,17 @@ def episode_results(cum, prev, T, w):
     return cost, final4, obj
 
 
+def config_w3(env, w):
+    """the config weights w = (w_mk, w_ec, w_tt) for every instance of `env`: the [B,3] device tensor an evaluation resets with"""
+    return torch.tensor([w], dtype=torch.float64, device=env.device).repeat(env.B, 1)
+
+
+def eval_reset(env, w3):
+    """An evaluation's reset (pdrs:675, env:1262 Random_weight_type="eval"): a fresh reward scaler (its output is not used), then the weights w3"""
+    env.scaler_init()
+    env.reset(w3)
+
+
 def replay_episode(env, T, actions, what):
     """T steps of the reset handle `env`, step s with the (task, mach) [B] int32 device tensors `actions(s)` returns, the raw rewards
     summed on the device; one synchronisation, then RuntimeError("<what> rollout: ...") if an instance met an invalid action or an
@@ -120,11 +131,12 @@ class CopyGroups:
     instances, n = chunk or N of them per pass, K copies of each side by side.  Three handles: `src` with the N loaded instances, `env`
     with the n*K copies (copy c of group i = element i*K + c; None with copies=False) and `top` with n, for the best copy of every
     group; per pass both take their constants from `src` by the explicit-index fork.  The constructor validates `chunk` and builds the
-    handles and index tensors (`copy_of`, `own`: every group's copy 0, `inst_of`, `w3_all`, `w3_top`: args' weights per element, or
-    w3 [K,3]: copy c of every group resets with w3[c]); leaving the `with` block closes the handles.  `passes()` iterates; `host`,
+    handles and index tensors (`copy_of`, `own`: every group's copy 0, `inst_of`, `w3_all`, `w3_top`: args' weights per element, or w3 [K,3]:
+    copy c of every group resets with w3[c]); leaving the `with` block closes the handles.  `passes()` iterates; `host`,
     `parts` and `collect()` gather the per-pass results.  `sizes(t, args)` gives N and T before anything is built.
-    For searches on plans (plans=True; [T, n*K] int32 histories, row s = the actions of step s): `plan_bufs(i)` are two pairs of them
-    that take turns, `round()` replays one on the copies (`replay()`) and reduces the groups, `finish()` replays every group's best plan on `top`."""
+    For searches on plans (plans=True; [T, n*K] int32 histories, row s = the actions of step s): `upload()` brings host plans into one,
+    `plan_bufs(i)` are two pairs of them that take turns, `round()` replays one on the copies (`replay()`) and reduces the groups,
+    `path_bufs()` / `prime_paths()` hold and first fill the critical paths of directed moves, `finish()` replays every group's best plan on `top`."""
 
     @staticmethod
     def sizes(t, args):
@@ -148,7 +160,7 @@ class CopyGroups:
             B = n * self.K
             if copies:                                                  # (every handle before the first tensor)
                 self.env = DeviceBatchEnv(J, M, E, B, **kw)
-            self.w3_top = torch.tensor([self.w], dtype=torch.float64, device=dev).repeat(n, 1)
+            self.w3_top = config_w3(self.top, self.w)
             self.inst_of = torch.arange(n, dtype=torch.int32, device=dev)
             if copies:
                 w3_k = torch.as_tensor(np.ascontiguousarray([self.w] if w3 is None else w3, np.float64), device=dev)
@@ -201,6 +213,23 @@ class CopyGroups:
     def plan_bufs(self, i):
         return self.bufs[i & 1]
 
+    def upload(self, plans, out=None):
+        """host plans [N,T] or [N,K,T] int32 -> this pass's device history [T,n] or [T,n*K], row s = the actions of step s (a new one, or `out`)"""
+        host = torch.as_tensor(np.ascontiguousarray(self.pad(plans).reshape(-1, self.T).T))
+        return host.to(self.dev) if out is None else out.copy_(host)
+
+    def path_bufs(self):
+        """every group's critical path, `DeviceBatchEnv.critical_path`'s outputs: (tasks [n,T] int32, arcs [n,T] int8, length [n] int32)"""
+        n, T, dev = self.n, self.T, self.dev
+        return torch.empty(n, T, dtype=torch.int32, device=dev), torch.empty(n, T, dtype=torch.int8, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+
+    def prime_paths(self, task, mach, path):
+        """the plans (task, mach) [T,n] replayed on `top` step by step, their schedules' critical paths into `path` (for round 0's directed moves)"""
+        eval_reset(self.top, self.w3_top)
+        for s in range(self.T):
+            self.top.step(task[s], mach[s])
+        self.top.critical_path(None, None, *path)
+
     REPLAY_MODES = ("steps", "launch")
 
     @classmethod
@@ -236,8 +265,7 @@ class CopyGroups:
         if col is not None:
             pick = torch.where(col < 0, self.own, col).long()
             task, mach = task.index_select(1, pick).contiguous(), mach.index_select(1, pick).contiguous()
-        self.top.scaler_init()
-        self.top.reset(self.w3_top)                                     # pdrs:675 reset(Random_weight_type="eval")
+        eval_reset(self.top, self.w3_top)
         cum, prev = replay_episode(self.top, self.T, lambda s: (task[s], mach[s]), what)
         self.parts.append(dict(cum=cum[:self.m], prev=prev[:self.m], task=self.host(task).T.copy(), mach=self.host(mach).T.copy(),
                                **{k: self.host(x) for k, x in extra.items()}))

@@ -181,3 +181,14 @@ def test_a_bad_start_plan_raises(what, gens):
     # beside valid starts it only never wins
     res = b.evolve(*data, args, [(task, mach), starts[1]], P=4, generations=gens, seed=SEED)
     assert (res["GA"][2] <= _start_objs("J3M4", False)[1]).all()
+
+
+def test_argument_errors():
+    b = _baselines()
+    data, args, starts, _ = _setup("J3M4")
+    for kw in (dict(moves=0), dict(moves=b.CRIT_MOVES), dict(P=0), dict(P=4097), dict(generations=-1), dict(chunk=0), dict(replay="other"),
+               dict(p_cross=1.5), dict(p_mut=-0.1), dict(P=STARTS - 1)):
+        with pytest.raises(ValueError):
+            b.evolve(*data, args, starts, **{**dict(P=4, generations=1), **kw})
+    with pytest.raises(ValueError):
+        b.evolve(*data, args, (starts[0][0][:, :-1], starts[0][1][:, :-1]), P=4, generations=1)

@@ -180,6 +180,8 @@ def test_argument_errors():
         b.evolve_pareto(*data, args, starts, P=8, generations=-1)
     with pytest.raises(ValueError):
         b.evolve_pareto(*data, args, starts, P=8, moves=8)
+    with pytest.raises(ValueError):
+        b.evolve_pareto(*data, args, starts, P=8, generations=1, replay="other")
 
 
 @pytest.mark.parametrize("gens", [0, 2])

@@ -152,3 +152,13 @@ def test_a_bad_start_plan_raises(what, rounds):
         b.local_search(*data, args, (task[:, :-1], mach[:, :-1]), K=4, rounds=1)
     with pytest.raises(ValueError):
         b.local_search(*data, args, start, K=4, rounds=1, moves=0)
+
+
+def test_argument_errors():
+    b = _baselines()
+    data, args, start, _ = _setup("J3M4")
+    for kw in (dict(moves=0), dict(moves=32), dict(K=0), dict(K=4097), dict(rounds=-1), dict(chunk=0), dict(replay="other")):
+        with pytest.raises(ValueError):
+            b.local_search(*data, args, start, **{**dict(K=4, rounds=1), **kw})
+    with pytest.raises(ValueError):
+        b.local_search(*data, args, (start[0][:, :-1], start[1][:, :-1]), K=4, rounds=1)

@@ -176,8 +176,52 @@ def test_a_bad_start_plan_raises(what, rounds):
 def test_argument_errors():
     b = _baselines()
     data, args, start, _ = _setup("J3M4")
-    for kw in (dict(moves=0), dict(K=0), dict(K=4097), dict(rounds=-1), dict(tabu=1025), dict(tabu=-1), dict(late=4097), dict(slack=[1.0, 0.0]), dict(chunk=0)):
+    for kw in (dict(moves=0), dict(K=0), dict(K=4097), dict(rounds=-1), dict(tabu=1025), dict(tabu=-1), dict(late=4097), dict(slack=[1.0, 0.0]), dict(chunk=0),
+               dict(replay="other")):
         with pytest.raises(ValueError):
             b.walk_search(*data, args, start, **{**dict(K=4, rounds=1), **kw})
     with pytest.raises(ValueError):
         b.walk_search(*data, args, (start[0][:, :-1], start[1][:, :-1]), K=4, rounds=1)
+
+
+def _layout(x, lead=True):
+    """(shape, dtype) of every array of a result, through its dicts, tuples and lists; lead=False: without the leading dimension"""
+    if isinstance(x, dict):
+        return {k: _layout(v, lead) for k, v in x.items()}
+    if isinstance(x, (tuple, list)):
+        return type(x).__name__, [_layout(v, lead) for v in x]
+    return (x.shape if lead else x.shape[1:]), x.dtype
+
+
+# the entries beside (name, PLANS, "start_obj", "history"): (key, dtype, leading dimension with no rounds)
+SEARCHES = {"local_search": ("rounds", "K", [("accepted", np.int8, 0)]),
+            "walk_search": ("rounds", "K", [("current", np.float64, 0), ("accepted", np.int8, 0), ("why", np.int8, 0), ("barred", np.int32, 0)]),
+            "evolve": ("generations", "P", []),
+            "evolve_pareto": ("generations", "P", [("front_size", np.int32, 1)])}
+
+
+@pytest.mark.parametrize("search", list(SEARCHES))
+def test_the_result_without_rounds_has_the_layout_of_one_with_rounds(search):
+    """rounds (generations) = 0: the exact key set and every entry's shape and dtype; with 2 the same keys and dtypes, and the same
+    shapes behind the leading dimension"""
+    b = _baselines()
+    data, args, start, (J, M, E, N) = _setup("J3M4")
+    count, copies, extra = SEARCHES[search]
+    T, f64, i32 = J * M, np.dtype(np.float64), np.dtype(np.int32)
+    run = lambda r: getattr(b, search)(*data, args, start, **{copies: 8, count: r}, seed=SEED, name="X")      # noqa: E731
+    res = run(0)
+    exp = {"X": ("tuple", [{key: ((N,), f64) for key in ref.COST_KEYS}, ((N, 4), f64), ((N,), f64)]),
+           b.PLANS: {"X": ("tuple", [((N, T), i32), ((N, T), i32)])}, "start_obj": ((N,), f64), "history": ((0, N), f64)}
+    exp.update({key: ((lead, N), np.dtype(dt)) for key, dt, lead in extra})
+    fronts = res.pop("fronts") if search == "evolve_pareto" else None
+    assert _layout(res) == exp
+    _same(_bits(res["start_obj"]), _bits(res["X"][2]), "start_obj is the entry's Objective (bits)")
+    two = run(2)
+    if fronts is not None:
+        two_fronts = two.pop("fronts")
+        assert isinstance(fronts, list) and len(fronts) == N
+        for f in fronts:
+            assert _layout(f, False) == {"cost": ((3,), f64), "final4": ((4,), f64), "obj": ((), f64), "task": ((T,), i32), "mach": ((T,), i32)}
+        assert _layout(two_fronts, False) == _layout(fronts, False)
+    assert _layout(two, False) == _layout(res, False)
+    assert two["history"].shape == (2, N) and all(two[key].shape == (lead + 2, N) for key, _, lead in extra)
