@@ -226,7 +226,8 @@ def gin_launches_for(batch, n_job, n_machine, num_cu=256, critic=False, candidat
     critic: the global critic asks (no candidates) instead of the job actor; candidates: per instance (default n_job, 0 for the critic);
     single_ok, reduce, product_mode: the handle's answers (its census passed; a statistics reduction is installed; its product mode); rows: rows per
     instance where they are not n_job * n_machine.  The streaming switches (MTFJSP_FUSE_GIN0, MTFJSP_FUSE_POOL, MTFJSP_FUSE_PAIR, MTFJSP_NO_STREAM_ORDER,
-    MTFJSP_STREAM_NT, MTFJSP_POOL_S, MTFJSP_FUSE_POOL_MAXT), MTFJSP_NO_RESIDENT_GIN and MTFJSP_GIN_RES_GENERIC are read from the environment per call."""
+    MTFJSP_STREAM_NT, MTFJSP_POOL_S, MTFJSP_FUSE_POOL_MAXT), MTFJSP_NO_RESIDENT_GIN and MTFJSP_GIN_RES_GENERIC are read from the environment per call
+    (defaults: csrc/mtfjsp_enc_switches.h, the table "Encoder switches" of DESIGN.md)."""
     flags = (GIN_CRITIC * bool(critic) | GIN_NODE_OUTPUT * bool(node_output) | GIN_PER_INSTANCE * bool(per_instance) | GIN_OBS_F64 * bool(obs_f64) |
              GIN_NO_SINGLE * (not single_ok) | GIN_REDUCE * bool(reduce))
     J = (0 if critic else n_job) if candidates is None else candidates
@@ -256,7 +257,7 @@ def heads_kernel_for(batch, n_job, n_machine, which=0, num_cu=256, gat=False, mh
     """(kernel name, instances per workgroup, workgroups): which heads kernel serves the job (which = 0) / machine (which = 1) actor's forward — the
     library's own rule (csrc/mtfjsp_heads_select.h), no GPU needed.  gat / mheads / env_tail / values_only: what the caller asks to ride in the launch;
     f32, gat_ok, mheads_ok: the handle's answers (product mode bit 4; its half of the two fusion conditions).  MTFJSP_NO_HEADS_HG8, MTFJSP_NO_HEADS10,
-    MTFJSP_FUSED3_NODES_HBM and MTFJSP_FUSED3_GENERIC are read from the environment per call."""
+    MTFJSP_FUSED3_NODES_HBM and MTFJSP_FUSED3_GENERIC are read from the environment per call (csrc/mtfjsp_enc_switches.h)."""
     flags = (HEADS_GAT * bool(gat) | HEADS_MHEADS * bool(mheads) | HEADS_ENV_TAIL * bool(env_tail) | HEADS_VALUES_ONLY * bool(values_only) |
              HEADS_F32 * bool(f32) | HEADS_NO_GAT * (not gat_ok) | HEADS_NO_MHEADS * (not mheads_ok) | HEADS_OBS_F64 * bool(obs_f64))
     group, grid = C.c_int32(0), C.c_int32(0)

@@ -2945,6 +2945,7 @@ static size_t inst_lds_bytes() { return (size_t)(HD * HD + 8 * 16 * LDA16 + 2 * 
 
 // =================================================================================================
 // host side
+#include "mtfjsp_enc_switches.h"
 struct mtfjsp_encoder {
     mtfjsp_encoder_config_t cfg;
     int T = 0;
@@ -2979,10 +2980,8 @@ struct mtfjsp_encoder {
     bool defer_poll = false;                // forward entries do not poll the asynchronous failure words: only mtfjsp_encoder_check reports them (mtfjsp_encoder_set_deferred_poll)
     mtfjsp_stats_reduce_fn reduce_fn = nullptr; void *reduce_user = nullptr;   // exact multi-shard BatchNorm: sums of every BN summed over the shards
     double reduce_scale = 1.0;              // global rows / local rows
-    // which products run with the f32 matrix instruction instead of the exact bf16 split (A/B reference; bits: 1 GIN products,
-    // 2 GAT passes, 4 heads, 8 first GIN Linear on the VALU); default from MTFJSP_GEMM_F32MFMA / _GAT_ / _HEADS_ / MTFJSP_GIN0_VALU
-    int f32_products = (getenv("MTFJSP_GEMM_F32MFMA") ? 1 : 0) | (getenv("MTFJSP_GAT_F32MFMA") ? 2 : 0) |
-                       (getenv("MTFJSP_HEADS_F32MFMA") ? 4 : 0) | (getenv("MTFJSP_GIN0_VALU") ? 8 : 0);
+    EncSwitches sw;                         // the run-time switches as they stood when the handle was created (mtfjsp_enc_switches.h), three of them lowered by what the device grants
+    int f32_products = 0;                   // the product mode (bits: mtfjsp_enc_switches.h; starts as sw.f32_products, then mtfjsp_encoder_set_product_mode and the range fallback)
     // resident GIN kernel (mtfjsp_gin_resident.h): eligibility decided at create time, then verified by a census launch
     bool res_ok = false; int res_ipc = 0, res_grid = 0;
     int res_last_kernel = -1;               // GinResKernel of the last single-launch forward (mtfjsp_encoder_gin_res_kernel_name)
@@ -2995,52 +2994,19 @@ struct mtfjsp_encoder {
     long long range_fallbacks = 0;          // times the handle switched to the f32-instruction kernels because of it
     bool res_eligible = false;              // the shape can use the single-launch kernel (res_ok: and the census passed / no failure since)
     long long res_failures = 0, res_launches = 0;
-    long long res_fail_at = getenv("MTFJSP_GIN_RES_FAIL_AT") ? atoll(getenv("MTFJSP_GIN_RES_FAIL_AT")) : 0;   // diagnostic: this launch's barriers time out
-    long long range_fail_at = getenv("MTFJSP_RANGE_FAIL_AT") ? atoll(getenv("MTFJSP_RANGE_FAIL_AT")) : 0, job_forwards = 0;   // diagnostic: the n-th job-actor forward raises the range word (as a NaN output would)
+    long long job_forwards = 0;
     unsigned long long res_epoch = 0;
     int gat_slot = 0;                       // the machine-path slot of the NEXT forward; the other one is zeroed by that forward's heads kernel
     struct { bool valid = false; const void *f1 = nullptr, *f2 = nullptr; int slot = 0;
              bool heads = false; const float *h_pooled_o = nullptr; const uint8_t *mmask = nullptr; float *prob = nullptr, *h_pooled = nullptr, *machine_v = nullptr;
            } prefused;   // the GAT passes of the coming machine forward already ran inside the job actor's heads launch (k_headsx_gat3x); heads: the WHOLE machine forward did (k_headsx_gat3x_headsx)
-    bool fuse_gat = !getenv("MTFJSP_NO_FUSED_GAT");
-    bool fuse_mheads = !getenv("MTFJSP_NO_FUSED_MHEADS");       // the machine heads in the job heads + GAT launch behind an in-launch exchange of the node statistics (three launches per rollout step)
     struct { bool armed = false; float *prob = nullptr, *h_pooled = nullptr, *machine_v = nullptr; } mh;   // mtfjsp_encoder_arm_machine_heads
     unsigned long long *xw = nullptr;       // [2 sets][XW_SET] count-carrying words of that exchange; forward n uses set n & 1 and zeroes the other
     unsigned long long xw_epoch = 0;
     long long fused3_launches = 0;
     int fused3_last_kernel = -1;            // Fused3Kernel of the last three-in-one launch (mtfjsp_encoder_fused3_kernel_name)
     struct { int kernel = -1, three = 0, hg = 0, grid = 0; } heads_last[2];   // HeadsKernel (Fused3Kernel), instances per workgroup and workgroups of the launch that computed the last job [0] / machine [1] forward (mtfjsp_encoder_heads_kernel_name)
-    double xchg_fine_limit = getenv("MTFJSP_XCHG_FINE_LIMIT") ? atof(getenv("MTFJSP_XCHG_FINE_LIMIT")) : 2147483648.0;   // diagnostic: a lower limit sends ordinary contributions through the wide-range words
-    long long fused3_fail_at = getenv("MTFJSP_FUSED3_FAIL_AT") ? atoll(getenv("MTFJSP_FUSED3_FAIL_AT")) : 0;   // diagnostic: this three-in-one launch waits for a workgroup that does not exist
-    bool heads_hg8 = !getenv("MTFJSP_NO_HEADS_HG8");
-    bool heads10 = !getenv("MTFJSP_NO_HEADS10");              // k_headsx10 (ten tiles per chunk) for groups of 7..10 tiles
-    // the environment step as the tail of the machine heads' launch (mtfjsp_encoder_arm_env_step).  OFF unless MTFJSP_FUSED_ENV is set:
-    // bit-identical (tests/test_fused_env_step_gpu.py) and one launch less per step, but measured SLOWER at the headline shape —
-    // 220.4 against 217.6 us per step, three alternating runs on one box — because the heads' 8 waves take the 16 instances in two
-    // rounds where k_env_grp16's 16 waves take them in one: the second round costs more than the launch boundary saves
-    bool fuse_env = getenv("MTFJSP_FUSED_ENV") != nullptr;
-    // Round 6: the step as the tail of the THREE-in-one launch (k_headsx_gat3x_headsx<1|2>) with its state lines requested 13 us ahead:
-    // two launches per rollout step, bit-identical (tests/test_fused_env_step_gpu.py).  OFF unless MTFJSP_FUSED_ENV3 is set: measured
-    // SLOWER again — 0.1772-0.1786 against 0.1750-0.1751 ms per step, three alternating runs on one box (tools/ab_bench_env3.sh,
-    // profiles/r06_ab_env3.txt): the launch's 8 waves take the 16 instances in two rounds behind one another, which costs about 3 us
-    // more than the launch boundary and the separate kernel's dispatch ramp together, warm state lines or not.
-    bool fuse_env3 = getenv("MTFJSP_FUSED_ENV3") != nullptr;
-    bool nodes_lds = !getenv("MTFJSP_FUSED3_NODES_HBM");         // three-in-one launch: the GAT part's node rows stay in LDS for the machine part (round 6)
-    bool warm_heads = !getenv("MTFJSP_NO_WARM_HEADS");          // k_gin_res requests the heads launch's weight lines in its last phase
-    struct { bool armed = false, done = false; EnvParams P; } env_step;          // groups of 8 instances in k_headsx when groups of 16 fill at most half the CUs
-    // streaming GIN launches: the two inner Linears of an MLP in one launch behind a statistics-only pass (mtfjsp_gemm_pair.h).
-    // MTFJSP_FUSE_PAIR=1: always; -1: where the activation matrix exceeds the 256 MB memory-side cache; 0 (default): never —
-    // measured (round 5, J10M10 x 8192 / J20M20 x 2048): statistics-only pass 102 us + pair launch 203 us against 2 x 148 us for the two
-    // launches: a consumer wave runs BOTH products of a step's four tiles back to back (8 tile products, ~10 k cycles per step) and
-    // is the critical path; the 25 % of HBM traffic saved does not show because these launches are bound by the SIMDs' instruction
-    // issue (~100 us per launch even with no output at all), not by memory
-    int fuse_pair = getenv("MTFJSP_FUSE_PAIR") ? atoi(getenv("MTFJSP_FUSE_PAIR")) : 0;
-    int stream_order = getenv("MTFJSP_NO_STREAM_ORDER") ? 0 : 1;   // streaming GIN launches: alternating row direction + non-temporal input reads (A/B switch)
-    // (what each of these switches changes in a forward's launches: gin_plan, mtfjsp_gin_select.h — the handle only holds their values)
-    int fuse_pool = getenv("MTFJSP_FUSE_POOL") ? atoi(getenv("MTFJSP_FUSE_POOL")) : 1;   // the last Linear's output pooled / gathered in a second pass' epilogue instead of stored
-    int fuse_gin0 = getenv("MTFJSP_FUSE_GIN0") ? atoi(getenv("MTFJSP_FUSE_GIN0")) : 1;   // the first Linear's output formed again by the second launch's producers instead of stored
-    int pool_s = getenv("MTFJSP_POOL_S") ? atoi(getenv("MTFJSP_POOL_S")) : 4;      // k_job_pool_gather: blocks per row range of the last product (0: plain instance order)
-    int stream_nt = getenv("MTFJSP_STREAM_NT") ? atoi(getenv("MTFJSP_STREAM_NT")) : 5;   // which readers use non-temporal loads: 1 BatchNorm+ReLU products, 2 aggregation product, 4 pool / gather
+    struct { bool armed = false, done = false; EnvParams P; } env_step;          // mtfjsp_encoder_arm_env_step
     mtfjsp_mfea1_ctx_t mf_ctx{}; bool mf_armed = false;
     struct FusedSample { bool armed = false; int greedy = 0; uint64_t seed = 0, counter = 0; int32_t *idx = nullptr; float *logp = nullptr;
                          const int32_t *gather_from = nullptr; int32_t *gathered = nullptr; } fs[2];   // [0] job actor, [1] machine actor
@@ -3199,6 +3165,7 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
     if (cfg->device_id < 0 || cfg->device_id >= ndev) { g_enc_err = "device_id out of range"; return MTFJSP_ERR_ARG; }
     if (hipSetDevice(cfg->device_id) != hipSuccess) { g_enc_err = "hipSetDevice failed"; return MTFJSP_ERR_HIP; }
     mtfjsp_encoder *e = new mtfjsp_encoder();
+    e->sw = enc_switches_read(); e->f32_products = e->sw.f32_products;
     e->cfg = *cfg;
     e->T = cfg->n_job * cfg->n_machine;
     hipDeviceProp_t prop;
@@ -3236,7 +3203,7 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
     (void)hipFuncSetAttribute((const void *)k_gemm_x6<PRO_AGG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_x6_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_gemm_x6<PRO_GIN0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_x6_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_gemm_x6<PRO_GIN0BN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_x6_lds_bytes());
-    if (hipFuncSetAttribute((const void *)k_gemm_x6f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_x6f_lds_bytes()) != hipSuccess) e->fuse_pair = 0;
+    if (hipFuncSetAttribute((const void *)k_gemm_x6f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_x6f_lds_bytes()) != hipSuccess) e->sw.fuse_pair = 0;
     (void)hipFuncSetAttribute((const void *)k_gin_inst<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_gin_inst<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst_lds_bytes());
     (void)hipFuncSetAttribute((const void *)k_gat_inst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst_lds_bytes());
@@ -3245,15 +3212,15 @@ extern "C" int mtfjsp_encoder_create(const mtfjsp_encoder_config_t *cfg, mtfjsp_
         if (r.kernel == HEADS_K_VALUES) continue;                    // (this diagnostic build never asked for it)
 #endif
         if (hipFuncSetAttribute(r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds) == hipSuccess) continue;
-        if (r.kernel == HEADS_K_X10) e->heads10 = false;
-        if (r.kernel == HEADS_K_FUSED3 && r.env == 0 && !r.nlds) e->fuse_mheads = false;
+        if (r.kernel == HEADS_K_X10) e->sw.heads10 = false;
+        if (r.kernel == HEADS_K_FUSED3 && r.env == 0 && !r.nlds) e->sw.fuse_mheads = false;
     }
 #if MTFJSP_BODY_FUNCS
-    e->fuse_mheads = false;
+    e->sw.fuse_mheads = false;
 #endif
     {   // resident GIN kernel: whole instances per workgroup, at most 576 rows, one workgroup per CU
         const GinResPlan pl = gin_res_plan_of(e);
-        if (!getenv("MTFJSP_NO_RESIDENT_GIN") && pl.eligible) {
+        if (!enc_no_resident_gin() && pl.eligible) {
             const int ipc = pl.ipc, grid = pl.grid;
             if (hipFuncSetAttribute((const void *)k_gin_res, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess &&
                 hipFuncSetAttribute((const void *)k_gin_res_t36j6x16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gin_res_lds_bytes()) == hipSuccess) {
@@ -3666,18 +3633,14 @@ struct GinIO {
     const void *tasks_fea; const int32_t *ell_col; const float *ell_val; const int32_t *candidate; int J;
     float *h_pooled, *cand_feat, *h_nodes;
 };
-// the request of a forward on this handle (mtfjsp_gin_select.h).  The create-time switches by the handle's values, MTFJSP_FUSE_POOL_MAXT once per process
-// (J10M10 x 8192: 264 us pooled in the heads launch, 240 us apart), MTFJSP_GIN_RES_GENERIC as it is NOW
+// the request of a forward on this handle (mtfjsp_gin_select.h): the switches as mtfjsp_enc_switches.h says when each is read, then the handle's own
 static GinRequest gin_request(const mtfjsp_encoder *e, const GinWeights &gw, bool job_actor, int J, bool h_nodes)
 {
-    static const int fuse_maxT = getenv("MTFJSP_FUSE_POOL_MAXT") ? atoi(getenv("MTFJSP_FUSE_POOL_MAXT")) : 64;
     GinRequest q{};
+    gin_request_switches(q, e->sw); q.heads_pool_maxT = enc_heads_pool_maxT_once();
     q.B = e->cfg.batch; q.T = e->T; q.n_job = e->cfg.n_job; q.J = J; q.num_cu = e->num_cu; q.obs_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64;
     q.job_actor = job_actor; q.h_nodes = h_nodes; q.per_instance = e->bn_mode != 0;
     q.res_ok = e->res_ok; q.reduce = e->reduce_fn != nullptr; q.f32_products = e->f32_products; q.last_wx6 = gw.l[5].Wx6 != nullptr;
-    q.fuse_pair = e->fuse_pair; q.fuse_gin0 = e->fuse_gin0; q.fuse_pool = e->fuse_pool;
-    q.stream_order = e->stream_order; q.stream_nt = e->stream_nt; q.pool_s = e->pool_s; q.heads_pool_maxT = fuse_maxT;
-    q.force_generic = getenv("MTFJSP_GIN_RES_GENERIC");
     return q;
 }
 static double *gin_slot(const mtfjsp_encoder *e, int s) { return e->stats + s * STAT_REP * 256; }
@@ -3810,7 +3773,7 @@ static int run_gin_resident(mtfjsp_encoder *e, const GinPlan &gp, const GinWeigh
     a.bar = e->res_bar; a.epoch = e->res_epoch++; a.fail = e->res_fail; a.range_flag = e->range_flag;
     a.candidate = candidate; a.pooled = h_pooled; a.cand_feat = cand_feat; a.h_nodes = h_nodes; a.zspill = nullptr;
     a.inv_rows = 1.0 / ((double)B * (double)T);
-    if (warm && e->warm_heads) {
+    if (warm && e->sw.warm_heads) {
         // what the heads launch behind this one reads first — the weight images of both actors' heads and of the GAT passes, last read a
         // rollout step ago and evicted from the XCDs' L2 since — is requested (one word per 128-byte line, dropped) in this kernel's last phase
         const char *keys[9] = {"job_actor.o_policy.linears.0.weight", "job_actor.job_critic.linears.0.weight", "job_actor.o_policy.linears.1.weight",
@@ -3825,7 +3788,7 @@ static int run_gin_resident(mtfjsp_encoder *e, const GinPlan &gp, const GinWeigh
         auto q = e->wfused.find("machine_actor.q");               // the GAT projection's operand image (8 KB), once it has been formed
         if (q != e->wfused.end() && !e->wfused_stale.count("machine_actor.q") && a.nwarm < GR_MAXWARM) { a.warm[a.nwarm] = q->second; a.warm_lines[a.nwarm] = 64; a.nwarm++; }
     }
-    if (++e->res_launches == e->res_fail_at) a.expect_extra = 1u;      // (diagnostic) this launch's barriers never complete
+    if (++e->res_launches == e->sw.res_fail_at) a.expect_extra = 1u;      // (diagnostic) this launch's barriers never complete
 #ifdef GR_STAMP
     static unsigned long long *d_st = nullptr;
     if (!d_st) (void)hipMalloc((void **)&d_st, 256 * 64 * 8);
@@ -3956,14 +3919,14 @@ static int gat3x_args(mtfjsp_encoder *e, const std::string &pre, const void *m_f
 // parts (16), m_fea1 produced by that launch itself, whole-batch statistics without a cross-shard reduction, split products.
 static bool gat_fusable(const mtfjsp_encoder *e)
 {
-    return e->fuse_gat && !e->bn_mode && !e->reduce_fn && !(e->f32_products & (2 | 4)) && heads_gat_ride_shape(e->cfg.batch, e->cfg.n_machine, e->num_cu) &&
+    return e->sw.fuse_gat && !e->bn_mode && !e->reduce_fn && !(e->f32_products & (2 | 4)) && heads_gat_ride_shape(e->cfg.batch, e->cfg.n_machine, e->num_cu) &&
            e->w.count("machine_actor.gat_layer.W") && e->wx6.count("machine_actor.gat_layer.W");
 }
 // ... and the machine actor's heads as well (k_headsx_gat3x_headsx)?  The in-launch exchange needs every workgroup resident at once:
 // one per CU, on a device where the census of the single-launch GIN kernel found all of them available (the shape's half: fused3_plan).
 static bool mheads_fusable(const mtfjsp_encoder *e)
 {
-    return e->fuse_mheads && e->res_ok && gat_fusable(e) && e->xw &&
+    return e->sw.fuse_mheads && e->res_ok && gat_fusable(e) && e->xw &&
            fused3_plan(e->cfg.batch, e->cfg.n_job, e->cfg.n_machine, e->T, e->num_cu, false, nullptr, false, nullptr).eligible &&
            e->wx6.count("machine_actor.m_policy.linears.0.weight") && e->wx6.count("machine_actor.machine_critic.linears.0.weight");
 }
@@ -4210,8 +4173,8 @@ static XchgArgs fused3_exchange(mtfjsp_encoder *e, int grid)
     const int set = (int)(e->xw_epoch++ & 1);
     xg.words = e->xw + (size_t)set * XW_SET; xg.words_next = e->xw + (size_t)(set ^ 1) * XW_SET;
     xg.nblk = (unsigned)grid; xg.fail = e->res_fail; xg.range_flag = e->range_flag;
-    xg.fine_limit = e->xchg_fine_limit > 0 && e->xchg_fine_limit <= 2147483648.0 ? e->xchg_fine_limit : 2147483648.0;
-    if (++e->fused3_launches == e->fused3_fail_at) xg.nblk += 8;      // (diagnostic) every group's count stays one short: the time-out path
+    xg.fine_limit = e->sw.xchg_fine_limit > 0 && e->sw.xchg_fine_limit <= 2147483648.0 ? e->sw.xchg_fine_limit : 2147483648.0;
+    if (++e->fused3_launches == e->sw.fused3_fail_at) xg.nblk += 8;      // (diagnostic) every group's count stays one short: the time-out path
 #ifdef MTFJSP_STAMP3
     if (!g_st3) { (void)hipMalloc((void **)&g_st3, (size_t)2048 * 64 * 8); (void)hipMemset(g_st3, 0, (size_t)2048 * 64 * 8); }
     xg.stamps = g_st3;
@@ -4267,8 +4230,9 @@ static int launch_heads(mtfjsp_encoder *e, const HeadsPlan &pl, int which, HeadA
 static HeadsRequest heads_request(const mtfjsp_encoder *e, int R)
 {
     HeadsRequest q{};
+    heads_request_switches(q, e->sw);
     q.B = e->cfg.batch; q.R = R; q.M = e->cfg.n_machine; q.T = e->T; q.num_cu = e->num_cu;
-    q.f32 = (e->f32_products & 4) != 0; q.hg8 = e->heads_hg8; q.heads10 = e->heads10; q.nodes_hbm = !e->nodes_lds;
+    q.f32 = (e->f32_products & 4) != 0;
     q.obs_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64;
     return q;
 }
@@ -4337,7 +4301,7 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device_id));
     if (!e->defer_poll && (rc = res_poll_failure(e))) return rc;
-    if (++e->job_forwards == e->range_fail_at && e->res_fail_host) e->res_fail_host[1] = 1u;   // (diagnostic, MTFJSP_RANGE_FAIL_AT)
+    if (++e->job_forwards == e->sw.range_fail_at && e->res_fail_host) e->res_fail_host[1] = 1u;   // (diagnostic, MTFJSP_RANGE_FAIL_AT)
     const int B = e->cfg.batch, J = e->cfg.n_job;
     auto W = [&](const std::string &k) { return e->w.at(k); };
     auto WI = [&](const std::string &k) { return e->wimg.at(k); };
@@ -4370,10 +4334,10 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
     rq.mheads_ok = rq.gat_ok && rq.mheads && mheads_fusable(e);
     // an environment step armed BEFORE this forward (mtfjsp_encoder_arm_env_step) rides in the three-in-one launch when the machine
     // selection made there is the one it reads and the shapes agree (round 6: two launches per rollout step)
-    rq.env_tail = rq.mheads_ok && e->env_step.armed && e->fuse_env3 && !e->timing && e->fs[0].armed &&
+    rq.env_tail = rq.mheads_ok && e->env_step.armed && e->sw.fuse_env3 && !e->timing && e->fs[0].armed &&
                   (const void *)e->fs[1].idx == (const void *)EP.mach_idx && (const void *)e->fs[0].gathered == (const void *)EP.task_idx &&
                   EP.B == B && EP.M == e->cfg.n_machine && env_one_slot(EP.J, EP.M, EP.T) && fused3_lds_bytes() >= EnvGrpDynLds<1>::bytes;
-    if (rq.mheads_ok) { rq.obs_f64 = rq.env_tail ? !EP.obs_f32 : (rq.obs_f64 || !e->mf_ctx.obs_f32); rq.force_generic = getenv("MTFJSP_FUSED3_GENERIC"); }
+    if (rq.mheads_ok) rq.obs_f64 = rq.env_tail ? !EP.obs_f32 : (rq.obs_f64 || !e->mf_ctx.obs_f32);
     const HeadsPlan hp = heads_plan(rq);
     const bool with_gat = hp.kernel == HEADS_K_GAT3X || hp.kernel == HEADS_K_FUSED3, with_mheads = hp.kernel == HEADS_K_FUSED3, env_tail = with_mheads && hp.env != 0;
     {
@@ -4509,7 +4473,7 @@ static int machine_actor_forward_impl(mtfjsp_encoder_t e, const void *m_fea1, co
     const EnvParams &EP = e->env_step.P;
     HeadsRequest rq = heads_request(e, M);
     rq.values_only = e->values_only > 0 && !e->fs[1].armed && !rq.f32 && !e->bn_mode;
-    rq.env_tail = e->env_step.armed && e->fuse_env && !e->timing && !e->bn_mode && !rq.f32 && e->fs[1].armed &&
+    rq.env_tail = e->env_step.armed && e->sw.fuse_env && !e->timing && !e->bn_mode && !rq.f32 && e->fs[1].armed &&
                   (const void *)e->fs[1].idx == (const void *)EP.mach_idx && EP.B == B && EP.M == M && env_one_slot(EP.J, EP.M, EP.T);
     if (rq.env_tail) rq.obs_f64 = !EP.obs_f32;
     const HeadsPlan hp = heads_plan(rq);
@@ -4629,7 +4593,7 @@ extern "C" int mtfjsp_encoder_check(mtfjsp_encoder_t e, int32_t *gin_resident_ou
     HIPCHK(e, hipSetDevice(e->cfg.device_id));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     int rc = res_poll_failure(e);                                  // (the stream is idle: the word is final)
-    if (!rc && e->res_eligible && !e->res_ok && e->res_failures > 0 && !getenv("MTFJSP_NO_RESIDENT_GIN")) {
+    if (!rc && e->res_eligible && !e->res_ok && e->res_failures > 0 && !enc_no_resident_gin()) {
         // a failure was reported earlier: the stream is idle now, so the census can run again; when the device holds the whole
         // grid again the single launch comes back (one transient overlap does not leave the handle on the slow path for good)
         e->res_ok = res_census(e);
@@ -4640,7 +4604,7 @@ extern "C" int mtfjsp_encoder_check(mtfjsp_encoder_t e, int32_t *gin_resident_ou
 extern "C" const char *mtfjsp_gin_res_kernel_name_for(int32_t batch, int32_t rows_per_instance, int32_t n_job, int32_t candidates, int32_t num_cu,
                                                       int32_t node_output, int32_t *ipc_out, int32_t *grid_out)
 {
-    const GinResPlan pl = gin_res_plan(batch, rows_per_instance, n_job, candidates, num_cu, node_output != 0, getenv("MTFJSP_GIN_RES_GENERIC"));
+    const GinResPlan pl = gin_res_plan(batch, rows_per_instance, n_job, candidates, num_cu, node_output != 0, enc_gin_res_generic());
     if (ipc_out) *ipc_out = pl.ipc;
     if (grid_out) *grid_out = pl.grid;
     return pl.eligible ? GIN_RES_KERNEL_NAME[pl.kernel] : nullptr;
@@ -4666,16 +4630,12 @@ extern "C" int32_t mtfjsp_gin_launches_for(int32_t batch, int32_t rows_per_insta
                                            uint32_t flags, char *buf, int32_t buf_len, int32_t *order_out, int32_t *pool_out)
 {
     if (batch < 1 || rows_per_instance < 1 || n_job < 1 || candidates < 0 || num_cu < 1 || product_mode < 0 || product_mode > 31) return MTFJSP_ERR_ARG;
-    auto env_int = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
     GinRequest q{};
+    gin_request_switches(q, enc_switches_read());
     q.B = batch; q.T = rows_per_instance; q.n_job = n_job; q.J = candidates; q.num_cu = num_cu; q.obs_f64 = flags & MTFJSP_GIN_OBS_F64;
     q.job_actor = !(flags & MTFJSP_GIN_CRITIC); q.h_nodes = flags & MTFJSP_GIN_NODE_OUTPUT; q.per_instance = flags & MTFJSP_GIN_PER_INSTANCE;
-    q.res_ok = !(flags & MTFJSP_GIN_NO_SINGLE) && !getenv("MTFJSP_NO_RESIDENT_GIN"); q.reduce = flags & MTFJSP_GIN_REDUCE; q.f32_products = product_mode;
+    q.res_ok = !(flags & MTFJSP_GIN_NO_SINGLE) && !enc_no_resident_gin(); q.reduce = flags & MTFJSP_GIN_REDUCE; q.f32_products = product_mode;
     q.last_wx6 = true;
-    q.fuse_pair = env_int("MTFJSP_FUSE_PAIR", 0); q.fuse_gin0 = env_int("MTFJSP_FUSE_GIN0", 1); q.fuse_pool = env_int("MTFJSP_FUSE_POOL", 1);
-    q.stream_order = getenv("MTFJSP_NO_STREAM_ORDER") ? 0 : 1; q.stream_nt = env_int("MTFJSP_STREAM_NT", 5); q.pool_s = env_int("MTFJSP_POOL_S", 4);
-    q.heads_pool_maxT = env_int("MTFJSP_FUSE_POOL_MAXT", 64);
-    q.force_generic = getenv("MTFJSP_GIN_RES_GENERIC");
     return gin_plan_report(gin_plan(q), buf, buf_len, order_out, pool_out);
 }
 extern "C" int32_t mtfjsp_encoder_gin_launches(mtfjsp_encoder_t e, char *buf, int32_t buf_len, int32_t *order_out, int32_t *pool_out)
@@ -4686,7 +4646,7 @@ extern "C" int32_t mtfjsp_encoder_gin_launches(mtfjsp_encoder_t e, char *buf, in
 }
 extern "C" const char *mtfjsp_fused3_kernel_name_for(int32_t batch, int32_t n_job, int32_t n_machine, int32_t num_cu, int32_t obs_f64, int32_t env_tail, int32_t *grid_out)
 {
-    const Fused3Plan pl = fused3_plan(batch, n_job, n_machine, n_job * n_machine, num_cu, obs_f64 != 0, getenv("MTFJSP_FUSED3_NODES_HBM"), env_tail != 0, getenv("MTFJSP_FUSED3_GENERIC"));
+    const Fused3Plan pl = fused3_plan_switches(batch, n_job, n_machine, n_job * n_machine, num_cu, obs_f64 != 0, env_tail != 0, enc_switches_read());
     if (grid_out) *grid_out = pl.grid;
     return pl.eligible ? FUSED3_KERNEL_NAME[pl.kernel] : nullptr;
 }
@@ -4695,11 +4655,10 @@ extern "C" const char *mtfjsp_heads_kernel_name_for(int32_t batch, int32_t rows_
 {
     if (batch < 1 || rows_per_instance < 1 || n_machine < 1 || task_rows < 1 || num_cu < 1) return nullptr;
     HeadsRequest q{};
+    heads_request_switches(q, enc_switches_read());
     q.B = batch; q.R = rows_per_instance; q.M = n_machine; q.T = task_rows; q.num_cu = num_cu;
     q.gat = flags & MTFJSP_HEADS_GAT; q.mheads = flags & MTFJSP_HEADS_MHEADS; q.env_tail = flags & MTFJSP_HEADS_ENV_TAIL; q.values_only = flags & MTFJSP_HEADS_VALUES_ONLY;
     q.f32 = flags & MTFJSP_HEADS_F32; q.gat_ok = !(flags & MTFJSP_HEADS_NO_GAT); q.mheads_ok = !(flags & MTFJSP_HEADS_NO_MHEADS); q.obs_f64 = flags & MTFJSP_HEADS_OBS_F64;
-    q.hg8 = !getenv("MTFJSP_NO_HEADS_HG8"); q.heads10 = !getenv("MTFJSP_NO_HEADS10"); q.nodes_hbm = getenv("MTFJSP_FUSED3_NODES_HBM") != nullptr;
-    q.force_generic = getenv("MTFJSP_FUSED3_GENERIC");
     const HeadsPlan pl = heads_plan(q);
     if (group_out) *group_out = pl.hg;
     if (grid_out) *grid_out = pl.grid;

@@ -81,10 +81,10 @@ struct GinRequest {
     bool reduce;                          // a statistics reduction over several shards is installed
     int f32_products;                     // product mode (mtfjsp_encoder_set_product_mode)
     bool last_wx6;                        // the last Linear has its split-product weight image
-    // the switches, by value
-    int fuse_pair, fuse_gin0, fuse_pool;  // MTFJSP_FUSE_PAIR (0), MTFJSP_FUSE_GIN0 (1), MTFJSP_FUSE_POOL (1)
-    int stream_order, stream_nt, pool_s;  // !MTFJSP_NO_STREAM_ORDER, MTFJSP_STREAM_NT (5), MTFJSP_POOL_S (4)
-    int heads_pool_maxT;                  // MTFJSP_FUSE_POOL_MAXT (64)
+    // the switches, by value (names' defaults and when each is read: mtfjsp_enc_switches.h, which fills these fields)
+    int fuse_pair, fuse_gin0, fuse_pool;  // MTFJSP_FUSE_PAIR, MTFJSP_FUSE_GIN0, MTFJSP_FUSE_POOL
+    int stream_order, stream_nt, pool_s;  // !MTFJSP_NO_STREAM_ORDER, MTFJSP_STREAM_NT, MTFJSP_POOL_S
+    int heads_pool_maxT;                  // MTFJSP_FUSE_POOL_MAXT
     const char *force_generic;            // the value of MTFJSP_GIN_RES_GENERIC or nullptr
 };
 

@@ -31,7 +31,7 @@ struct HeadsRequest {
     // the handle's answers
     bool f32;                             // product mode bit 4: the heads run the f32 matrix instruction
     bool gat_ok, mheads_ok;               // the handle's half of gat_fusable / mheads_fusable (switches, modes, weight images, the census) holds
-    bool hg8, heads10;                    // !MTFJSP_NO_HEADS_HG8; !MTFJSP_NO_HEADS10 and the device grants k_headsx10 its LDS
+    bool hg8, heads10;                    // !MTFJSP_NO_HEADS_HG8; !MTFJSP_NO_HEADS10 and the device grants k_headsx10 its LDS (read in mtfjsp_enc_switches.h, like the two below)
     bool nodes_hbm;                       // MTFJSP_FUSED3_NODES_HBM
     bool obs_f64;                         // the observation dtype the riding parts read
     const char *force_generic;            // the value of MTFJSP_FUSED3_GENERIC or nullptr

@@ -899,8 +899,8 @@ const char *mtfjsp_encoder_gin_res_kernel_name(mtfjsp_encoder_t e);
  *   MTFJSP_GIN_NO_SINGLE     the handle's census of co-resident workgroups has not passed (or a launch has timed out since)
  *   MTFJSP_GIN_REDUCE        a statistics reduction is installed (mtfjsp_encoder_set_stats_reduce)
  * The weights are taken as loaded.  MTFJSP_FUSE_PAIR, MTFJSP_FUSE_GIN0, MTFJSP_FUSE_POOL, MTFJSP_NO_STREAM_ORDER, MTFJSP_STREAM_NT, MTFJSP_POOL_S,
- * MTFJSP_FUSE_POOL_MAXT, MTFJSP_NO_RESIDENT_GIN and MTFJSP_GIN_RES_GENERIC are read per call under the names and defaults a handle uses (a handle reads
- * them when it is created, MTFJSP_FUSE_POOL_MAXT once per process, MTFJSP_GIN_RES_GENERIC per forward).
+ * MTFJSP_FUSE_POOL_MAXT, MTFJSP_NO_RESIDENT_GIN and MTFJSP_GIN_RES_GENERIC are read per call, through the reader a handle uses (their defaults, and
+ * when a handle reads each — MTFJSP_FUSE_POOL_MAXT only once per process —: csrc/mtfjsp_enc_switches.h and the table "Encoder switches" of DESIGN.md).
  * buf receives "path;pooling form;family:kernel,family:kernel,...": path = "per_instance" | "single_launch" | "streaming"; pooling form = "gin_kernel"
  * (the per-instance / single-launch kernel itself) | "heads" (the job actor's heads launch) | "epilogue" (the epilogue of a second pass of the last
  * product, + k_cand_fixup) | "pool_gather" (k_job_pool_gather); then each launch's timing family (mtfjsp_encoder_timing_query) and kernel.
@@ -951,7 +951,7 @@ const char *mtfjsp_encoder_fused3_kernel_name(mtfjsp_encoder_t e);
  * GAT and machine heads asked for and allowed, shape eligible); "k_headsx_gat3x" (GAT asked for and allowed; whole groups of 16 in one round of
  * workgroups, a grid as wide as the GAT launch's own); "k_headsx_envstep"; "k_headsx_values"; "k_headsx10" (a full group has 7 to 10 tiles of 16 rows);
  * "k_headsx".  Groups of 8 instances only where nothing rides and 2 * ceil(batch / 16) <= num_cu.  MTFJSP_NO_HEADS_HG8, MTFJSP_NO_HEADS10,
- * MTFJSP_FUSED3_NODES_HBM and MTFJSP_FUSED3_GENERIC are read per call (a handle reads the first three when it is created).  *group_out / *grid_out
+ * MTFJSP_FUSED3_NODES_HBM and MTFJSP_FUSED3_GENERIC are read per call (a handle: csrc/mtfjsp_enc_switches.h).  *group_out / *grid_out
  * (may be NULL): instances per workgroup, workgroups.  NULL: a size below 1.
  * mtfjsp_encoder_heads_kernel_name: the kernel that computed the handle's last job (which = 0) / machine (which = 1) forward, with its group size and
  * grid — for a machine forward that the job forward's launch had already run, the three-in-one launch.  NULL: no such forward yet. */
