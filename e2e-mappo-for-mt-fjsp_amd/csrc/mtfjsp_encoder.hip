@@ -4236,6 +4236,15 @@ static HeadsRequest heads_request(const mtfjsp_encoder *e, int R)
     q.obs_f64 = e->cfg.obs_dtype == MTFJSP_OBS_F64;
     return q;
 }
+// The ONE place that takes every arm off the handle (the contract: include/mtfjsp.h, "One-shot arms") — and, with them, what a launch did ahead for
+// the pair they were made for (the selection a three-in-one launch consumed would be armed again by the next machine forward).  Reached from every
+// error return of the two actor forwards (armed_forward) and from mtfjsp_encoder_check when it reports a failure.
+static void disarm(mtfjsp_encoder *e)
+{
+    e->fs[0].armed = e->fs[1].armed = false; e->fs1_consumed = mtfjsp_encoder::FusedSample{};
+    e->mf_armed = false; e->mh.armed = false; e->env_step.armed = false; e->values_only = 0;
+    e->prefused.valid = false; e->prefused.heads = false;
+}
 static void arm_sampling(mtfjsp_encoder *e, int which, HeadArgs &ha)
 {
     mtfjsp_encoder::FusedSample &f = e->fs[which];
@@ -4296,7 +4305,9 @@ static int job_actor_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea, con
                                   const int32_t *candidate, const uint8_t *job_mask, const float *h_m_prev,
                                   float *prob, float *h_pooled, float *job_v, float *h_nodes)
 {
-    if (!e || !tasks_fea || !ell_col || !ell_val || !candidate || !job_mask || !prob || !h_pooled || !job_v) return MTFJSP_ERR_ARG;
+    if (!e) return MTFJSP_ERR_ARG;
+    e->env_step.done = false;                                       // mtfjsp_encoder_env_step_fused speaks of THIS forward pair: set below / by the machine forward when an armed step rides
+    if (!tasks_fea || !ell_col || !ell_val || !candidate || !job_mask || !prob || !h_pooled || !job_v) return MTFJSP_ERR_ARG;
     int rc = mtfjsp_encoder_weights_ready(e);
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device_id));
@@ -4456,6 +4467,7 @@ static int machine_actor_forward_impl(mtfjsp_encoder_t e, const void *m_fea1, co
         e->prefused.heads = false; e->prefused.valid = false;
         e->fs1_consumed = mtfjsp_encoder::FusedSample{};
         e->env_step.armed = false;                                    // (env_step.done: set by the job forward whose launch ran this forward — and the armed step, if it could)
+        if (e->values_only > 0) e->values_only--;                     // (this forward's half of an armed values-only pair: the count does not outlive the pair)
         e->fs[1].armed = false;                                       // (a selection armed again for this call has been made already)
         e->heads_last[1] = e->heads_last[0];                          // (that launch computed this forward)
         return MTFJSP_OK;
@@ -4558,16 +4570,25 @@ static int global_critic_forward_impl(mtfjsp_encoder_t e, const void *tasks_fea,
 #define GUARDED(e, call)                                                                               \
     try { return call; }                                                                               \
     catch (const std::exception &ex) { if (e) (e)->err = std::string("missing weight or internal error: ") + ex.what(); return MTFJSP_ERR_STATE; }
+// ... and an actor forward that returns an error, whichever return it took, leaves nothing armed on the handle
+template <class F> static int armed_forward(mtfjsp_encoder_t e, F &&forward)
+{
+    int rc = MTFJSP_ERR_STATE;
+    try { rc = forward(); }
+    catch (const std::exception &ex) { if (e) e->err = std::string("missing weight or internal error: ") + ex.what(); }
+    if (rc && e) disarm(e);
+    return rc;
+}
 extern "C" int mtfjsp_job_actor_forward(mtfjsp_encoder_t e, const void *tasks_fea, const int32_t *ell_col, const float *ell_val,
                                         const int32_t *candidate, const uint8_t *job_mask, const float *h_m_prev,
                                         float *prob, float *h_pooled, float *job_v, float *h_nodes)
 {
-    GUARDED(e, job_actor_forward_impl(e, tasks_fea, ell_col, ell_val, candidate, job_mask, h_m_prev, prob, h_pooled, job_v, h_nodes))
+    return armed_forward(e, [&] { return job_actor_forward_impl(e, tasks_fea, ell_col, ell_val, candidate, job_mask, h_m_prev, prob, h_pooled, job_v, h_nodes); });
 }
 extern "C" int mtfjsp_machine_actor_forward(mtfjsp_encoder_t e, const void *m_fea1, const void *m_fea2, const float *h_pooled_o,
                                             const uint8_t *mmask, float *prob, float *h_pooled, float *machine_v)
 {
-    GUARDED(e, machine_actor_forward_impl(e, m_fea1, m_fea2, h_pooled_o, mmask, prob, h_pooled, machine_v))
+    return armed_forward(e, [&] { return machine_actor_forward_impl(e, m_fea1, m_fea2, h_pooled_o, mmask, prob, h_pooled, machine_v); });
 }
 extern "C" int mtfjsp_global_critic_forward(mtfjsp_encoder_t e, const void *tasks_fea, const int32_t *ell_col, const float *ell_val,
                                             const void *m_fea1, const void *m_fea2, float *value4)
@@ -4593,6 +4614,7 @@ extern "C" int mtfjsp_encoder_check(mtfjsp_encoder_t e, int32_t *gin_resident_ou
     HIPCHK(e, hipSetDevice(e->cfg.device_id));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     int rc = res_poll_failure(e);                                  // (the stream is idle: the word is final)
+    if (rc) disarm(e);                                             // (the forwards the arms were made for are void)
     if (!rc && e->res_eligible && !e->res_ok && e->res_failures > 0 && !enc_no_resident_gin()) {
         // a failure was reported earlier: the stream is idle now, so the census can run again; when the device holds the whole
         // grid again the single launch comes back (one transient overlap does not leave the handle on the slow path for good)

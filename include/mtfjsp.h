@@ -765,6 +765,15 @@ typedef struct {
                                          * — the mtfjsp_machine_actor_forward that follows with exactly these two pointers skips them */
 } mtfjsp_mfea1_ctx_t;
 int mtfjsp_get_mfea1_context(mtfjsp_handle_t h, void *m_fea1_out, uint8_t *mmask_out, mtfjsp_mfea1_ctx_t *ctx);
+/* ---- One-shot arms: mtfjsp_encoder_arm_selection (which = 0, 1), _arm_mfea1, _arm_machine_heads, _arm_env_step, _arm_values_only.
+ * AN ARM BELONGS TO THE NEXT CALL OF THE FORWARD IT NAMES, AND TO NO LATER CALL.  A forward that returns MTFJSP_OK takes what is its
+ * own: a job forward that does not run the machine heads itself leaves the machine selection and the environment step to the machine
+ * forward that follows, and a values-only pair is one job forward and one machine forward.  A forward that returns an error — any
+ * error, from any of its checks: MTFJSP_ERR_RETRY at its entry, MTFJSP_ERR_ARG, MTFJSP_ERR_STATE, MTFJSP_ERR_HIP — leaves
+ * NOTHING armed on the handle: the pair the arms were made for is void (and so is work a launch did ahead for it).  mtfjsp_encoder_check does the same when it returns MTFJSP_ERR_RETRY.  The caller arms again for the
+ * forwards it repeats; no later forward ever selects, writes m_fea1, runs the machine heads or steps the environment through
+ * pointers armed for an earlier one.  mtfjsp_encoder_env_step_fused() speaks of the last forward pair only: 0 after any pair that
+ * had no armed step, whichever launch served it. */
 /* The WHOLE machine actor forward (ac:359-498) inside the job actor's heads launch: three launches per rollout step.  With these
  * outputs armed (prob [B,M], h_pooled [B,H], machine_v [B,2]; one-shot), a machine selection armed (mtfjsp_encoder_arm_selection,
  * which = 1) and an mfea1 context with m_fea2 (above), the NEXT mtfjsp_job_actor_forward — where the shape allows it: one workgroup
