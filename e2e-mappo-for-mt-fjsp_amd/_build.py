@@ -6,7 +6,7 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmtfjsp.so")
-SOURCES = ["mtfjsp_env.hip", "mtfjsp_encoder.hip", "mtfjsp_gin_res.hip", "mtfjsp_pdr.hip", "mtfjsp_lookahead.hip", "mtfjsp_beam.hip", "mtfjsp_group.hip", "mtfjsp_plan.hip", "mtfjsp_evolve.hip", "mtfjsp_nsga.hip", "mtfjsp_walk.hip", "mtfjsp_replay.hip", "mtfjsp_hostgen.cpp"]
+SOURCES = ["mtfjsp_env.hip", "mtfjsp_encoder.hip", "mtfjsp_gin_res.hip", "mtfjsp_pdr.hip", "mtfjsp_lookahead.hip", "mtfjsp_beam.hip", "mtfjsp_policy_beam.hip", "mtfjsp_group.hip", "mtfjsp_plan.hip", "mtfjsp_evolve.hip", "mtfjsp_nsga.hip", "mtfjsp_walk.hip", "mtfjsp_replay.hip", "mtfjsp_hostgen.cpp"]
 # -ffp-contract=off: the scheduling state must follow the reference's binary64 operation order exactly
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall"]
 # per translation unit (round 6, A/B on one box with the whole library built either way): hipcc's max-ILP scheduling strategy shortens the step kernels

@@ -203,6 +203,24 @@ BEAM_MAX_WIDTH, BEAM_MAX_CANDIDATES = 64, 8192
 BEAM_SCRATCH_BATCH = 262144          # the chip-filling batch: what one pass of beam_baselines keeps in flight
 
 
+def _backtrack(beam, N, W, s, hist, start_slot):
+    """mtfjsp_beam_backtrack over the first s rows of `hist` (from_slot, task, mach: [cap, N*W] each) from slot start_slot[n] (None:
+    slot 0) of the beam handle `beam` -> (task[N,s], mach[N,s]) int32 device tensors"""
+    if s < 1:
+        raise ValueError("no decision has been taken yet")
+    dev = beam.device
+    if start_slot is not None and not torch.is_tensor(start_slot):
+        start_slot = torch.as_tensor(np.ascontiguousarray(start_slot, np.int32), device=dev)
+    if start_slot is not None:
+        assert start_slot.is_cuda and start_slot.dtype == torch.int32 and start_slot.is_contiguous() and start_slot.shape == (N,)
+    task = torch.empty(N, s, dtype=torch.int32, device=dev)
+    mach = torch.empty(N, s, dtype=torch.int32, device=dev)
+    capi.check(beam.L.mtfjsp_beam_backtrack(beam.h, W, s, hist["from_slot"].data_ptr(), hist["task"].data_ptr(), hist["mach"].data_ptr(),
+                                            C.c_void_p(start_slot.data_ptr() if start_slot is not None else None),
+                                            task.data_ptr(), mach.data_ptr()), beam.h)
+    return task, mach
+
+
 class BeamSearch:
     """Beam search of width `width` from the states `src` (a reset DeviceBatchEnv of N instances) holds now: a beam handle of N*W
     instances (slot w of instance n = n*W + w) and a scratch handle of N*W*T (child (j, m) of every slot).  Constants and state are
@@ -269,20 +287,7 @@ class BeamSearch:
     def plans(self, start_slot=None):
         """-> (task[N,s], mach[N,s]) int32 device tensors: the decisions that led to slot start_slot[n] (host sequence or int32
         device tensor [N]; None: slot 0, the best) of the present beam, -1 where the slot is empty or the instance had finished"""
-        if self.s < 1:
-            raise ValueError("no decision has been taken yet")
-        dev = self.src.device
-        if start_slot is not None and not torch.is_tensor(start_slot):
-            start_slot = torch.as_tensor(np.ascontiguousarray(start_slot, np.int32), device=dev)
-        if start_slot is not None:
-            assert start_slot.is_cuda and start_slot.dtype == torch.int32 and start_slot.is_contiguous() and start_slot.shape == (self.N,)
-        task = torch.empty(self.N, self.s, dtype=torch.int32, device=dev)
-        mach = torch.empty(self.N, self.s, dtype=torch.int32, device=dev)
-        h = self.hist
-        capi.check(self.src.L.mtfjsp_beam_backtrack(self.beam.h, self.W, self.s, h["from_slot"].data_ptr(), h["task"].data_ptr(), h["mach"].data_ptr(),
-                                                    C.c_void_p(start_slot.data_ptr() if start_slot is not None else None),
-                                                    task.data_ptr(), mach.data_ptr()), self.beam.h)
-        return task, mach
+        return _backtrack(self.beam, self.N, self.W, self.s, self.hist, start_slot)
 
     def run(self, column, steps=None):
         """`steps` (default T: the whole episode) decisions -> (task[N,steps], mach[N,steps], score[N,W]): the best slot's plan and
@@ -335,6 +340,188 @@ def beam_baselines(t, p, tt, edge, args, rules=BEAM_RULES, width=8, dedupe=True,
                 bs.close()
             env.close()
     return _results(names, {name: tuple(np.concatenate([x[k] for x in parts[name]]) for k in range(4)) for name in names}, T, w)
+
+
+# ---- policy-guided beam search (csrc/mtfjsp_policy_beam.hip): the beam's slots, scored by the actors' joint log-probability
+PB_TOP, PB_BEST = "PB_TOP", "PB_BEST"
+POLICY_BEAM_BATCH = 65536            # (slot, job) rows of the machine forward that one pass of policy_beam keeps in flight
+_PB_HIST = ("parent", "from_slot", "job", "task", "mach", "child")
+
+
+class PolicyBeamSearch:
+    """Beam decoding of the trained actors from the states `src` (a reset DeviceBatchEnv of N instances) holds now: the W most
+    probable partial schedules per instance, a slot's score being the running sum of log p(job) + log p(machine | job).  Two beam
+    handles of N*W instances (slot w of instance n = n*W + w) take turns, both forked from `src` with constants, state and
+    observation here (and again by `restart`), so every slot always holds some valid state; an `Encoder` of batch N*W runs the job
+    forwards and one of batch N*W*J the machine forwards, both with per-instance BatchNorm (a slot's forward does not depend on its
+    neighbours).  weights: (job actor, machine actor) state dicts.  The scores start as [0, -inf, ...] per instance.
+    `advance()` is one decision: the job forward on the current beam (with the embedding every slot carries from the machine
+    forward of its last decision; none at decision 0), m_fea1 of every job's candidate task, ONE machine forward over all (slot,
+    job) rows, the two logarithms (torch.log of the binary64 probabilities), the selection of the W best (slot, job, machine) into
+    row s of the history, the fork of the winners' slots into the other handle, its step with the chosen actions, the carried
+    embedding and — with `dedupe` — the merge of slots that hold one partial schedule (the later, less probable one is emptied
+    and refilled by the next selection).  Only the W kept children are stepped.  Nothing is read back; everything runs on the
+    stream that was current at construction.  A rank without a candidate has parent -1 (the fork leaves its slot untouched) and
+    task -1 (the step rejects it).  A forward that reports capi.ERR_RETRY raises MtfjspError: there is no retry loop.
+    on_decision(s, tensors) (tests): called at the end of decision s with that decision's device tensors — inputs, probabilities,
+    logarithms, outputs, signatures; they are overwritten by the next decision."""
+
+    def __init__(self, src, weights, width, dedupe=True, on_decision=None):
+        from .encoder import Encoder
+        W = int(width)
+        if not 1 <= W <= BEAM_MAX_WIDTH or W * src.T > BEAM_MAX_CANDIDATES:
+            raise ValueError(f"beam width must be 1..{BEAM_MAX_WIDTH} with width * n_job * n_machine <= {BEAM_MAX_CANDIDATES}")
+        self.src, self.W, self.dedupe, self.on_decision = src, W, bool(dedupe), on_decision
+        N, T, J, M, dev = src.B, src.T, src.J, src.M, src.device
+        self.N, self.T = N, T
+        NW = N * W
+        obs = "f32" if src.obs_f32 else "f64"
+        self.cur = self.nxt = self.enc_job = self.enc_mach = None
+        try:
+            self.cur, self.nxt = DeviceBatchEnv.like(src, NW), DeviceBatchEnv.like(src, NW)
+            self.enc_job = Encoder(J, M, NW, device=dev.index or 0, obs_dtype=obs)
+            self.enc_mach = Encoder(J, M, NW * J, device=dev.index or 0, obs_dtype=obs)
+            for e in (self.enc_job, self.enc_mach):
+                e.load_weights(weights[0], weights[1])
+                e.set_bn_mode(True)
+        except Exception:
+            self.close()
+            raise
+        self._beam_index = torch.arange(NW, dtype=torch.int32, device=dev) // W
+        self._job_rows = torch.arange(NW * J, dtype=torch.int64, device=dev) // J         # (slot, job) row -> slot
+        odt = torch.float32 if src.obs_f32 else torch.float64
+        self.m_fea1 = torch.empty(NW, J, M, 6, dtype=odt, device=dev)
+        self.mmask = torch.empty(NW, J, M, dtype=torch.uint8, device=dev)
+        self.sig = torch.zeros(NW, dtype=torch.int64, device=dev)
+        self.score = torch.empty(NW, dtype=torch.float64, device=dev)
+        self._score_next = torch.empty_like(self.score)
+        self.hist = {k: torch.full((T, NW), -1, dtype=torch.int32, device=dev) for k in _PB_HIST}
+        self.restart()
+
+    def restart(self):
+        """take `src`'s present state again: every slot of both handles a copy of its instance, one live slot, no history"""
+        for e in (self.cur, self.nxt):
+            e.fork_from(self.src, self._beam_index, instance=True, state=True, obs=True)
+        self.score.fill_(float("-inf"))
+        self.score.view(self.N, self.W)[:, 0] = 0.0
+        self.h_m = None                                                 # the embedding every slot carries ([N*W,128] f32)
+        self.s = 0
+
+    def advance(self):
+        """one decision of every instance; -> the decision's history row index.  `self.score` [N*W] then holds the new scores and
+        `self.cur` the new beam."""
+        s, cur, nxt, W, J = self.s, self.cur, self.nxt, self.W, self.src.J
+        if s >= self.hist["task"].shape[0]:
+            old = self.hist
+            self.hist = {k: torch.full((2 * s, v.shape[1]), -1, dtype=torch.int32, device=v.device) for k, v in old.items()}
+            for k, v in old.items():
+                self.hist[k][:s].copy_(v)
+        ej, em = self.enc_job, self.enc_mach
+        job_prob, h_o, _ = ej.job_actor_forward(cur.tasks_fea, cur.ell_col, cur.ell_val, cur.candidate, cur.job_mask, self.h_m)
+        cur.observe_mfea1_jobs(self.m_fea1, self.mmask)
+        m_fea2 = cur.m_fea2.index_select(0, self._job_rows)            # [N*W*J,M,8]: a slot's machines, once per job
+        h_o_rows = h_o.index_select(0, self._job_rows)                 # [N*W*J,128]
+        mch_prob, h_mach, _ = em.machine_actor_forward(self.m_fea1, m_fea2, h_o_rows, self.mmask)
+        logp_job, logp_mach = torch.log(job_prob.double()), torch.log(mch_prob.double())
+        h = {k: v[s] for k, v in self.hist.items()}
+        capi.check(cur.L.mtfjsp_beam_select_policy(cur.h, W, self.score.data_ptr(), logp_job.data_ptr(), logp_mach.data_ptr(), self.mmask.data_ptr(),
+                                                   *[h[k].data_ptr() for k in _PB_HIST], self._score_next.data_ptr()), cur.h)
+        nxt.fork_from(cur, h["parent"], instance=False, state=True, obs=True)
+        nxt.step(h["task"], h["mach"])
+        h_m_prev, self.h_m = self.h_m, h_mach.index_select(0, h["child"].clamp(min=0).long())
+        selected = self._score_next.clone() if self.on_decision is not None else None
+        if self.dedupe:
+            nxt.state_signature(self.sig)
+            capi.check(cur.L.mtfjsp_beam_merge_slots(nxt.h, W, self.sig.data_ptr(), self._score_next.data_ptr()), nxt.h)
+        if self.on_decision is not None:
+            self.on_decision(s, dict(
+                beam=cur, next=nxt, candidate=cur.candidate, job_mask=cur.job_mask, h_m_prev=h_m_prev, job_prob=job_prob, h_o=h_o,
+                m_fea1=self.m_fea1, mmask=self.mmask, m_fea2=cur.m_fea2, m_fea2_rows=m_fea2, h_o_rows=h_o_rows, mch_prob=mch_prob,
+                h_mach=h_mach, logp_job=logp_job, logp_mach=logp_mach, score_in=self.score, score_selected=selected,
+                score_out=self._score_next, sig=self.sig if self.dedupe else None, h_m=self.h_m, **h))
+        self.score, self._score_next = self._score_next, self.score
+        self.cur, self.nxt = nxt, cur
+        self.s = s + 1
+        return s
+
+    def plans(self, start_slot=None):
+        """-> (task[N,s], mach[N,s]) int32 device tensors: the decisions that led to slot start_slot[n] (host sequence or int32
+        device tensor [N]; None: slot 0, the most probable) of the present beam, -1 where the slot is empty"""
+        return _backtrack(self.cur, self.N, self.W, self.s, self.hist, start_slot)
+
+    def run(self, steps=None):
+        """`steps` (default T: the whole episode) decisions -> (task[N,steps], mach[N,steps], score[N,W]): the most probable slot's
+        plan and every slot's joint log-probability (-inf: empty)"""
+        for _ in range(self.T if steps is None else int(steps)):
+            self.advance()
+        task, mach = self.plans()
+        return task, mach, self.score.view(self.N, self.W)
+
+    def close(self):
+        for e in (self.enc_job, self.enc_mach):
+            if e is not None:
+                e.set_bn_mode(False)
+                e.close()
+        for e in (self.cur, self.nxt):
+            if e is not None:
+                e.close()
+        self.cur = self.nxt = self.enc_job = self.enc_mach = None
+
+
+def policy_beam(weights, t, p, tt, edge, args, width=8, dedupe=True, chunk=None, device=0, obs_dtype="f32", left_shift=True, on_decision=None):
+    """Beam decoding of the policy `weights` ((job actor, machine actor) state dicts, as for `evaluate.validate_cost_batched`) on the
+    N instances t, p [N,T,M], tt [N,M,M], edge [N,E,M/E]; args as for `pdr_baselines`; left shift on, as the policy's evaluations
+    have it.  Per pass a `PolicyBeamSearch` of width `width` runs the T decisions of the episode; then `final_costs` of the last
+    beam and `group_reduce(n, W)` over its live slots give every instance's finished slot with the smallest Objective.  Two plans
+    per instance are read out through the back-pointers and replayed on the plain handle step by step, as `beam_baselines` replays
+    its plan: PB_TOP, slot 0 — the most probable finished schedule the beam holds —, and PB_BEST, the cheapest one (lowest slot on
+    ties).  width = 1 is the joint arg-max of p(job) * p(machine | job) at every decision, which is not the sequential greedy of
+    `validate_cost_batched` (the most probable job first, then its most probable machine).
+    chunk: bounds (source instances per pass) * width * n_job, the rows of the machine forward (None: POLICY_BEAM_BATCH).  The
+    results are NOT promised to be bit-independent of chunk: which kernels the forwards run follows their batch.
+    on_decision(s, tensors): handed to every pass's `PolicyBeamSearch` (tests).
+    -> {"PB_TOP", "PB_BEST": (cost_dict_cumsum, Final_4cost, Objective)} in `pdr_baselines`' layout, under PLANS both plans
+    {name: (task[N,T], mach[N,T])}, and "logp" [N,W]: every final slot's joint log-probability (descending; -inf: empty or merged)."""
+    J, M, E, T, w, kw = parse_args(args, left_shift=left_shift, obs_dtype=obs_dtype, device=device)
+    W = int(width)
+    t, p, tt, edge = np.asarray(t, np.float64), np.asarray(p, np.float64), np.asarray(tt, np.float64), np.asarray(edge)
+    N = t.shape[0]
+    chunk = POLICY_BEAM_BATCH if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    per_pass = max(1, chunk // (W * J))
+    names = [PB_TOP, PB_BEST]
+    parts, logp = {name: [] for name in names}, []
+    for lo in range(0, N, per_pass):
+        hi = min(N, lo + per_pass)
+        n = hi - lo
+        env = DeviceBatchEnv(J, M, E, n, **kw)
+        pb = None
+        try:
+            env.load_instances(t[lo:hi], p[lo:hi], tt[lo:hi], edge=edge[lo:hi])
+            w3 = config_w3(env, w)
+            eval_reset(env, w3)
+            pb = PolicyBeamSearch(env, weights, W, dedupe, on_decision=on_decision)
+            top_t, top_m, score = pb.run(T)
+            cost4, done = pb.cur.final_costs()
+            done &= (score.reshape(-1) != float("-inf")).to(torch.uint8)            # an emptied slot is nobody's best
+            _, best, _, _ = env.group_reduce(n, W, cost4, done, w, obj=False, best_obj=False, front=False)
+            if int(best.min().item()) < 0:
+                raise RuntimeError("policy-beam search: an instance has no finished slot")
+            best_t, best_m = pb.plans(best - torch.arange(n, dtype=torch.int32, device=env.device) * W)
+            logp.append(score.cpu().numpy().copy())
+            for name, (task, mach) in ((PB_TOP, (top_t, top_m)), (PB_BEST, (best_t, best_m))):
+                eval_reset(env, w3)
+                ts, ms = task.t().contiguous(), mach.t().contiguous()   # [T,n]: row s = the actions of step s
+                cum, prev = replay_episode(env, T, lambda s: (ts[s], ms[s]), "policy-beam")
+                parts[name].append((cum, prev, task.cpu().numpy(), mach.cpu().numpy()))
+        finally:
+            if pb is not None:
+                pb.close()
+            env.close()
+    out = _results(names, {name: tuple(np.concatenate([x[k] for x in parts[name]]) for k in range(4)) for name in names}, T, w)
+    out["logp"] = np.concatenate(logp)
+    return out
 
 
 # ---- the random dispatch rule as best-of-K (csrc/mtfjsp_group.hip): K uniformly random episodes per instance, the best kept

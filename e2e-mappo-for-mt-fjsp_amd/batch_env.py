@@ -578,6 +578,16 @@ class DeviceBatchEnv:
         capi.check(self.L.mtfjsp_observe_mfea1(self.h, task_idx.data_ptr(), mm, self.m_fea1.data_ptr(), self.mmask.data_ptr()), self.h)
         return self.m_fea1
 
+    def observe_mfea1_jobs(self, out=None, mmask_out=None):
+        """m_fea1 and the machine mask of EVERY job's candidate task (mtfjsp_observe_mfea1_jobs: one launch, nothing read back):
+        row (b, j) is what `observe_mfea1` writes for task_idx[b] = candidate[b][j].  -> (out [B,J,M,6] observation dtype,
+        mmask_out [B,J,M] uint8) device tensors; either may be given to write into"""
+        B, J, M = self.B, self.J, self.M
+        out = _out(True if out is None else out, (B, J, M, 6), torch.float32 if self.obs_f32 else torch.float64, self.device)
+        mmask_out = _out(True if mmask_out is None else mmask_out, (B, J, M), torch.uint8, self.device)
+        capi.check(self.L.mtfjsp_observe_mfea1_jobs(self.h, out.data_ptr(), mmask_out.data_ptr()), self.h)
+        return out, mmask_out
+
     def mfea1_context(self):
         """device-pointer recipe of observe_mfea1 (-> self.m_fea1, self.mmask) for the encoder's heads kernel to execute right
         after it has selected the task (capi.Mfea1Ctx; valid while the instances stay loaded)"""

@@ -84,6 +84,9 @@ PROTOTYPES = {
     "mtfjsp_state_signature": (_I, [_VP, _VP]),
     "mtfjsp_beam_select": (_I, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_beam_backtrack": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mtfjsp_observe_mfea1_jobs": (_I, [_VP, _VP, _VP]),
+    "mtfjsp_beam_select_policy": (_I, [_VP, C.c_int32] + [_VP] * 11),
+    "mtfjsp_beam_merge_slots": (_I, [_VP, C.c_int32, _VP, _VP]),
     "mtfjsp_final_costs": (_I, [_VP, _VP, _VP]),
     "mtfjsp_group_reduce": (_I, [_VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mtfjsp_replay_plans": (_I, [_VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int32]),

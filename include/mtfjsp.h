@@ -305,6 +305,47 @@ int mtfjsp_beam_select(mtfjsp_handle_t scratch, mtfjsp_handle_t beam, int32_t W,
 int mtfjsp_beam_backtrack(mtfjsp_handle_t h, int32_t W, int32_t S, const int32_t *hist_from_slot, const int32_t *hist_task,
                           const int32_t *hist_mach, const int32_t *start_slot, int32_t *task_plan, int32_t *mach_plan);
 
+/* ------------------------------------------------------------------ policy-guided beam search on the fork */
+/* Beam decoding of the trained actors: a slot's score is the running sum of log p(job) + log p(machine | job) along its decisions,
+ * and only the W children that are kept are stepped.  Two beam handles of N*W instances take turns (mtfjsp_fork needs distinct
+ * handles).  One decision on the current one: mtfjsp_job_actor_forward (batch N*W), mtfjsp_observe_mfea1_jobs, ONE
+ * mtfjsp_machine_actor_forward over all N*W*n_job (slot, job) rows, the two logarithms, mtfjsp_beam_select_policy,
+ * mtfjsp_fork(next, current, parent_out, STATE | OBS), mtfjsp_step(next, task_out, mach_out), optionally
+ * mtfjsp_state_signature(next) + mtfjsp_beam_merge_slots; mtfjsp_beam_backtrack reads the plans out as for the cost beam.
+ * The reference decodes greedily or by sampling only (validate.py:60-297).
+ *
+ * mtfjsp_observe_mfea1_jobs: out [B, n_job, n_machine, 6] in the handle's observation dtype, mmask_out [B, n_job, n_machine] bytes
+ * (may be NULL).  Row (b, j) is, bit for bit, what mtfjsp_observe_mfea1 writes for task_idx[b] = candidate[b][j] (the handle's bound
+ * observation field) with mmask_in = NULL — for every job, masked or not; an index outside [0, T) is treated as there (task 0).
+ * One launch on the handle's stream, nothing read back.  MTFJSP_ERR_STATE: no reset, or no bound observations.  MTFJSP_ERR_ARG,
+ * nothing written: out NULL, or the two outputs overlap.
+ *
+ * mtfjsp_beam_select_policy: beam holds N*W slots (slot w of source n = instance n*W + w) with bound candidate and job_mask.
+ * score_in [N*W] f64, logp_job [N*W, n_job] f64, logp_mach [N*W*n_job, n_machine] f64, mmask [N*W*n_job, n_machine] bytes (device).
+ * Candidate c = w*T + j*n_machine + m of source n is "slot w schedules job j's next task on machine m"; with slot = n*W + w it is
+ * eligible iff score_in[slot] != -inf, job_mask[slot][j] == 0, mmask[slot*n_job + j][m] == 0 and its value is neither NaN nor -inf;
+ * value = (score_in[slot] + logp_job[slot][j]) + logp_mach[slot*n_job + j][m] — two binary64 additions in exactly this order.  The
+ * kernel takes logarithms, not probabilities, on purpose: it holds comparisons and these two additions only, so a host model
+ * reproduces it exactly.  Ranks k = 0..W-1 in turn take the eligible candidate of the largest value, the lowest c among equals, and
+ * remove it.  Outputs, device [N*W], at n*W + k: parent_out = slot (the index of the following mtfjsp_fork), from_slot_out = w,
+ * job_out = j, task_out = the child's task (formed from beam's job records as mtfjsp_beam_select forms it), mach_out = m,
+ * child_out = slot*n_job + j (the machine forward's row: its pooled embedding is the child's), score_out = the picked candidate's own
+ * sum, bit for bit.  A rank left without a candidate writes -1 in the six integer outputs and -inf in score_out: the fork leaves that
+ * slot untouched, the step rejects task -1, and the score marks it empty.  1 <= W <= 64, beam.batch % W == 0, W*T <= 8192,
+ * score_out != score_in: otherwise MTFJSP_ERR_ARG and nothing is written.  One launch, one workgroup per source instance, on beam's
+ * stream.
+ *
+ * mtfjsp_beam_merge_slots: sig [N*W] (device u64, what mtfjsp_state_signature(h) wrote), score_inout [N*W] f64.  Slot k's score
+ * becomes -inf iff a slot k' < k of the same source has the same signature and had a score other than -inf ON ENTRY (the entry
+ * scores are staged before anything is written).  Ranks come out in score order, so the more probable representative survives; the
+ * emptied slot is refilled by the next selection.  The signature ignores what is not schedule (above) — here also the embedding a
+ * slot carries — so merging is a heuristic, as for the cost beam.  1 <= W <= 64, batch % W == 0, else MTFJSP_ERR_ARG.  One launch. */
+int mtfjsp_observe_mfea1_jobs(mtfjsp_handle_t h, void *out, uint8_t *mmask_out);
+int mtfjsp_beam_select_policy(mtfjsp_handle_t beam, int32_t W, const double *score_in, const double *logp_job, const double *logp_mach,
+                              const uint8_t *mmask, int32_t *parent_out, int32_t *from_slot_out, int32_t *job_out, int32_t *task_out,
+                              int32_t *mach_out, int32_t *child_out, double *score_out);
+int mtfjsp_beam_merge_slots(mtfjsp_handle_t h, int32_t W, const uint64_t *sig, double *score_inout);
+
 /* ------------------------------------------------------------------ groups of copies: final costs, best copy, Pareto front */
 /* Best-of-K evaluation keeps K copies of each of N instances in one handle of N*K (copy c of instance n = element n*K + c, made
  * with mtfjsp_fork and the index i / K) and lets every copy play its own episode.  These two calls reduce the copies on the
